@@ -242,6 +242,41 @@ def _latest_pmc():
     return None, {}, None
 
 
+DUMP_TABLE_ROWS = 1 << 20  # hash-table rows in the --dump-outputs sample (fixed seed): 8 MB per [rows, 2] float32 array
+DUMP_MAX_BYTES = 64 << 20
+
+
+def snapshot_outputs(trainer, model, loss):
+    """What the training step hands back after its last timed call, as float32 host arrays (--dump-outputs): the loss it
+    returned, the parameters it stepped (the MLP weights whole; the hash table and its last gradient on a fixed, seeded
+    sample of DUMP_TABLE_ROWS rows).  Collective under data parallel with a sharded table optimizer (gathers the table)."""
+    trainer.gather_table_state()
+    torch.cuda.synchronize()
+    table = trainer.table if trainer.table is not None else model.encoder.embeddings
+    rows = table.view(-1, table.shape[-1]).shape[0]
+    pick = np.sort(np.random.default_rng(0).choice(rows, size=min(rows, DUMP_TABLE_ROWS), replace=False))
+    pick_t = torch.from_numpy(pick).to(table.device)
+    out = {"loss": loss.detach().float().cpu().numpy()}
+    for name, p in model.named_parameters():
+        if p.data_ptr() == table.data_ptr() and p.numel() == table.numel():
+            out["param." + name + ".sample"] = p.detach().view(rows, -1)[pick_t].float().cpu().numpy()
+        else:
+            out["param." + name] = p.detach().float().cpu().numpy()
+    g = trainer.table_grad() if trainer.table is not None else table.grad
+    if g is not None:
+        out["grad.encoder.embeddings.sample"] = g.detach().view(rows, -1)[pick_t].float().cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit")
+    return out
+
+
+def write_outputs(directory, arrays):
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.asarray(a, dtype=np.float32))
+
+
 def run_nerfmvl(args):
     """BASELINE config 4 (secondary workload, `--workload nerfmvl`): NeRF-MVL-shaped object scene — 256 x 1800 range image,
     intrinsics (fov_up, fov) = (15, 40), scale 0.005 (configs/nerf_mvl.txt; preprocess/generate_train_rangeview.py:166-168),
@@ -336,6 +371,7 @@ def run_nerfmvl(args):
                 "timers": _hip.disable_timers() if not use_graph else {}}
 
     regions = [region(r) for r in range(n_regions)]
+    dumped = snapshot_outputs(trainer, model, regions[-1]["loss"]) if args.dump_outputs else None
     mid = sorted(regions, key=lambda g: g["elapsed"])[n_regions // 2]
     elapsed, host_ms, host_step, host_update, loss = (mid[k] for k in ("elapsed", "host_ms", "host_step", "host_update", "loss"))
     n_rays, samples, timers = mid["n_rays"], mid["samples"], mid["timers"]
@@ -375,6 +411,8 @@ def run_nerfmvl(args):
                 "note": "marched samples per launch are two orders of magnitude below the dense workload's 3.4 M: the launch "
                         "is dominated by per-launch costs (bucket images, cursors), not by bytes per point"}
     bwd_name = "lnh_grid_encode_backward_ws" if "lnh_grid_encode_backward_ws" in kernels else "lnh_grid_encode_backward"
+    if dumped is not None:
+        write_outputs(args.dump_outputs, dumped)
     print(json.dumps({
         "metric": "train rays/sec (occupancy-grid sampling + encode + MLP + ragged composite + bwd), NeRF-MVL-shaped 256x1800",
         "value": round(n_rays / elapsed, 1), "unit": "rays/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -442,6 +480,10 @@ def main():
     ap.add_argument("--no-mfma-states", action="store_true", help="skip the two fixed-state MFMA measurements (fresh table with a frozen optimizer; 600-step trained table)")
     ap.add_argument("--no-eval", action="store_true", help="skip the secondary full-frame evaluation measurement")
     ap.add_argument("--kernel-timers", action="store_true", help="HIP-event timing of every C-ABI call (adds ~4 %%)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32): the "
+                         "loss it returned, every parameter it stepped and the hash table's gradient (table and gradient "
+                         "on a fixed, seeded sample of rows); the inputs are the same on every run with the same arguments")
     args = ap.parse_args()
 
     from lidarnerf import _hip, parallel
@@ -561,6 +603,8 @@ def main():
     timers = _hip.disable_timers()
     elapsed = parallel.max_over_ranks(elapsed, device)
     loss_val = float(loss.detach().float().item())
+    # (outside the timed region, before any further step: the state the last timed step left)
+    dumped = snapshot_outputs(trainer, model, loss) if args.dump_outputs else None
     graph_info = None
     if use_graph:
         # the same number of steps launch by launch: entry-point timings for the rooflines, and the eager step time beside it
@@ -704,6 +748,8 @@ def main():
 
     if rank != 0:
         return
+    if dumped is not None:
+        write_outputs(args.dump_outputs, dumped)
     # SURVEY 8(d) asks for >= 100 steps and the median: with fewer steps the timed region is tens of milliseconds and one
     # region moves by ~2 % against the next, so the reported step time is the MEDIAN of the three regions of K steps each
     # (ms_per_step_repeats lists all three, the first being the region bracketed right after the warm-up)

@@ -1,40 +1,52 @@
-"""with `lidar-nerf_amd/` in front of the reference checkout on PYTHONPATH, the import chain of
+"""with `lidar-nerf_amd/` in front of a lidar-nerf checkout on PYTHONPATH, the import chain of
 main_lidarnerf.py (main_lidarnerf.py:6-13, 27-34, 289-324) resolves the hot-path modules from THIS package and the
-host glue (Trainer, datasets) from the reference.  Runs in a subprocess (the package's __path__ is fixed at first
-import); third-party modules the container lacks are stubbed; skipped where the reference checkout is absent."""
+host glue (Trainer, datasets) from the checkout.  The checkout is a stand-in written into a temporary directory: the
+upstream layout (a `lidarnerf/__init__.py`, `nerf/` and `dataset/` without one), its host-glue modules with the
+cross-module imports they make (nerf/utils.py:26-28, kitti360_dataset.py:10, nerfmvl_dataset.py:10), and decoys of
+every module this package provides, which fail if imported.  Runs in a subprocess (the package's __path__ is fixed at
+first import)."""
 import os
 import subprocess
 import sys
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+
+# module path -> source, relative to the stand-in checkout's root
+UPSTREAM_GLUE = {
+    "main_lidarnerf.py": "from lidarnerf.nerf.utils import Trainer, seed_everything\n",
+    "lidarnerf/__init__.py": "",
+    "lidarnerf/loss.py": "",
+    "lidarnerf/nerf/utils.py": ("from lidarnerf.dataset.base_dataset import custom_meshgrid\n"
+                                "from lidarnerf.convert import pano_to_lidar\n"
+                                "def seed_everything(seed):\n    pass\n"
+                                "class Trainer:\n    pass\n"),
+    "lidarnerf/dataset/base_dataset.py": ("def get_lidar_rays(*args, **kwargs):\n    pass\n"
+                                          "def custom_meshgrid(*args):\n    pass\n"
+                                          "class BaseDataset:\n    pass\n"),
+    "lidarnerf/dataset/kitti360_dataset.py": ("from lidarnerf.dataset.base_dataset import get_lidar_rays, BaseDataset\n"
+                                              "class KITTI360Dataset(BaseDataset):\n    pass\n"),
+    "lidarnerf/dataset/nerfmvl_dataset.py": ("from lidarnerf.dataset.base_dataset import get_lidar_rays, BaseDataset\n"
+                                             "class NeRFMVLDataset(BaseDataset):\n    pass\n"),
+}
+# modules of the upstream tree that this package shadows
+SHADOWED = ["lidarnerf/activation.py", "lidarnerf/convert.py", "lidarnerf/encoding.py", "lidarnerf/nerf/network.py",
+            "lidarnerf/nerf/network_tcnn.py", "lidarnerf/nerf/renderer.py", "lidarnerf/gridencoder/__init__.py",
+            "lidarnerf/raymarching/__init__.py", "lidarnerf/freqencoder/__init__.py", "lidarnerf/shencoder/__init__.py",
+            "lidarnerf/ffmlp/__init__.py"]
 
 SCRIPT = r'''
-import sys, types, importlib.machinery
-class _Stub(types.ModuleType):
-    def __getattr__(self, name):
-        if name.startswith("__"):
-            raise AttributeError(name)
-        return type(name, (), {})
-for name in ("cv2", "imageio", "lpips", "mcubes", "tensorboardX", "trimesh", "skimage", "skimage.metrics", "torch_ema",
-             "configargparse", "extern", "extern.chamfer3D", "extern.chamfer3D.dist_chamfer_3D", "extern.fscore"):
-    if name not in sys.modules:
-        m = _Stub(name)
-        m.__spec__ = importlib.machinery.ModuleSpec(name, None)
-        m.__path__ = []
-        sys.modules[name] = m
+import sys
 import main_lidarnerf                                    # main_lidarnerf.py:1-13
-from lidarnerf.nerf.utils import Trainer                 # the reference's host glue
+from lidarnerf.nerf.utils import Trainer                 # the upstream host glue
 from lidarnerf.nerf.network import NeRFNetwork           # main_lidarnerf.py:309
 from lidarnerf.nerf.network_tcnn import NeRFNetwork as TcnnNetwork   # main_lidarnerf.py:292 (-L)
 from lidarnerf.dataset.kitti360_dataset import KITTI360Dataset      # main_lidarnerf.py:27
 from lidarnerf.dataset.nerfmvl_dataset import NeRFMVLDataset
 import lidarnerf, lidarnerf.nerf.renderer, lidarnerf.encoding, lidarnerf.gridencoder, lidarnerf.raymarching
+upstream = sys.argv[1]
 for mod in (Trainer, KITTI360Dataset, NeRFMVLDataset, main_lidarnerf):
     f = sys.modules[mod.__module__].__file__ if hasattr(mod, "__module__") else mod.__file__
-    assert f.startswith("/root/reference/"), f
+    assert f.startswith(upstream + "/"), f
 for mod in (NeRFNetwork, TcnnNetwork, lidarnerf.nerf.renderer, lidarnerf.encoding, lidarnerf.gridencoder,
             lidarnerf.raymarching, lidarnerf.convert):
     f = sys.modules[mod.__module__].__file__ if isinstance(mod, type) else mod.__file__
@@ -48,8 +60,15 @@ print("DROPIN_OK")
 '''
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "lidarnerf")), reason="reference checkout not present")
-def test_main_lidarnerf_import_chain():
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(ROOT, "lidar-nerf_amd"), REF]))
-    r = subprocess.run([sys.executable, "-c", SCRIPT], env=env, capture_output=True, text=True, cwd="/tmp", timeout=600)
+def test_main_lidarnerf_import_chain(tmp_path):
+    upstream = tmp_path / "lidar-nerf"
+    files = dict(UPSTREAM_GLUE)
+    files.update({p: f"raise ImportError('upstream {p} imported: lidar-nerf_amd should shadow it')\n" for p in SHADOWED})
+    for rel, src in files.items():
+        path = upstream / rel
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(src)
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(ROOT, "lidar-nerf_amd"), str(upstream)]))
+    r = subprocess.run([sys.executable, "-c", SCRIPT, str(upstream)], env=env, capture_output=True, text=True,
+                       cwd=str(tmp_path), timeout=600)
     assert r.returncode == 0 and "DROPIN_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
