@@ -41,6 +41,8 @@ enum {
 
 #define LNH_MAX_LEVELS 32
 
+/* 100: the initial ABI.  101 adds gridtype 2 (tiny-cuda-nn's HashGrid lattice, below) to every grid entry point that takes
+ * a gridtype, and lnh_grid_encode_forward_mapped_ex. */
 LNH_API int lnh_version(void);
 LNH_API const char *lnh_last_error(void);
 /* "gfx950" — the only architecture this library carries code for */
@@ -55,8 +57,15 @@ LNH_API const char *lnh_build_variant(void);
  * inputs [B,D] f32 in [0,1]; embeddings [rows,C] (dtype); offsets_host [L+1] int32 ON THE HOST (the reference
  * passes a device tensor that never changes after construction: grid.py:179-193; a binding caches offsets.cpu());
  * outputs [L,B,C] (dtype) — level-major exactly like the reference (gridencoder.cu:437-438);
- * dy_dx NULL or [B,L,D,C] (dtype).  D in {2,3,4,5}, C in {1,2,4,8}; gridtype 0=hash 1=tiled; interp 0=linear
- * 1=smoothstep.  S = log2(per_level_scale), H = base resolution.
+ * dy_dx NULL or [B,L,D,C] (dtype).  D in {2,3,4,5}, C in {1,2,4,8}; gridtype 0=hash 1=tiled 2=hash on tiny-cuda-nn's
+ * lattice; interp 0=linear 1=smoothstep.  S = log2(per_level_scale), H = base resolution.
+ *
+ * gridtype 2 (since lnh_version 101) restates tiny-cuda-nn's published GridEncoding (parity with a real tiny-cuda-nn build
+ * is UNPINNED): scale, resolution, cell position and hash as gridtype 0, but a dense level has stride `resolution` (not
+ * resolution + 1), res^D rows rounded up to 8, and its row index is ALWAYS taken modulo the level's rows — the vertices at
+ * x = resolution alias the next row.  align_corners != 0 with gridtype 2 returns LNH_ERR_INVALID_ARG; so does a gridtype
+ * above 2, in every entry point that takes one.  Points outside [0,1] give zero output and no gradient (tiny-cuda-nn does
+ * not check).
  */
 LNH_API int lnh_grid_encode_forward(const float *inputs, const void *embeddings, const int32_t *offsets_host,
                                     void *outputs, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S,
@@ -404,6 +413,12 @@ LNH_API int lnh_grid_encode_forward_mapped(const float *inputs_all, const void *
                                            void *outputs_all, uint32_t B, uint32_t T_cur, uint32_t T_tot,
                                            uint32_t slot_off, uint32_t B_all, uint32_t C, uint32_t L, float S,
                                            uint32_t H, int dtype, lnh_stream_t stream);
+/* lnh_grid_encode_forward_mapped with a gridtype: 0 (hash) or 2 (tiny-cuda-nn lattice); the entry point above is this one
+ * with gridtype 0.  (lnh_version >= 101) */
+LNH_API int lnh_grid_encode_forward_mapped_ex(const float *inputs_all, const void *embeddings, const int32_t *offsets_host,
+                                              void *outputs_all, uint32_t B, uint32_t T_cur, uint32_t T_tot,
+                                              uint32_t slot_off, uint32_t B_all, uint32_t C, uint32_t L, float S,
+                                              uint32_t H, uint32_t gridtype, int dtype, lnh_stream_t stream);
 /*
  * lnh_density_mlp_forward: sigma-net 32 -> 64 -> 16 (ReLU, no bias; network.py:45-59,162-179) on features in the
  * encoder's level-major layout [16,B,2] (fp16).  Point p = r*T_cur + j writes row r*T_tot + slot_off + j of

@@ -29,7 +29,8 @@ struct LevelParams {
     uint32_t resolution;
     uint32_t hashmap_size;
     uint32_t offset;  // rows before this level
-    uint32_t flags;   // bits 0-3: dims accumulated densely; bit4 hash; bit5 pow2 table; bit6 no wrap needed
+    uint32_t flags;   // bits 0-3: dims accumulated densely; bit4 hash; bit5 pow2 table; bit6 no wrap needed;
+                      // bit7 lattice stride = resolution (tiny-cuda-nn); bit8 wrap by one compare-and-subtract
 };
 struct GridMeta {
     LevelParams lv[LNH_MAX_LEVELS];
@@ -37,7 +38,13 @@ struct GridMeta {
 struct RowMap {
     uint32_t T_cur, T_tot, slot_off, B_all;
 };
-enum { LV_HASH = 16, LV_POW2 = 32, LV_NOWRAP = 64 };
+enum { LV_HASH = 16, LV_POW2 = 32, LV_NOWRAP = 64, LV_RSTRIDE = 128, LV_WRAP1 = 256 };
+// gridtype 2: tiny-cuda-nn's lattice (its published GridEncoding: grid_index / pos_fract, restated; parity with a real
+// tiny-cuda-nn build is unpinned).  Same scale, resolution, hash and cell position as gridtype 0, but a dense level has
+// stride `resolution` (not resolution + 1) and its rows ALWAYS wrap modulo the level's rows: the +1 corner of the last cell
+// (x = resolution) aliases the next row, exactly as tiny-cuda-nn does.  A dense level there has idx <= res + ... + res^D <
+// 2 * rows, so the modulo is one compare-and-subtract (LV_WRAP1); a hashed level has rows = 2^log2_hashmap_size (mask).
+enum { kGridHash = 0, kGridTiled = 1, kGridTcnn = 2 };
 
 // gridencoder.cu:55-57 (spatial-hash primes); folded to immediates after unrolling
 __host__ __device__ constexpr uint32_t prime_of(int d) {
@@ -49,6 +56,8 @@ __host__ __device__ constexpr uint32_t prime_of(int d) {
 // exp2f(level*S) is evaluated in double and rounded once (same convention as the oracle).
 int build_meta(GridMeta &m, const int32_t *offsets, uint32_t D, uint32_t L, float S, uint32_t H, uint32_t gridtype,
                bool align) {
+    if (gridtype > kGridTcnn || (gridtype == kGridTcnn && align)) return -1;  // tiny-cuda-nn has no align_corners
+    const bool tcnn = gridtype == kGridTcnn;
     for (uint32_t l = 0; l < L; l++) {
         LevelParams &p = m.lv[l];
         float e = (float)l * S;
@@ -59,7 +68,7 @@ int build_meta(GridMeta &m, const int32_t *offsets, uint32_t D, uint32_t L, floa
         if (hm <= 0 || offsets[l] < 0) return -1;
         p.hashmap_size = (uint32_t)hm;
         p.offset = (uint32_t)offsets[l];
-        uint32_t R = align ? p.resolution : p.resolution + 1;
+        uint32_t R = (align || tcnn) ? p.resolution : p.resolution + 1;
         uint32_t stride = 1, nd = 0;
         uint64_t exact = 1;
         for (uint32_t d = 0; d < D && stride <= p.hashmap_size; d++) {
@@ -68,10 +77,18 @@ int build_meta(GridMeta &m, const int32_t *offsets, uint32_t D, uint32_t L, floa
             nd++;
         }
         uint32_t f = nd;
-        bool hash = (gridtype == 0 && stride > p.hashmap_size);
+        bool hash = (gridtype != kGridTiled && stride > p.hashmap_size);
         if (hash) f |= LV_HASH;
         if ((p.hashmap_size & (p.hashmap_size - 1)) == 0) f |= LV_POW2;
-        if (!hash && nd == D && exact <= p.hashmap_size) f |= LV_NOWRAP;
+        if (tcnn) {
+            f |= LV_RSTRIDE;
+            // largest index of a dense level: every coordinate at R (the +1 corner of the last cell) -> R + R^2 + .. + R^D
+            uint64_t top = 0, pw = 1;
+            for (uint32_t d = 0; d < nd; d++) top += (pw *= R);
+            if (!hash && top < 2ull * p.hashmap_size) f |= LV_WRAP1;
+        } else if (!hash && nd == D && exact <= p.hashmap_size) {
+            f |= LV_NOWRAP;
+        }
         p.flags = f;
     }
     return 0;
@@ -92,7 +109,7 @@ __device__ __forceinline__ bool locate(const float (&x)[D], const LevelParams &l
 #pragma unroll
     for (int d = 0; d < D; d++) ok = ok && !(x[d] < 0.0f || x[d] > 1.0f);
     if (!ok) return false;
-    const uint32_t R = align ? lv.resolution : lv.resolution + 1;
+    const uint32_t R = (align || (lv.flags & LV_RSTRIDE)) ? lv.resolution : lv.resolution + 1;
     const bool hash = lv.flags & LV_HASH;
     const uint32_t nd = lv.flags & 15u;
     uint32_t stride = 1;
@@ -137,6 +154,7 @@ __device__ __forceinline__ uint32_t corner_row(const Cell<D> &c, const LevelPara
         for (int d = 0; d < D; d++) idx += c.term[d][(corner >> d) & 1];
     }
     if (lv.flags & LV_POW2) idx &= lv.hashmap_size - 1;
+    else if (lv.flags & LV_WRAP1) idx = idx >= lv.hashmap_size ? idx - lv.hashmap_size : idx;
     else if (!(lv.flags & LV_NOWRAP)) idx %= lv.hashmap_size;
     return idx;
 }
@@ -217,13 +235,14 @@ k_grid_forward(const float *__restrict__ inputs, const T *__restrict__ table, T 
     T *out = outputs + ((size_t)level * Bs + b) * C;
     // The level class is workgroup-uniform.  The two classes that make up the usual configuration (hashed power-of-two
     // level / dense level indexed in all D dimensions, both with linear interpolation and align_corners = false) get
-    // their own straight-line copy of the body with the flags as compile-time constants; everything else takes the
-    // generic copy with run-time branches.
+    // their own straight-line copy of the body with the flags as compile-time constants, and so does the dense level of
+    // tiny-cuda-nn's lattice (MODE 3: stride res, one wrap); everything else takes the generic copy with run-time branches.
     auto body = [&](auto mode_c) {
     constexpr int MODE = decltype(mode_c)::value;
     LevelParams lv = lv_rt;
     if constexpr (MODE == 1) lv.flags = LV_HASH | LV_POW2;
     if constexpr (MODE == 2) lv.flags = LV_NOWRAP | (uint32_t)D;
+    if constexpr (MODE == 3) lv.flags = LV_RSTRIDE | LV_WRAP1 | (uint32_t)D;
     const uint32_t align = MODE ? 0u : align_rt, interp = MODE ? 0u : interp_rt;
     Cell<D> cell;
     Vec<T, C> res;
@@ -241,7 +260,7 @@ k_grid_forward(const float *__restrict__ inputs, const T *__restrict__ table, T 
             // (tag look-up), its width (4 / 8 / 16 bytes per lane) costs nothing — so each (y,z) corner pair is fetched
             // with one wide load wherever its two rows share an aligned block.
             const bool hash = lv.flags & LV_HASH;
-            const bool x_dense = !hash && (lv.flags & 15u) >= 1 && (lv.flags & LV_NOWRAP);
+            const bool x_dense = MODE == 3 || (!hash && (lv.flags & 15u) >= 1 && (lv.flags & LV_NOWRAP));
             const bool hash_pair = hash && (lv.flags & LV_POW2);   // level-uniform
             const bool x_odd = cell.term[0][0] & 1u;               // per lane
             // All loads first, every use after the loop, and no per-lane branch around a load: a consumer (or the end of
@@ -287,6 +306,8 @@ k_grid_forward(const float *__restrict__ inputs, const T *__restrict__ table, T 
             if (!(sizeof(T) * C == 4 && hash_pair)) {
             //   pair[yz]: the aligned row pair holding corner c0 (hashed levels) / rows r0, r0+1 (dense x)
             //   solo[yz]: corner c1 on its own, fetched only where it is not the sibling of c0 (hashed level, odd x)
+            //   (MODE 3, tiny-cuda-nn lattice: r0 + 1 wraps to row 0 when r0 is the level's last row — the one straddling
+            //   pair; its lanes read the pair block one row lower and take c1 from solo = row 0, which every lane reads)
             Vec<T, 4> pair[4];
             Vec<T, C> solo[4];
             uint32_t r0s[4];
@@ -295,7 +316,11 @@ k_grid_forward(const float *__restrict__ inputs, const T *__restrict__ table, T 
                 const uint32_t c0 = yz << 1, c1 = c0 | 1u;
                 const uint32_t r0 = corner_row<D>(cell, lv, c0);
                 r0s[yz] = r0;
-                if (x_dense || hash_pair) {
+                if constexpr (MODE == 3) {
+                    const bool strad = r0 == lv.hashmap_size - 1u;
+                    pair[yz] = load_vec<T, 4>(tab + (size_t)(strad ? r0 - 1u : r0) * C);
+                    solo[yz] = load_vec<T, C>(tab);
+                } else if (x_dense || hash_pair) {
                     pair[yz] = load_vec<T, 4>(tab + (size_t)(x_dense ? r0 : (r0 & ~1u)) * C);
                     // lanes whose c1 IS the sibling read row 0 instead (one broadcast line): selecting the address
                     // keeps the load unconditional — an exec-masked load would be waited for at the end of its branch
@@ -306,7 +331,17 @@ k_grid_forward(const float *__restrict__ inputs, const T *__restrict__ table, T 
                     g[c1] = load_vec<T, C>(tab + (size_t)corner_row<D>(cell, lv, c1) * C);
                 }
             }
-            if (x_dense || hash_pair) {
+            if constexpr (MODE == 3) {
+#pragma unroll
+                for (uint32_t yz = 0; yz < 4; yz++) {
+                    const uint32_t c0 = yz << 1, c1 = c0 | 1u;
+                    const bool strad = r0s[yz] == lv.hashmap_size - 1u;
+                    g[c0].v[0] = strad ? pair[yz].v[2] : pair[yz].v[0];
+                    g[c0].v[1] = strad ? pair[yz].v[3] : pair[yz].v[1];
+                    g[c1].v[0] = strad ? solo[yz].v[0] : pair[yz].v[2];
+                    g[c1].v[1] = strad ? solo[yz].v[1] : pair[yz].v[3];
+                }
+            } else if (x_dense || hash_pair) {
 #pragma unroll
                 for (uint32_t yz = 0; yz < 4; yz++) {
                     const uint32_t c0 = yz << 1, c1 = c0 | 1u;
@@ -379,6 +414,8 @@ k_grid_forward(const float *__restrict__ inputs, const T *__restrict__ table, T 
     if (plain && (lv_rt.flags & (LV_HASH | LV_POW2)) == (LV_HASH | LV_POW2)) body(std::integral_constant<int, 1>{});
     else if (plain && !(lv_rt.flags & LV_HASH) && (lv_rt.flags & LV_NOWRAP) && (lv_rt.flags & 15u) == (uint32_t)D)
         body(std::integral_constant<int, 2>{});
+    else if (plain && !(lv_rt.flags & LV_HASH) && (lv_rt.flags & LV_WRAP1) && (lv_rt.flags & 15u) == (uint32_t)D)
+        body(std::integral_constant<int, 3>{});
     else body(std::integral_constant<int, 0>{});
     }  // level
 }
@@ -537,6 +574,12 @@ struct BucketPlan {
 // Pool streams per level: values (two channel pairs: 8 bytes for fp16 tables, 16 for fp32) | 2-byte (row | code << 13):
 // 10 bytes per PAIR of corners through HBM instead of 12, and half the LDS rank / stage / row-decode work per corner.
 constexpr uint32_t kCodeSingle = 7;
+// Dense level indexed in all D dimensions that the paired scatter serves (k_grid_bwd_scatter_plain MODE 2 / 3): the
+// default lattice (no wrap needed) or tiny-cuda-nn's (stride res, one wrap: the x pair whose first row is the level's
+// last row wraps to row 0 and travels as two singles).
+__host__ __device__ inline bool dense_paired(uint32_t flags, uint32_t D) {
+    return !(flags & LV_HASH) && (flags & (LV_NOWRAP | LV_WRAP1)) && (flags & 15u) == D;
+}
 
 // Rows -> buckets.  Hashed (and generic) levels: bucket = 8192 CONSECUTIVE rows — the hash spreads every batch evenly.
 // Dense plain levels: rows are positions in space, every LiDAR ray leaves the same few cells around the sensor, and with
@@ -906,13 +949,13 @@ k_grid_bwd_scatter(const T *__restrict__ grad, const float *__restrict__ inputs,
     // k_grid_bwd_scatter_plain's levels: this kernel serves the generic classes of a window (8 singles per point)
     const bool plain = align_rt == 0 && interp_rt == 0;
     if (plain && (lv_rt.flags & (LV_HASH | LV_POW2)) == (LV_HASH | LV_POW2)) return;
-    if (plain && !(lv_rt.flags & LV_HASH) && (lv_rt.flags & LV_NOWRAP) && (lv_rt.flags & 15u) == (uint32_t)D) return;
+    if (plain && dense_paired(lv_rt.flags, (uint32_t)D)) return;
     body(std::integral_constant<int, 0>{});
 }
 // true when every corner of the level travels as a single (generic class): 8 entries per point
 __host__ __device__ inline bool level_is_generic(const LevelParams &lv, uint32_t D, bool plain) {
     if (plain && (lv.flags & (LV_HASH | LV_POW2)) == (LV_HASH | LV_POW2)) return false;
-    if (plain && !(lv.flags & LV_HASH) && (lv.flags & LV_NOWRAP) && (lv.flags & 15u) == D) return false;
+    if (plain && dense_paired(lv.flags, D)) return false;
     return true;
 }
 
@@ -974,14 +1017,21 @@ k_grid_bwd_scatter_plain(const T *__restrict__ grad, const float *__restrict__ i
     const uint32_t level = level0 + blockIdx.x, chunk = blockIdx.y;
     const LevelParams lv = meta.lv[level];
     const bool cls_hash = (lv.flags & (LV_HASH | LV_POW2)) == (LV_HASH | LV_POW2);
-    const bool cls_dense = !(lv.flags & LV_HASH) && (lv.flags & LV_NOWRAP) && (lv.flags & 15u) == 3u;
+    const bool cls_dense = dense_paired(lv.flags, 3u);
     if (!cls_hash && !cls_dense) return;  // generic class: k_grid_bwd_scatter's level
     const uint32_t fb = plan.first_bucket[level], nb = plan.first_bucket[level + 1] - fb, cap = plan.cap[level];
     auto lds_at = [](uint32_t *base, uint32_t byte_off) -> uint32_t & {
         return *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(base) + byte_off);
     };
     auto body = [&](auto mode_c) {
-    constexpr int MODE = decltype(mode_c)::value;  // 1 hashed, 2 dense
+    constexpr int MODE = decltype(mode_c)::value;  // 1 hashed, 2 dense, 3 dense on tiny-cuda-nn's lattice (stride res, wrap)
+    constexpr bool DENSE = MODE >= 2;
+    // x neighbour of a dense row: r + 1, wrapped to row 0 past the level's last row on tiny-cuda-nn's lattice (only singles
+    // reach the wrap: a pair whose first row is the last row is sent as two singles, see `single` below)
+    auto x_next = [&](uint32_t r) -> uint32_t {
+        if constexpr (MODE == 3) return r + 1u == lv.hashmap_size ? 0u : r + 1u;
+        else return r + 1u;
+    };
     LNH_MARK("A load+locate");
     if (tid < kMaxBucketsPerLevel) lcnt[tid] = 0;
     // ---- load (unconditional, clamped index), range test, cell
@@ -1039,15 +1089,23 @@ k_grid_bwd_scatter_plain(const T *__restrict__ grad, const float *__restrict__ i
         for (int p = 0; p < NP; p++) single[p] = sg;
         codesh = (sg ? kCodeSingle : t_hash) << kBucketRowsLog2;
     } else {
-        const uint32_t R = lv.resolution + 1u, RR = R * R;
+        const uint32_t R = MODE == 3 ? lv.resolution : lv.resolution + 1u, RR = R * R;
         const uint32_t base = c0 + c1 * R + c2 * RR;
         r0[0] = base;
         r0[1] = base + R;
         r0[2] = base + RR;
         r0[3] = base + R + RR;
+        if constexpr (MODE == 3) {  // idx <= res + res^2 + res^3 < 2 * rows: one compare-and-subtract is the modulo
+#pragma unroll
+            for (int p = 0; p < NP; p++) r0[p] = r0[p] >= lv.hashmap_size ? r0[p] - lv.hashmap_size : r0[p];
+        }
 #pragma unroll
         for (int p = 0; p < NP; p++)  // r0 + 1 opens the next 128-row group, i.e. another bucket (bucket_of_row)
             single[p] = (r0[p] & ((1u << kGroupRowsLog2) - 1)) == (1u << kGroupRowsLog2) - 1;
+        if constexpr (MODE == 3) {  // the straddling pair: its second row wraps to row 0
+#pragma unroll
+            for (int p = 0; p < NP; p++) single[p] |= r0[p] == lv.hashmap_size - 1u;
+        }
         codesh = 0;
     }
     LNH_MARK("C masks");
@@ -1100,8 +1158,8 @@ k_grid_bwd_scatter_plain(const T *__restrict__ grad, const float *__restrict__ i
     if (wave_singles) {  // the second corners of pairs that travel as two singles
 #pragma unroll
         for (int p = 0; p < NP; p++) {
-            const uint32_t r1 = MODE == 1 ? (r0[p] ^ xm) : r0[p] + 1u;
-            if (emit && single[p]) rank_x[p] = atomicAdd(&lcnt[bucket_of_row(r1, MODE == 2)], 1u);
+            const uint32_t r1 = MODE == 1 ? (r0[p] ^ xm) : x_next(r0[p]);
+            if (emit && single[p]) rank_x[p] = atomicAdd(&lcnt[bucket_of_row(r1, DENSE)], 1u);
         }
     }
     LNH_MARK("D values");
@@ -1147,7 +1205,7 @@ k_grid_bwd_scatter_plain(const T *__restrict__ grad, const float *__restrict__ i
                 }
             }
         }
-        if constexpr (MODE == 2) {
+        if constexpr (DENSE) {
             // cross-row steps: lanes of rows 1, 3 (then 2, 3) whose run began before their row (before lane 32) take the
             // sum the last lane of the preceding row (lane 31) holds.  pre = lanes whose whole row prefix continues.
             unsigned long long pre = cont;
@@ -1207,7 +1265,7 @@ k_grid_bwd_scatter_plain(const T *__restrict__ grad, const float *__restrict__ i
     const uint32_t total = min(total_all, (uint32_t)CAP);
     const bool all_staged = total_all <= (uint32_t)CAP;  // workgroup-uniform; false only for adversarial inputs
     auto key_of = [&](uint32_t r, uint32_t csh) {  // staged key of level-local row r, code << 13
-        return local_of_row(r, MODE == 2) | csh | (bucket_of_row(r, MODE == 2) << 18);
+        return local_of_row(r, DENSE) | csh | (bucket_of_row(r, DENSE) << 18);
     };
     constexpr int NW = CAP / NTHREADS;
     static_assert(CAP % NTHREADS == 0, "staging slots are dealt to the threads in rounds");
@@ -1227,7 +1285,7 @@ k_grid_bwd_scatter_plain(const T *__restrict__ grad, const float *__restrict__ i
                 pos[p] += rank[p];
                 const uint32_t csh = MODE == 1 ? codesh : (single[p] ? kCodeSingle << kBucketRowsLog2 : 0u);
                 if (!CHECKED || pos[p] < (uint32_t)CAP) {
-                    skey[pos[p]] = local_of_row(r0[p], MODE == 2) | (csh | (bk4[p] << 16));
+                    skey[pos[p]] = local_of_row(r0[p], DENSE) | (csh | (bk4[p] << 16));
                     sa[pos[p]] = val[2 * p];
                     sb[pos[p]] = val[2 * p + 1];
                 }
@@ -1237,8 +1295,8 @@ k_grid_bwd_scatter_plain(const T *__restrict__ grad, const float *__restrict__ i
 #pragma unroll
             for (int p = 0; p < NP; p++)
                 if (single[p]) {
-                    const uint32_t r1 = MODE == 1 ? (r0[p] ^ xm) : r0[p] + 1u;
-                    pos_x[p] = lstart[bucket_of_row(r1, MODE == 2)] + rank_x[p];
+                    const uint32_t r1 = MODE == 1 ? (r0[p] ^ xm) : x_next(r0[p]);
+                    pos_x[p] = lstart[bucket_of_row(r1, DENSE)] + rank_x[p];
                     if (!CHECKED || pos_x[p] < (uint32_t)CAP) {
                         skey[pos_x[p]] = key_of(r1, kCodeSingle << kBucketRowsLog2);
                         sa[pos_x[p]] = val[2 * p + 1];
@@ -1346,7 +1404,7 @@ k_grid_bwd_scatter_plain(const T *__restrict__ grad, const float *__restrict__ i
             *reinterpret_cast<unsigned short *>(prows + slot * 2u) = (unsigned short)k;
         } else {
             const uint32_t sp = lds_at(lsp, bo) + q;
-            const uint32_t rr = row_of_local(k & (kBucketRows - 1), k >> 18, MODE == 2), cd = (k >> kBucketRowsLog2) & 7u;
+            const uint32_t rr = row_of_local(k & (kBucketRows - 1), k >> 18, DENSE), cd = (k >> kBucketRowsLog2) & 7u;
             if (sp < plan.spill_cap) {
                 SpillEntry<T> e = {rr | (cd << 29), a, b2};
                 *reinterpret_cast<SpillEntry<T> *>(spill + sp * (uint32_t)sizeof(SpillEntry<T>)) = e;
@@ -1377,7 +1435,7 @@ k_grid_bwd_scatter_plain(const T *__restrict__ grad, const float *__restrict__ i
 #pragma unroll
             for (int p = 0; p < NP; p++)
                 if (single[p] && pos_x[p] >= (uint32_t)CAP)
-                    to_global(pos_x[p], key_of(MODE == 1 ? (r0[p] ^ xm) : r0[p] + 1u, kCodeSingle << kBucketRowsLog2),
+                    to_global(pos_x[p], key_of(MODE == 1 ? (r0[p] ^ xm) : x_next(r0[p]), kCodeSingle << kBucketRowsLog2),
                               val[2 * p + 1], make_v2<T>(0.0f, 0.0f));
         }
     }
@@ -1386,6 +1444,7 @@ k_grid_bwd_scatter_plain(const T *__restrict__ grad, const float *__restrict__ i
     body(std::integral_constant<int, LNH_ONLY_MODE>{});
 #else
     if (cls_hash) body(std::integral_constant<int, 1>{});
+    else if (lv.flags & LV_WRAP1) body(std::integral_constant<int, 3>{});
     else body(std::integral_constant<int, 2>{});
 #endif
 }
@@ -1711,8 +1770,8 @@ uint64_t plan_buckets(BucketPlan &plan, const GridMeta &m, uint32_t L, uint32_t 
     uint32_t nbt = 0;
     plan.interleaved = 0;
     for (uint32_t l = 0; l < L; l++) {
-        // dense plain levels (k_grid_bwd_scatter_plain's MODE 2): 128-row groups dealt to up to 64 buckets
-        const bool il = plain && !(m.lv[l].flags & LV_HASH) && (m.lv[l].flags & LV_NOWRAP) && (m.lv[l].flags & 15u) == D;
+        // dense plain levels (k_grid_bwd_scatter_plain's MODE 2 / 3): 128-row groups dealt to up to 64 buckets
+        const bool il = plain && dense_paired(m.lv[l].flags, D);
         if (il) plan.interleaved |= 1u << l;
         const uint32_t groups = (m.lv[l].hashmap_size + (1u << kGroupRowsLog2) - 1) >> kGroupRowsLog2;
         const uint32_t nb = il ? std::min<uint32_t>(groups, kMaxBucketsPerLevel)
@@ -1990,7 +2049,7 @@ k_grad_tv(const T *__restrict__ inputs, const T *__restrict__ table, T *__restri
 #pragma unroll
     for (int d = 0; d < D; d++) pg[d] = (uint32_t)floorf(fmaf(x[d], lv.scale, align ? 0.0f : 0.5f));
     auto row_of = [&](const uint32_t(&p)[D]) {
-        const uint32_t R = align ? lv.resolution : lv.resolution + 1;
+        const uint32_t R = (align || (lv.flags & LV_RSTRIDE)) ? lv.resolution : lv.resolution + 1;
         const uint32_t nd = lv.flags & 15u;
         uint32_t idx = 0, stride = 1;
         if (lv.flags & LV_HASH) {
@@ -2174,7 +2233,7 @@ int lnh_grid_encode_forward(const float *inputs, const void *embeddings, const i
     if (B == 0) return LNH_OK;
     GridMeta m;
     LNH_REQUIRE(build_meta(m, offsets_host, D, L, S, H, gridtype, align_corners != 0) == 0, LNH_ERR_INVALID_ARG,
-                "grid: offsets must be increasing and non-negative");
+                "grid: offsets must be increasing and non-negative, gridtype 0 / 1 / 2 (2: align_corners off)");
     hipStream_t s = (hipStream_t)stream;
     if (dtype == LNH_F32) {
         LNH_DISPATCH_D(D, (launch_forward_c<float, DD>(inputs, (const float *)embeddings, (float *)outputs,
@@ -2186,10 +2245,10 @@ int lnh_grid_encode_forward(const float *inputs, const void *embeddings, const i
     return rc;
 }
 
-int lnh_grid_encode_forward_mapped(const float *inputs_all, const void *embeddings, const int32_t *offsets_host,
-                                   void *outputs_all, uint32_t B, uint32_t T_cur, uint32_t T_tot, uint32_t slot_off,
-                                   uint32_t B_all, uint32_t C, uint32_t L, float S, uint32_t H, int dtype,
-                                   lnh_stream_t stream) {
+int lnh_grid_encode_forward_mapped_ex(const float *inputs_all, const void *embeddings, const int32_t *offsets_host,
+                                      void *outputs_all, uint32_t B, uint32_t T_cur, uint32_t T_tot, uint32_t slot_off,
+                                      uint32_t B_all, uint32_t C, uint32_t L, float S, uint32_t H, uint32_t gridtype,
+                                      int dtype, lnh_stream_t stream) {
     int rc = check_common(inputs_all, offsets_host, B, 3, C, L, dtype);
     if (rc) return rc;
     LNH_REQUIRE(embeddings && outputs_all, LNH_ERR_INVALID_ARG, "grid forward (mapped): null embeddings/outputs");
@@ -2197,8 +2256,10 @@ int lnh_grid_encode_forward_mapped(const float *inputs_all, const void *embeddin
                 LNH_ERR_INVALID_ARG, "grid forward (mapped): inconsistent row map");
     if (B == 0) return LNH_OK;
     GridMeta m;
-    LNH_REQUIRE(build_meta(m, offsets_host, 3, L, S, H, 0, false) == 0, LNH_ERR_INVALID_ARG,
-                "grid: offsets must be increasing and non-negative");
+    LNH_REQUIRE(gridtype == kGridHash || gridtype == kGridTcnn, LNH_ERR_INVALID_ARG,
+                "grid forward (mapped): gridtype must be 0 (hash) or 2 (tiny-cuda-nn lattice), got %u", gridtype);
+    LNH_REQUIRE(build_meta(m, offsets_host, 3, L, S, H, gridtype, false) == 0, LNH_ERR_INVALID_ARG,
+                "grid: offsets must be increasing and non-negative, gridtype 0 / 1 / 2 (2: align_corners off)");
     const RowMap map{T_cur, T_tot, slot_off, B_all};
     hipStream_t s = (hipStream_t)stream;
     if (dtype == LNH_F32)
@@ -2206,6 +2267,14 @@ int lnh_grid_encode_forward_mapped(const float *inputs_all, const void *embeddin
                                           0, 0, s, map);
     return launch_forward_c<half_t, 3>(inputs_all, (const half_t *)embeddings, (half_t *)outputs_all, nullptr, B, C, L, m, 0,
                                        0, s, map);
+}
+
+int lnh_grid_encode_forward_mapped(const float *inputs_all, const void *embeddings, const int32_t *offsets_host,
+                                   void *outputs_all, uint32_t B, uint32_t T_cur, uint32_t T_tot, uint32_t slot_off,
+                                   uint32_t B_all, uint32_t C, uint32_t L, float S, uint32_t H, int dtype,
+                                   lnh_stream_t stream) {
+    return lnh_grid_encode_forward_mapped_ex(inputs_all, embeddings, offsets_host, outputs_all, B, T_cur, T_tot, slot_off,
+                                             B_all, C, L, S, H, kGridHash, dtype, stream);
 }
 
 int lnh_grid_encode_backward(const void *grad, const float *inputs, const void *embeddings,
@@ -2221,7 +2290,7 @@ int lnh_grid_encode_backward(const void *grad, const float *inputs, const void *
     if (B == 0) return LNH_OK;
     GridMeta m;
     LNH_REQUIRE(build_meta(m, offsets_host, D, L, S, H, gridtype, align_corners != 0) == 0, LNH_ERR_INVALID_ARG,
-                "grid: offsets must be increasing and non-negative");
+                "grid: offsets must be increasing and non-negative, gridtype 0 / 1 / 2 (2: align_corners off)");
     hipStream_t s = (hipStream_t)stream;
     if (dtype == LNH_F32) {
         LNH_DISPATCH_D(D, (launch_backward_c<float, DD>((const float *)grad, inputs, (float *)grad_embeddings, B, C, L,
@@ -2312,7 +2381,7 @@ int lnh_grid_encode_backward_ws(const void *grad, const float *inputs, const int
     if (B == 0) return LNH_OK;
     GridMeta m;
     LNH_REQUIRE(build_meta(m, offsets_host, D, L, S, H, gridtype, align_corners != 0) == 0, LNH_ERR_INVALID_ARG,
-                "grid: offsets must be increasing and non-negative");
+                "grid: offsets must be increasing and non-negative, gridtype 0 / 1 / 2 (2: align_corners off)");
     hipStream_t s = (hipStream_t)stream;
     if (dtype == LNH_F32)
         return launch_backward_bucketed<float>((const float *)grad, inputs, (float *)grad_embeddings, B, L, m,
@@ -2336,7 +2405,7 @@ int lnh_grid_encode_backward_ws_levels(const void *grad, const float *inputs, co
     if (B == 0) return LNH_OK;
     GridMeta m;
     LNH_REQUIRE(build_meta(m, offsets_host, D, L, S, H, gridtype, align_corners != 0) == 0, LNH_ERR_INVALID_ARG,
-                "grid: offsets must be increasing and non-negative");
+                "grid: offsets must be increasing and non-negative, gridtype 0 / 1 / 2 (2: align_corners off)");
     hipStream_t s = (hipStream_t)stream;
     if (dtype == LNH_F32)
         return launch_backward_bucketed<float>((const float *)grad, inputs, (float *)grad_embeddings, B, L, m,
@@ -2361,7 +2430,7 @@ static int backward_ws_split(const void *grad, const float *inputs, const int32_
     if (B == 0) return LNH_OK;
     GridMeta m;
     LNH_REQUIRE(build_meta(m, offsets_host, D, L, S, H, gridtype, align_corners != 0) == 0, LNH_ERR_INVALID_ARG,
-                "grid: offsets must be increasing and non-negative");
+                "grid: offsets must be increasing and non-negative, gridtype 0 / 1 / 2 (2: align_corners off)");
     hipStream_t s = (hipStream_t)stream;
     if (dtype == LNH_F32)
         return launch_backward_bucketed<float>((const float *)grad, inputs, (float *)grad_embeddings, B, L, m,
@@ -2388,7 +2457,7 @@ int lnh_grid_encode_backward_ws_ex(const void *grad, const float *inputs, const 
     if (B == 0) return LNH_OK;
     GridMeta m;
     LNH_REQUIRE(build_meta(m, offsets_host, D, L, S, H, gridtype, align_corners != 0) == 0, LNH_ERR_INVALID_ARG,
-                "grid: offsets must be increasing and non-negative");
+                "grid: offsets must be increasing and non-negative, gridtype 0 / 1 / 2 (2: align_corners off)");
     hipStream_t s = (hipStream_t)stream;
     if (split == 1) {  // begin: everything but the last reduce pass, over all levels
         level_begin = 0;
@@ -2451,7 +2520,7 @@ int lnh_grad_total_variation(const void *inputs, const void *embeddings, void *g
     if (B == 0) return LNH_OK;
     GridMeta m;
     LNH_REQUIRE(build_meta(m, offsets_host, D, L, S, H, gridtype, align_corners != 0) == 0, LNH_ERR_INVALID_ARG,
-                "grid: offsets must be increasing and non-negative");
+                "grid: offsets must be increasing and non-negative, gridtype 0 / 1 / 2 (2: align_corners off)");
     hipStream_t s = (hipStream_t)stream;
     if (dtype == LNH_F32) {
         LNH_DISPATCH_D(D, (launch_tv_c<float, DD>((const float *)inputs, (const float *)embeddings, (float *)grad,
@@ -2472,7 +2541,7 @@ int lnh_grid_corner_indices(const float *inputs, const int32_t *offsets_host, ui
     if (B == 0) return LNH_OK;
     GridMeta m;
     LNH_REQUIRE(build_meta(m, offsets_host, D, L, S, H, gridtype, align_corners != 0) == 0, LNH_ERR_INVALID_ARG,
-                "grid: offsets must be increasing and non-negative");
+                "grid: offsets must be increasing and non-negative, gridtype 0 / 1 / 2 (2: align_corners off)");
     hipStream_t s = (hipStream_t)stream;
     dim3 grid(div_up(B, 256), L), block(256);
     switch (D) {

@@ -58,6 +58,7 @@ _SIGS = {
     "lnh_lidar_sample_points": [P, P, P, P, F32, U32, U32, U32, U32, P],
     "lnh_lidar_coarse_sample_points": [P, P, P, P, F32, U32, U32, U32, F32, F32, P, P],
     "lnh_grid_encode_forward_mapped": [P, P, P, P, U32, U32, U32, U32, U32, U32, U32, F32, U32, I32],
+    "lnh_grid_encode_forward_mapped_ex": [P, P, P, P, U32, U32, U32, U32, U32, U32, U32, F32, U32, U32, I32],
     "lnh_density_mlp_forward": [P, P, U32, U32, U32, U32, U32, P, P],
     "lnh_density_mlp_backward": [P, P, P, U32, U32, U32, U32, P, P, P, C.c_uint64],
     "lnh_lidar_merge_weights": [P, P, P, P, U32, U32, F32, P, P],
@@ -153,6 +154,24 @@ def lib():
                                "(set LNH_ALLOW_VARIANT=1 to time it; its results are wrong by construction)")
         _lib = L
     return _lib
+
+
+GRIDTYPE_TCNN = 2  # hash on tiny-cuda-nn's lattice (include/lidarnerf_hip.h, lnh_grid_encode_forward)
+_GRIDTYPE_MIN_VERSION = {GRIDTYPE_TCNN: 101}
+_gridtype_ok = set()
+
+
+def require_gridtype(gridtype):
+    """Refuse a grid type the loaded library predates (gridtype 2 needs lnh_version() >= 101): an older library would
+    return LNH_ERR_INVALID_ARG at best, index with the wrong lattice at worst."""
+    if gridtype in _gridtype_ok:
+        return
+    need = _GRIDTYPE_MIN_VERSION.get(gridtype, 100)
+    have = lib().lnh_version()
+    if have < need:
+        raise RuntimeError(f"{_LIB_PATH} reports lnh_version() {have}; gridtype {gridtype} (tiny-cuda-nn lattice) needs "
+                           f"{need} or later — rebuild the library (python lidar-nerf_amd/build.py)")
+    _gridtype_ok.add(gridtype)
 
 
 def ptr(t):

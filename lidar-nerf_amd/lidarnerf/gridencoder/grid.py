@@ -14,14 +14,36 @@ from torch.autograd import Function
 
 from .. import _hip
 
-_GRIDTYPE = {"hash": 0, "tiled": 1}
+# "tcnn": hash on tiny-cuda-nn's lattice (stride res and res^D rows on the dense levels, rows always wrap); see
+# include/lidarnerf_hip.h (lnh_grid_encode_forward) and level_offsets
+_GRIDTYPE = {"hash": 0, "tiled": 1, "tcnn": 2}
 _INTERP = {"linear": 0, "smoothstep": 1}
 
 
-def level_offsets(input_dim, num_levels, per_level_scale, base_resolution, log2_hashmap_size, align_corners):
-    """Rows per level: min(2^log2_hashmap_size, (res[+1])^D) rounded up to a multiple of 8 (grid.py:179-193)."""
+def tcnn_level_resolution(level, per_level_scale, base_resolution):
+    """Lattice resolution of a level exactly as the kernel's build_meta computes it (float32 scale; exp2 in double, rounded
+    once): ceil(exp2(level * S) * H - 1) + 1 with S = log2(per_level_scale) as float32."""
+    S = np.float32(np.log2(per_level_scale))
+    e = np.float32(level) * S
+    pw = np.float32(np.exp2(np.float64(e)))
+    scale = pw * np.float32(base_resolution) - np.float32(1.0)
+    return int(np.ceil(scale)) + 1
+
+
+def level_offsets(input_dim, num_levels, per_level_scale, base_resolution, log2_hashmap_size, align_corners,
+                  gridtype="hash"):
+    """Rows per level: min(2^log2_hashmap_size, (res[+1])^D) rounded up to a multiple of 8 (grid.py:179-193).
+    gridtype "tcnn": tiny-cuda-nn's rule min(2^log2_hashmap_size, res^D rounded up to 8), with the resolution of the
+    kernel's float32 arithmetic (tcnn_level_resolution)."""
     cap = 2 ** log2_hashmap_size
     offs = [0]
+    if gridtype == "tcnn":
+        if align_corners:
+            raise ValueError("gridtype 'tcnn' has no align_corners (tiny-cuda-nn's lattice)")
+        for lvl in range(num_levels):
+            res = tcnn_level_resolution(lvl, per_level_scale, base_resolution)
+            offs.append(offs[-1] + min(cap, -(-res ** input_dim // 8) * 8))
+        return np.asarray(offs, dtype=np.int32)
     for lvl in range(num_levels):
         res = int(np.ceil(base_resolution * per_level_scale ** lvl))
         side = res if align_corners else res + 1
@@ -33,6 +55,7 @@ def level_offsets(input_dim, num_levels, per_level_scale, base_resolution, log2_
 def grid_forward_raw(inputs, embeddings, offsets_host, S, H, gridtype, align_corners, interp, want_dy_dx):
     """inputs [B,D] f32 in [0,1]; returns (outputs [L,B,C], dy_dx or None) — level-major like the kernel writes it."""
     _hip.require_cuda(inputs, embeddings)
+    _hip.require_gridtype(gridtype)
     B, D = inputs.shape
     L, C = offsets_host.shape[0] - 1, embeddings.shape[1]
     out = torch.empty((L, B, C), device=inputs.device, dtype=embeddings.dtype)
@@ -70,6 +93,7 @@ def grid_backward_raw(grad_lbc, inputs, rows, offsets_host, S, H, gridtype, alig
     """grad [L,B,C] -> (grad_embeddings [rows,C] in grad's dtype, grad_inputs [B,D] or None)."""
     L, B, C = grad_lbc.shape
     D = inputs.shape[1]
+    _hip.require_gridtype(gridtype)
     ge = torch.zeros((rows, C), device=grad_lbc.device, dtype=grad_lbc.dtype)
     if dy_dx is None and D == 3 and C == 2:
         # hot configuration: bucketed scatter-reduce, no atomic adds to HBM (lnh_grid_encode_backward_ws)
@@ -143,7 +167,8 @@ class GridEncoder(nn.Module):
         self.interpolation, self.interp_id = interpolation, _INTERP[interpolation]
         self.align_corners = align_corners
         self.max_params = 2 ** log2_hashmap_size
-        offs = level_offsets(input_dim, num_levels, per_level_scale, base_resolution, log2_hashmap_size, align_corners)
+        offs = level_offsets(input_dim, num_levels, per_level_scale, base_resolution, log2_hashmap_size, align_corners,
+                             gridtype)
         self.register_buffer("offsets", torch.from_numpy(offs))
         self._offsets_host = torch.from_numpy(offs.copy())  # host copy handed to the C ABI
         self.n_params = int(offs[-1]) * level_dim
@@ -193,6 +218,7 @@ class GridEncoder(nn.Module):
             inputs = ((inputs + bound) / (2 * bound)).view(-1, self.input_dim)
             B = inputs.shape[0]
         inputs = inputs.contiguous().to(self.embeddings.dtype)
+        _hip.require_gridtype(self.gridtype_id)
         _hip.call("lnh_grad_total_variation", inputs.data_ptr(), self.embeddings.data_ptr(),
                   self.embeddings.grad.data_ptr(), self._offsets_host.data_ptr(), float(weight), B, self.input_dim,
                   self.level_dim, self.num_levels, self.log2_scale, self.base_resolution, self.gridtype_id,

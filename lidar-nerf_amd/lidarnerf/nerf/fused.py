@@ -52,9 +52,16 @@ def _bucketed_backward_ok(enc):
     ok = getattr(enc, "_lnh_bucketed_ok", None)
     if ok is None:
         ok = _hip.lib().lnh_grid_backward_workspace_size(enc._offsets_host.data_ptr(), 1024, 3, 2, enc.num_levels,
-                                                         enc.log2_scale, enc.base_resolution, 0, 0, _hip.LNH_F16) > 0
+                                                         enc.log2_scale, enc.base_resolution, enc.gridtype_id, 0,
+                                                         _hip.LNH_F16) > 0
         enc._lnh_bucketed_ok = ok
     return ok
+
+
+def _gridtype_ok(enc):
+    """gridtype 0 (hash) or 2 (tiny-cuda-nn lattice); the latter needs a library that knows it (lnh_version >= 101)."""
+    _hip.require_gridtype(enc.gridtype_id)
+    return True
 
 
 def supported(model, cal_lidar_color, num_steps, upsample_steps):
@@ -64,12 +71,12 @@ def supported(model, cal_lidar_color, num_steps, upsample_steps):
         enc = sp.grid
         ok = (cal_lidar_color and upsample_steps > 0 and model.bg_radius <= 0
               and enc.input_dim == 3 and enc.num_levels == 16
-              and enc.level_dim == 2 and enc.gridtype_id == 0 and not enc.align_corners and enc.interp_id == 0
+              and enc.level_dim == 2 and enc.gridtype_id in (0, 2) and not enc.align_corners and enc.interp_id == 0
               and tuple(sp.ws0.shape) == (64, 32) and tuple(sp.ws1.shape) == (16, 64)
               and sp.n_color_mats == 3 and 1 <= sp.n_dir <= 128 and tuple(sp.wc0.shape) == (64, sp.n_dir + 15)
               and tuple(sp.wc1.shape) == (64, 64) and tuple(sp.wc2.shape) == (2, 64)
               and model.geo_feat_dim == 15 and (num_steps + upsample_steps) % 16 == 0
-              and sp.table.is_cuda and _bucketed_backward_ok(enc))
+              and sp.table.is_cuda and _gridtype_ok(enc) and _bucketed_backward_ok(enc))
         return bool(ok)
     except AttributeError:
         return False
@@ -79,7 +86,7 @@ def _grid_fwd(x01, table16, enc, B):
     L = enc.num_levels
     out = torch.empty((L, B, 2), dtype=torch.half, device=x01.device)
     _hip.call("lnh_grid_encode_forward", x01.data_ptr(), table16.data_ptr(), enc._offsets_host.data_ptr(),
-              out.data_ptr(), B, 3, 2, L, enc.log2_scale, enc.base_resolution, None, 0, 0, 0, _hip.LNH_F16, tag=B)
+              out.data_ptr(), B, 3, 2, L, enc.log2_scale, enc.base_resolution, None, enc.gridtype_id, 0, 0, _hip.LNH_F16, tag=B)
     return out
 
 
@@ -91,15 +98,16 @@ def _grid_bwd_workspace(dev, enc, B):
     off = enc._offsets_host
     if ent is None:
         L = enc.num_levels
-        need = _hip.lib().lnh_grid_backward_workspace_size(off.data_ptr(), B, 3, 2, L, enc.log2_scale, enc.base_resolution, 0, 0,
-                                                           _hip.LNH_F16)
+        need = _hip.lib().lnh_grid_backward_workspace_size(off.data_ptr(), B, 3, 2, L, enc.log2_scale, enc.base_resolution,
+                                                           enc.gridtype_id, 0, _hip.LNH_F16)
         if len(cache) > 16:
             cache.clear()
         ent = cache[B] = [need, None]
     ws = _workspace(dev, ent[0])
     if ent[1] is None or ent[1][0] != ws.numel():
         clear = _hip.lib().lnh_grid_backward_workspace_clear_bytes(off.data_ptr(), B, 3, 2, enc.num_levels, enc.log2_scale,
-                                                                   enc.base_resolution, 0, 0, 0, _hip.LNH_F16, ws.numel())
+                                                                   enc.base_resolution, enc.gridtype_id, 0, 0, _hip.LNH_F16,
+                                                                   ws.numel())
         ent[1] = (ws.numel(), int(clear))
     return ws, ent[1][1]
 
@@ -112,7 +120,8 @@ def _grid_bwd(g_feat, x01, g_table16, enc, B, ws=None, flags=0):
     if ws is None:
         ws, _ = _grid_bwd_workspace(g_feat.device, enc, B)
     _hip.call("lnh_grid_encode_backward_ws_ex", g_feat.data_ptr(), x01.data_ptr(), off.data_ptr(), g_table16.data_ptr(),
-              B, 3, 2, L, enc.log2_scale, enc.base_resolution, 0, 0, 0, _hip.LNH_F16, ws.data_ptr(), ws.numel(), 0, L, 0,
+              B, 3, 2, L, enc.log2_scale, enc.base_resolution, enc.gridtype_id, 0, 0, _hip.LNH_F16, ws.data_ptr(), ws.numel(),
+              0, L, 0,
               int(flags), tag=B, timer="lnh_grid_encode_backward_ws")
 
 
@@ -149,7 +158,7 @@ def _grid_bwd_windows(g_feat, x01, g_table16, enc, B, ws=None, flags=0):
     if ws is None:
         ws, _ = _grid_bwd_workspace(g_feat.device, enc, B)
     args = (g_feat.data_ptr(), x01.data_ptr(), off.data_ptr(), g_table16.data_ptr(), B, 3, 2, L, enc.log2_scale,
-            enc.base_resolution, 0, 0, 0, _hip.LNH_F16, ws.data_ptr(), ws.numel())
+            enc.base_resolution, enc.gridtype_id, 0, 0, _hip.LNH_F16, ws.data_ptr(), ws.numel())
     _hip.call("lnh_grid_encode_backward_ws_ex", *args, 0, L, 1, int(flags), tag=B, timer="lnh_grid_encode_backward_ws_begin")
     for l0, l1 in (_DP_LEVEL_WINDOWS if L == 16 else ((0, L),)):
         _hip.call("lnh_grid_encode_backward_ws_ex", *args, l0, l1, 2, int(flags), timer="lnh_grid_encode_backward_ws_finish")
@@ -322,9 +331,9 @@ class FusedLidarRender(Function):
             else:
                 _hip.call("lnh_lidar_sample_points", rays_o.data_ptr(), rays_d.data_ptr(), zz.data_ptr(), aabb.data_ptr(),
                           bound, N, Tc, Ttot, off, x01.data_ptr())
-            _hip.call("lnh_grid_encode_forward_mapped", x01.data_ptr(), table16.data_ptr(),
+            _hip.call("lnh_grid_encode_forward_mapped_ex", x01.data_ptr(), table16.data_ptr(),
                       enc._offsets_host.data_ptr(), feat.data_ptr(), B, Tc, Ttot, off, B_all, 2, L, enc.log2_scale,
-                      enc.base_resolution, _hip.LNH_F16, tag=B)
+                      enc.base_resolution, enc.gridtype_id, _hip.LNH_F16, tag=B, timer="lnh_grid_encode_forward_mapped")
             _hip.call("lnh_density_mlp_forward" + sfx, feat.data_ptr(), wsig16.data_ptr(), B, Tc, Ttot, off, B_all,
                       h16.data_ptr(), sigma_pt.data_ptr())
 
@@ -570,7 +579,7 @@ class FusedLidarRagged(Function):
         _hip.call("lnh_ragged_points", xyzs.data_ptr(), bound, M, x01.data_ptr())
         feat = torch.empty((L, M, 2), dtype=torch.half, device=dev)
         _hip.call("lnh_grid_encode_forward", x01.data_ptr(), table16.data_ptr(), enc._offsets_host.data_ptr(),
-                  feat.data_ptr(), M, 3, 2, L, enc.log2_scale, enc.base_resolution, None, 0, 0, 0, _hip.LNH_F16, tag=M)
+                  feat.data_ptr(), M, 3, 2, L, enc.log2_scale, enc.base_resolution, None, enc.gridtype_id, 0, 0, _hip.LNH_F16, tag=M)
         h16 = torch.empty((M, 16), dtype=mdt, device=dev)
         sigma = torch.empty(M, dtype=torch.float32, device=dev)
         _hip.call("lnh_density_mlp_forward" + sfx, feat.data_ptr(), wsig16.data_ptr(), M, M, M, 0, 0, h16.data_ptr(),
@@ -694,7 +703,10 @@ def ragged_supported(model):
         sp = model.fused_spec()
     except AttributeError:
         return False
-    return supported(model, True, 16, 16) and getattr(sp, "dir_freq_degree", None) is not None \
+    # gridtype 0 only: the tcnn-shaped field renders without cuda_ray (as the reference's -L run does), and this chain is
+    # not verified on tiny-cuda-nn's lattice (gridtype 2) — such a model takes the modular occupancy path (the grid
+    # encoder's own HIP kernels, which serve every gridtype) instead
+    return supported(model, True, 16, 16) and sp.grid.gridtype_id == 0 and getattr(sp, "dir_freq_degree", None) is not None \
         and 3 + 6 * sp.dir_freq_degree == sp.n_dir and sp.n_dir + 15 <= 96
 
 

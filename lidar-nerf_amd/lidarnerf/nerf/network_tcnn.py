@@ -3,6 +3,10 @@
 instead of tinycudann.  Differences from `network.NeRFNetwork` that change numbers: positions and directions are mapped
 to [0,1] before the encoders, the LiDAR direction encoding is tcnn's 72-wide Frequency (no raw input, pi-scaled), and
 every module owns a flat `params` vector.  PARITY UNPINNED against real tiny-cuda-nn (see tcnn_compat.py).
+
+`tcnn_geometry` selects the hash grid's level geometry (tcnn_compat: "torch-ngp", the default, or "tcnn" — tiny-cuda-nn's
+res^D rows / stride res, whose `encoder.params` loads and saves tiny-cuda-nn-sized vectors); None reads LNH_TCNN_GEOMETRY,
+so `main_lidarnerf.py -L` opts in without a code change.
 """
 import torch
 
@@ -16,7 +20,7 @@ class NeRFNetwork(NeRFRenderer):
     def __init__(self, encoding="HashGrid", desired_resolution=2048, log2_hashmap_size=19,
                  encoding_dir="SphericalHarmonics", n_features_per_level=2, num_layers=2, hidden_dim=64,
                  geo_feat_dim=15, num_layers_color=3, hidden_dim_color=64, out_color_dim=3, out_lidar_color_dim=2,
-                 bound=1, fused_lidar=True, **kwargs):
+                 bound=1, fused_lidar=True, tcnn_geometry=None, **kwargs):
         super().__init__(bound, **kwargs)
         self.fused_lidar = fused_lidar
         self.num_layers, self.hidden_dim, self.geo_feat_dim = num_layers, hidden_dim, geo_feat_dim
@@ -29,7 +33,7 @@ class NeRFNetwork(NeRFRenderer):
         self.encoder = tcnn.Encoding(3, {"otype": "HashGrid", "n_levels": 16,
                                          "n_features_per_level": n_features_per_level,
                                          "log2_hashmap_size": log2_hashmap_size, "base_resolution": 16,
-                                         "per_level_scale": pls})
+                                         "per_level_scale": pls}, geometry=tcnn_geometry)
         mlp = {"otype": "FullyFusedMLP", "activation": "ReLU", "output_activation": "None"}
         self.sigma_net = tcnn.Network(self.encoder.n_output_dims, 1 + geo_feat_dim,
                                       dict(mlp, n_neurons=hidden_dim, n_hidden_layers=num_layers - 1))

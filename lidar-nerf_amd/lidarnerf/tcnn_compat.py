@@ -4,10 +4,19 @@ tinycudann.  Only the two entry points that file uses exist: `Encoding(n_input_d
 `Network(n_input_dims, n_output_dims, network_config)`, with tcnn's conventions: inputs in [0,1], a flat fp32 `params`
 Parameter per module (state-dict key `<name>.params`), `n_output_dims`, fp16 outputs under autocast.
 
-NOT CHECKPOINT-COMPATIBLE with real tiny-cuda-nn: `_HashGrid` keeps torch-ngp's level geometry ((res+1)^D rows and
-stride res+1 on the dense levels, row counts rounded up to 8) whereas tiny-cuda-nn uses res^D rows / stride res there, so
-the flat `params` vector of a tcnn-trained HashGrid has a different length and index function (strict load fails with a
-size mismatch).  The modules train, render and resume their OWN checkpoints; see INTEGRATION.md §A.
+HashGrid LEVEL GEOMETRY.  Two lattices, chosen per Encoding with `geometry=` (or, when that is None,
+the environment variable LNH_TCNN_GEOMETRY):
+  * "torch-ngp" (the default): torch-ngp's geometry — (res+1)^D rows and stride res+1 on the dense levels, row counts
+    rounded up to 8.  NOT CHECKPOINT-COMPATIBLE with real tiny-cuda-nn, which uses res^D rows / stride res there: the flat
+    `params` vector of a tcnn-trained HashGrid has another length and index function.  Such a checkpoint is refused by name
+    (or re-indexed at load with LNH_TCNN_CONVERT=1, convert_tcnn_hashgrid_params); the modules train, render and resume
+    their OWN checkpoints.
+  * "tcnn": tiny-cuda-nn's geometry (GridEncoder gridtype "tcnn", kernel gridtype 2) — res^D rows rounded up to 8, stride
+    res, every dense row index wrapped modulo the level's rows, so the vertices at x = res alias the next row and share its
+    parameter as they do in tiny-cuda-nn.  `params` has exactly the length tiny-cuda-nn allocates
+    (_tcnn_hashgrid_param_count); a vector of that length loads natively (no conversion), and what is saved has that
+    length and index function.  A torch-ngp-sized vector is refused by name.  The index function is RESTATED from
+    tiny-cuda-nn's published GridEncoding and pinned by this package's tests, not against a real tiny-cuda-nn build.
 
 PARITY UNPINNED: tiny-cuda-nn is an external, unversioned dependency of the reference (readme.md:74-76) whose source is
 not in the tree.  HashGrid / SphericalHarmonics reuse the in-tree encoders' arithmetic (torch-ngp's gridencoder and
@@ -31,16 +40,29 @@ def _pad16(n):
     return (n + 15) // 16 * 16
 
 
+GEOMETRIES = ("torch-ngp", "tcnn")
+
+
+def resolve_geometry(geometry=None):
+    """HashGrid level geometry: `geometry` if given, else LNH_TCNN_GEOMETRY, else "torch-ngp".  Unknown values raise."""
+    if geometry is None:
+        geometry = os.environ.get("LNH_TCNN_GEOMETRY") or "torch-ngp"
+    if geometry not in GEOMETRIES:
+        raise ValueError(f"tcnn_compat: unknown HashGrid geometry {geometry!r} (LNH_TCNN_GEOMETRY / geometry=): "
+                         f"one of {GEOMETRIES}")
+    return geometry
+
+
 class _HashGrid(GridEncoder):
     """GridEncoder whose table is exposed as tcnn's flat `params` vector."""
 
-    def __init__(self, cfg, n_input_dims):
+    def __init__(self, cfg, n_input_dims, geometry="torch-ngp"):
         super().__init__(input_dim=n_input_dims, num_levels=int(cfg.get("n_levels", 16)),
                          level_dim=int(cfg.get("n_features_per_level", 2)),
                          per_level_scale=float(cfg.get("per_level_scale", 2.0)),
                          base_resolution=int(cfg.get("base_resolution", 16)),
                          log2_hashmap_size=int(cfg.get("log2_hashmap_size", 19)), desired_resolution=None,
-                         gridtype="hash", align_corners=False,
+                         gridtype="tcnn" if geometry == "tcnn" else "hash", align_corners=False,
                          interpolation="smoothstep" if str(cfg.get("interpolation", "Linear")).lower() == "smoothstep"
                          else "linear")
         flat = self.embeddings.data.reshape(-1).clone()
@@ -140,14 +162,16 @@ def convert_tcnn_hashgrid_params(params, cfg, n_input_dims=3):
 class Encoding(nn.Module):
     """tcnn.Encoding(n_input_dims, encoding_config): otype HashGrid | Frequency | SphericalHarmonics | Identity."""
 
-    def __init__(self, n_input_dims, encoding_config, dtype=None, seed=1337):
+    def __init__(self, n_input_dims, encoding_config, dtype=None, seed=1337, geometry=None):
         super().__init__()
         self.n_input_dims = int(n_input_dims)
         self.encoding_config = dict(encoding_config)
         otype = str(encoding_config.get("otype", "")).lower()
         self.otype = otype
+        # HashGrid level geometry (module docstring); parameter-free encodings have none but still validate the choice
+        self.geometry = resolve_geometry(geometry)
         if otype in ("hashgrid", "grid"):
-            self.impl = _HashGrid(encoding_config, self.n_input_dims)
+            self.impl = _HashGrid(encoding_config, self.n_input_dims, self.geometry)
             self.n_output_dims = self.impl.output_dim
         elif otype == "frequency":
             self.degree = int(encoding_config.get("n_frequencies", encoding_config.get("degree", 12)))
@@ -183,6 +207,14 @@ class Encoding(nn.Module):
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
         if prefix + "params" in state_dict and self.otype in ("hashgrid", "grid"):
             got, mine = state_dict[prefix + "params"].numel(), self.impl.params.numel()
+            if got != mine and self.geometry == "tcnn":
+                ngp = self._torch_ngp_param_count()
+                hint = (f"{got} is what this package allocates in its default torch-ngp geometry: the checkpoint was written "
+                        "with geometry \"torch-ngp\".  Load it into an Encoding(..., geometry=\"torch-ngp\") (or "
+                        "LNH_TCNN_GEOMETRY=torch-ngp); the two geometries index dense levels differently, so there is no "
+                        "conversion." if got == ngp else "the checkpoint belongs to another encoding config.")
+                raise RuntimeError(f"tcnn_compat.Encoding: `{prefix}params` holds {got} values, this HashGrid in tiny-cuda-nn "
+                                   f"geometry (geometry=\"tcnn\") has {mine} — {hint}")
             if got != mine:
                 theirs = _tcnn_hashgrid_param_count(self.encoding_config, self.n_input_dims)
                 if got == theirs and os.environ.get("LNH_TCNN_CONVERT") == "1":
@@ -198,9 +230,10 @@ class Encoding(nn.Module):
                         "Such checkpoints do not load into this package: tiny-cuda-nn's dense levels have res^D rows with stride "
                         "res, this package keeps torch-ngp's (res+1)^D rows with stride res+1 (INTEGRATION.md §A), so the flat "
                         "vector has another length AND another index function.  Re-train with this package, resume one of its own "
-                        "checkpoints, or set LNH_TCNN_CONVERT=1 to convert the table at load (tcnn_compat."
-                        "convert_tcnn_hashgrid_params: same encoder output at load time, restated from tiny-cuda-nn's published "
-                        "index function — unpinned).")
+                        "checkpoints, load it natively into tiny-cuda-nn geometry (LNH_TCNN_GEOMETRY=tcnn, or "
+                        "Encoding(..., geometry=\"tcnn\") / NeRFNetwork(tcnn_geometry=\"tcnn\")), or set LNH_TCNN_CONVERT=1 "
+                        "to convert the table at load (tcnn_compat.convert_tcnn_hashgrid_params: same encoder output at load "
+                        "time, restated from tiny-cuda-nn's published index function — unpinned).")
                 else:
                     raise RuntimeError(
                     f"tcnn_compat.Encoding: `{prefix}params` holds {got} values, this HashGrid has {mine} (real tiny-cuda-nn "
@@ -209,6 +242,12 @@ class Encoding(nn.Module):
         elif prefix + "params" in state_dict:
             state_dict.pop(prefix + "params")  # parameter-free encodings store an empty tensor
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def _torch_ngp_param_count(self):
+        from .gridencoder.grid import level_offsets
+        g = self.impl
+        return int(level_offsets(g.input_dim, g.num_levels, g.per_level_scale, g.base_resolution, g.log2_hashmap_size,
+                                 False)[-1]) * g.level_dim
 
     def frequency(self, x):
         """[M, D] in [0,1] -> [M, D*2K] fp32: out[d*2K + 2k + p] = sin(2^k * pi * x_d + p*pi/2)."""
