@@ -42,7 +42,7 @@ enum {
 #define LNH_MAX_LEVELS 32
 
 /* 100: the initial ABI.  101 adds gridtype 2 (tiny-cuda-nn's HashGrid lattice, below) to every grid entry point that takes
- * a gridtype, and lnh_grid_encode_forward_mapped_ex. */
+ * a gridtype, and lnh_grid_encode_forward_mapped_ex.  102 adds lnh_lidar_loss_ex (every loss option of the reference CLI). */
 LNH_API int lnh_version(void);
 LNH_API const char *lnh_last_error(void);
 /* "gfx950" — the only architecture this library carries code for */
@@ -492,6 +492,47 @@ LNH_API int lnh_lidar_loss_patch(const float *depth, const float *image, const f
                                  uint32_t py, float scale, float alpha_d, float alpha_r, float alpha_i, float alpha_grad,
                                  const float *grad_scale, float *loss, float *grad_depth, float *grad_image,
                                  lnh_stream_t stream);
+/*
+ * lnh_lidar_loss_ex (lnh_version >= 102): the reference's Trainer.train_step loss (nerf/utils.py:697-884) for ANY option
+ * set of its CLI (main_lidarnerf.py:46-60, 92-103, 330-342), with the contract of lnh_lidar_loss_patch: writes *loss and
+ * d loss/d depth [N], d loss/d image [N,2], the gradients multiplied by *grad_scale when grad_scale != NULL.
+ * Criterion codes (LNH_LOSS_*): L1, MSE, HUBER (torch.nn.HuberLoss, delta = huber_delta; the CLI's is 0.2 * scale) and BCE
+ * (BCEWithLogitsLoss on the prediction as given: (1 - y) x - log sigmoid(x)) in every slot, COS in the grad slot only.
+ * Semantics, term for term the reference's:
+ *   - per ray: alpha_d C_depth(d gr, gd gr) + alpha_r C_raydrop(r, gr) + alpha_i C_intensity(i gr, gi gr), mean over N;
+ *     predictions and targets masked by the ground-truth ray-drop gr before every criterion.
+ *   - px > 1 (patch epochs; rays are N / (px py) patches of px x py pixels, row-major): depths in metres (value / scale).
+ *     Without LNH_LOSS_SOBEL the prediction gradient is |neighbour difference| (x: along py, [px, py-1]; y: along px,
+ *     [px-1, py]); with it, the SIGNED 3x3 Sobel responses with zero padding inside each patch ([px, py] each).
+ *     dx = |grad x|, dy = |grad y|.  GRAD_NORM_SMOOTH: + alpha_grad_norm (mean e^-dx + mean e^-dy); SPATIAL:
+ *     + alpha_spatial (mean dx^2 + mean dy^2); TV: + alpha_tv (mean dx + mean dy) — each mean over its own tensor.
+ *   - LNH_LOSS_GRAD: + alpha_grad * mean C_grad(grad x * m, gt grad x * m), only the x term; m = gr * (|gt grad x| < 0.01),
+ *     cropped to [px, py-1] without Sobel (gr of the left pixel), full size with it.  COS: 1 - CosineSimilarity per patch
+ *     over the flattened masked vectors, mean over the patches, with torch's eps handling (torch 2.x):
+ *     cos = u.w / (max(|u|, 1e-8) max(|w|, 1e-8)), d cos/du = w / (max(|u|,eps) max(|w|,eps)) - cos u / (max(|u|,eps) |u|)
+ *     (the clamp is invisible to autograd; the second term is 0 at |u| = 0): an all-zero patch gives cos 0, gradient 0.
+ *   - d|x|/dx at 0 is 0 (torch's sign).
+ * Deterministic (fixed-order sums, no atomics) and stateless.  workspace: lnh_lidar_loss_ex_workspace_bytes(N) bytes of
+ * device scratch, 4-byte aligned, contents irrelevant (per-workgroup partial sums; a second launch adds them in order).
+ * Errors (before any launch): LNH_ERR_INVALID_ARG for a null pointer, an unknown criterion code or COS outside the grad
+ * slot, N % (px py) != 0, px > 1 with py < 2, scale <= 0 on patch epochs, a workspace smaller than the query.
+ */
+enum { LNH_LOSS_L1 = 0, LNH_LOSS_MSE = 1, LNH_LOSS_HUBER = 2, LNH_LOSS_BCE = 3, LNH_LOSS_COS = 4 };
+enum {
+    LNH_LOSS_SOBEL = 1, LNH_LOSS_GRAD = 2, LNH_LOSS_GRAD_NORM_SMOOTH = 4, LNH_LOSS_SPATIAL = 8, LNH_LOSS_TV = 16
+};
+typedef struct lnh_lidar_loss_options {
+    int32_t depth_loss, raydrop_loss, intensity_loss, grad_loss; /* LNH_LOSS_L1 .. LNH_LOSS_COS */
+    uint32_t flags;                                              /* LNH_LOSS_SOBEL | LNH_LOSS_GRAD | ... */
+    uint32_t px, py;                                             /* patch shape; px <= 1: per-ray terms only */
+    float scale, huber_delta;
+    float alpha_d, alpha_r, alpha_i, alpha_grad, alpha_grad_norm, alpha_spatial, alpha_tv;
+} lnh_lidar_loss_options;
+LNH_API uint64_t lnh_lidar_loss_ex_workspace_bytes(uint32_t N);
+LNH_API int lnh_lidar_loss_ex(const float *depth, const float *image, const float *gt, uint32_t N,
+                              const lnh_lidar_loss_options *options, const float *grad_scale, void *workspace,
+                              uint64_t workspace_bytes, float *loss, float *grad_depth, float *grad_image,
+                              lnh_stream_t stream);
 /*
  * The LiDAR colour head on the marcher's RAGGED samples (BASELINE config 4; network.py:199-237 evaluated on the samples of
  * renderer.run_cuda, which the reference dropped while keeping raymarching.cu:331-772), with the dense chain's two moves:

@@ -24,7 +24,7 @@ int lnh_cu_count() {
 }
 
 extern "C" {
-int lnh_version(void) { return 101; }
+int lnh_version(void) { return 102; }
 const char *lnh_last_error(void) { return g_err; }
 const char *lnh_arch(void) { return "gfx950"; }
 const char *lnh_build_variant(void) { return LNH_VARIANT_TAG; }

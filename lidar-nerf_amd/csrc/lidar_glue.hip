@@ -289,6 +289,274 @@ k_lidar_loss_patch(const float *__restrict__ depth, const float *__restrict__ im
     loss_finish(l, 1.0f, loss);
 }
 
+// ------------------------------------------------------------------------------------------------ loss, every option
+// lnh_lidar_loss_ex: the reference's train_step loss for any option set of its CLI (include/lidarnerf_hip.h states the
+// semantics).  Thread n = ray n, 256 rays per workgroup.  A thread writes the gradient of its ray and adds up the loss
+// terms its ray OWNS: its per-ray term, the x / y smoothness and gradient elements anchored at its pixel, and (first ray
+// of a patch) the patch's 1 - cos.  What a ray's gradient needs from its neighbours — neighbour differences, the 3x3 Sobel
+// responses of the <= 9 elements whose stencil covers it, and with COS its patch's dot product and norms — is recomputed
+// from the inputs (L1-resident at these sizes) instead of being staged in scratch.  The workgroups leave their partial
+// sums in the caller's workspace and a second launch of one workgroup adds them in workgroup order: the same bits on
+// every launch, no atomics, nothing that outlives the call.
+//
+// torch's CosineSimilarity (torch 2.x, eps 1e-8, checked numerically on the CPU build): the norms are clamped to eps in
+// place under no_grad, so the value is u.w / (max(|u|, eps) max(|w|, eps)) while autograd differentiates the UNCLAMPED
+// norm:  d cos / du = w / (nu nw) - cos u / (nu |u|)  (nu, nw: the clamped norms; the second term is 0 at |u| = 0, the
+// norm's backward masks it).  A patch whose masked vectors are both zero (a dropped patch) gives cos = 0 (loss 1 per
+// patch) and gradient 0; u = 0 with w != 0 gives the gradient -w / (eps |w|).
+constexpr uint32_t kLossExThreads = 256;
+struct LossEx {
+    int32_t crit[4];  // depth, raydrop, intensity, grad (LNH_LOSS_*)
+    uint32_t flags, px, py, S;
+    float scale, delta, a_d, a_r, a_i, a_g, a_gn, a_sp, a_tv;
+    float inv_n, inv_nx, inv_ny, inv_ng;  // 1 / element count of: the rays, dx, dy, the gradient term (elements / patches)
+};
+
+__device__ __forceinline__ float sgnf(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f); }  // torch.sign
+
+// criterion value (reduction 'none') and its derivative with respect to the prediction x
+__device__ __forceinline__ float criterion(int32_t c, float x, float y, float delta, float &g) {
+    const float d = x - y;
+    if (c == LNH_LOSS_L1) {
+        g = sgnf(d);
+        return fabsf(d);
+    }
+    if (c == LNH_LOSS_MSE) {
+        g = 2.0f * d;
+        return d * d;
+    }
+    if (c == LNH_LOSS_HUBER) {  // torch: |d| < delta ? d^2 / 2 : delta (|d| - delta / 2); backward clamps d to [-delta, delta]
+        const float a = fabsf(d);
+        g = d < -delta ? -delta : (d > delta ? delta : d);
+        return a < delta ? 0.5f * d * d : delta * (a - 0.5f * delta);
+    }
+    // BCE with logits (torch: (1 - y) x - log_sigmoid(x), log_sigmoid(x) = min(x, 0) - log1p(e^-|x|); d/dx = sigmoid(x) - y)
+    g = 1.0f / (1.0f + expf(-x)) - y;
+    return (1.0f - y) * x - (fminf(x, 0.0f) - log1pf(expf(-fabsf(x))));
+}
+
+// one patch: pixel (i, j) of the patch starting at ray b; outside the patch the zero padding of the reference's conv2d
+struct PatchIn {
+    const float *depth, *gt;
+    uint32_t b;
+    int px, py;
+    float scale;
+    __device__ __forceinline__ bool in(int i, int j) const { return i >= 0 && j >= 0 && i < px && j < py; }
+    __device__ __forceinline__ float pred(int i, int j) const {  // depth * gt raydrop / scale
+        if (!in(i, j)) return 0.0f;
+        const uint32_t n = b + (uint32_t)(i * py + j);
+        return depth[n] * gt[n * 3] / scale;
+    }
+    __device__ __forceinline__ float truth(int i, int j) const {  // gt depth * gt raydrop / scale
+        if (!in(i, j)) return 0.0f;
+        const uint32_t n = b + (uint32_t)(i * py + j);
+        return gt[n * 3 + 2] * gt[n * 3] / scale;
+    }
+    __device__ __forceinline__ float drop(int i, int j) const { return gt[(b + (uint32_t)(i * py + j)) * 3]; }
+    // Sobel responses (conv2d cross-correlation, padding 1): x = [[-1,0,1],[-2,0,2],[-1,0,1]], y = its transpose.
+    // Summed as three neighbour differences: depths of tens of metres against gradients below the 0.01 m mask, and a
+    // difference of two neighbours is exact (Sterbenz) where a running sum of the taps rounds at ulp(100 m)
+    template <bool PRED>
+    __device__ __forceinline__ float v(int i, int j) const { return PRED ? pred(i, j) : truth(i, j); }
+    template <bool PRED>
+    __device__ __forceinline__ float sobel_x(int i, int j) const {
+        const float a = v<PRED>(i - 1, j + 1) - v<PRED>(i - 1, j - 1), b = v<PRED>(i, j + 1) - v<PRED>(i, j - 1),
+                    c = v<PRED>(i + 1, j + 1) - v<PRED>(i + 1, j - 1);
+        return (a + c) + 2.0f * b;
+    }
+    template <bool PRED>
+    __device__ __forceinline__ float sobel_y(int i, int j) const {
+        const float a = v<PRED>(i + 1, j - 1) - v<PRED>(i - 1, j - 1), b = v<PRED>(i + 1, j) - v<PRED>(i - 1, j),
+                    c = v<PRED>(i + 1, j + 1) - v<PRED>(i - 1, j + 1);
+        return (a + c) + 2.0f * b;
+    }
+};
+
+// x element (i, j): the raw response s (neighbour difference or Sobel x), the prediction gradient pg (|s| or s), the
+// ground-truth gradient gg and the mask m
+struct XElem {
+    float s, pg, gg, m;
+};
+template <bool SOBEL>
+__device__ __forceinline__ XElem x_elem(const PatchIn &p, int i, int j) {
+    XElem e;
+    if (SOBEL) {
+        e.s = p.sobel_x<true>(i, j);
+        e.pg = e.s;
+        e.gg = p.sobel_x<false>(i, j);
+    } else {
+        e.s = p.pred(i, j) - p.pred(i, j + 1);
+        e.pg = fabsf(e.s);
+        e.gg = p.truth(i, j) - p.truth(i, j + 1);
+    }
+    e.m = fabsf(e.gg) < 0.01f ? p.drop(i, j) : 0.0f;
+    return e;
+}
+
+// smoothness terms of one dx / dy element: value, and d/d(that element) into `h`
+__device__ __forceinline__ float smooth(const LossEx &o, float d, float inv, float &h) {
+    float val = 0.0f;
+    h = 0.0f;
+    if (o.flags & LNH_LOSS_GRAD_NORM_SMOOTH) {
+        const float e = expf(-d);
+        val += o.a_gn * e * inv;
+        h -= o.a_gn * e * inv;
+    }
+    if (o.flags & LNH_LOSS_SPATIAL) {
+        val += o.a_sp * (d * d) * inv;
+        h += o.a_sp * 2.0f * d * inv;
+    }
+    if (o.flags & LNH_LOSS_TV) {
+        val += o.a_tv * d * inv;
+        h += o.a_tv * inv;
+    }
+    return val;
+}
+
+struct CosPatch {
+    float nu, nw, u_norm, cos;  // clamped norms, the unclamped |u|, the cosine
+};
+
+// x element (i, j): its loss value (smoothness + elementwise gradient term; the cos term is per patch) and d loss / d s
+template <bool SOBEL>
+__device__ __forceinline__ float x_term(const LossEx &o, const PatchIn &p, const CosPatch &cp, int i, int j, float &hs) {
+    const XElem e = x_elem<SOBEL>(p, i, j);
+    float hd;
+    float val = smooth(o, fabsf(e.pg), o.inv_nx, hd);
+    float hpg = hd * sgnf(e.pg);  // d dx / d pg
+    if (o.flags & LNH_LOSS_GRAD) {
+        const float u = e.pg * e.m, w = e.gg * e.m;
+        if (o.crit[3] == LNH_LOSS_COS) {
+            float dc = w / (cp.nu * cp.nw);
+            if (cp.u_norm > 0.0f) dc -= cp.cos * u / (cp.nu * cp.u_norm);
+            hpg += -o.a_g * o.inv_ng * dc * e.m;
+        } else {
+            float g;
+            val += o.a_g * criterion(o.crit[3], u, w, o.delta, g) * o.inv_ng;
+            hpg += o.a_g * g * e.m * o.inv_ng;
+        }
+    }
+    hs = SOBEL ? hpg : hpg * sgnf(e.s);
+    return val;
+}
+
+// y element (i, j): smoothness only (the reference computes the y gradient term but never adds it)
+template <bool SOBEL>
+__device__ __forceinline__ float y_term(const LossEx &o, const PatchIn &p, int i, int j, float &hs) {
+    const float s = SOBEL ? p.sobel_y<true>(i, j) : p.pred(i, j) - p.pred(i + 1, j);
+    float hd;
+    const float val = smooth(o, fabsf(s), o.inv_ny, hd);
+    hs = hd * sgnf(s);
+    return val;
+}
+
+// the patch terms owned by pixel (k, l), and d (all patch terms) / d pred(k, l)
+template <bool SOBEL>
+__device__ __forceinline__ float patch_terms(const LossEx &o, const PatchIn &p, int k, int l, float &g) {
+    CosPatch cp{1.0f, 1.0f, 0.0f, 0.0f};
+    float val = 0.0f;
+    if ((o.flags & LNH_LOSS_GRAD) && o.crit[3] == LNH_LOSS_COS) {
+        float uw = 0.0f, uu = 0.0f, ww = 0.0f;  // fixed order: row-major over the x elements of the patch
+        const int jx = SOBEL ? p.py : p.py - 1;
+        for (int i = 0; i < p.px; i++)
+            for (int j = 0; j < jx; j++) {
+                const XElem e = x_elem<SOBEL>(p, i, j);
+                const float u = e.pg * e.m, w = e.gg * e.m;
+                uw += u * w;
+                uu += u * u;
+                ww += w * w;
+            }
+        cp.u_norm = sqrtf(uu);
+        cp.nu = fmaxf(cp.u_norm, 1e-8f);
+        cp.nw = fmaxf(sqrtf(ww), 1e-8f);
+        cp.cos = uw / (cp.nu * cp.nw);
+        if (k == 0 && l == 0) val += o.a_g * (1.0f - cp.cos) * o.inv_ng;
+    }
+    float h;
+    g = 0.0f;
+    if (SOBEL) {
+        // d s(i, j) / d pred(k, l) = K[k - i + 1][l - j + 1]: x weights (l - j) (2 on the centre row), y weights (k - i)
+        // (2 on the centre column); the zero taps are skipped
+        val += x_term<true>(o, p, cp, k, l, h);
+        val += y_term<true>(o, p, k, l, h);
+        for (int a = -1; a <= 1; a++)
+            for (int c = -1; c <= 1; c++) {
+                const int i = k + a, j = l + c;
+                if (!p.in(i, j)) continue;
+                if (c != 0) {
+                    (void)x_term<true>(o, p, cp, i, j, h);
+                    g += h * (float)(-c) * (a == 0 ? 2.0f : 1.0f);
+                }
+                if (a != 0) {
+                    (void)y_term<true>(o, p, i, j, h);
+                    g += h * (float)(-a) * (c == 0 ? 2.0f : 1.0f);
+                }
+            }
+    } else {
+        if (l + 1 < p.py) {
+            val += x_term<false>(o, p, cp, k, l, h);
+            g += h;
+        }
+        if (l > 0) {
+            (void)x_term<false>(o, p, cp, k, l - 1, h);
+            g -= h;
+        }
+        if (k + 1 < p.px) {
+            val += y_term<false>(o, p, k, l, h);
+            g += h;
+        }
+        if (k > 0) {
+            (void)y_term<false>(o, p, k - 1, l, h);
+            g -= h;
+        }
+    }
+    return val;
+}
+
+__global__ void __launch_bounds__(kLossExThreads)
+k_lidar_loss_ex(const float *__restrict__ depth, const float *__restrict__ image, const float *__restrict__ gt, uint32_t N,
+                LossEx o, const float *__restrict__ grad_scale, float *__restrict__ partials, float *__restrict__ g_depth,
+                float *__restrict__ g_image) {
+    const uint32_t n = blockIdx.x * kLossExThreads + threadIdx.x;
+    float l = 0.0f;
+    if (n < N) {
+        const float gsc = grad_scale ? *grad_scale : 1.0f;
+        const float gr = gt[n * 3], gi = gt[n * 3 + 1] * gr, gd = gt[n * 3 + 2] * gr;
+        const float pr = image[n * 2], pi = image[n * 2 + 1] * gr, pd = depth[n] * gr;
+        float cd, cr, ci;
+        const float ld = criterion(o.crit[0], pd, gd, o.delta, cd);
+        const float lr = criterion(o.crit[1], pr, gr, o.delta, cr);
+        const float li = criterion(o.crit[2], pi, gi, o.delta, ci);
+        l = (o.a_d * ld + o.a_r * lr + o.a_i * li) * o.inv_n;
+        float gdep = o.a_d * cd * gr * o.inv_n;
+        g_image[n * 2] = o.a_r * cr * o.inv_n * gsc;
+        g_image[n * 2 + 1] = o.a_i * ci * gr * o.inv_n * gsc;
+        if (o.px > 1) {
+            const uint32_t q = n % o.S;
+            const PatchIn p{depth, gt, n - q, (int)o.px, (int)o.py, o.scale};
+            float g;
+            l += (o.flags & LNH_LOSS_SOBEL) ? patch_terms<true>(o, p, (int)(q / o.py), (int)(q % o.py), g)
+                                            : patch_terms<false>(o, p, (int)(q / o.py), (int)(q % o.py), g);
+            gdep += g * gr / o.scale;  // d pred(k, l) / d depth = gr / scale
+        }
+        g_depth[n] = gdep * gsc;
+    }
+    __shared__ float part[kLossExThreads / 64];
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) l += __shfl_xor(l, s, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = l;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
+}
+
+// the per-workgroup partials in workgroup order: thread t adds t, t + 1024, ..., then loss_finish's fixed tree
+__global__ void __launch_bounds__(kLossThreads)
+k_lidar_loss_ex_sum(const float *__restrict__ partials, uint32_t n, float *__restrict__ loss) {
+    float l = 0.0f;
+    for (uint32_t i = threadIdx.x; i < n; i += kLossThreads) l += partials[i];
+    loss_finish(l, 1.0f, loss);
+}
+
 }  // namespace
 
 template <typename E>
@@ -442,6 +710,66 @@ int lnh_lidar_loss_patch(const float *depth, const float *image, const float *gt
     LNH_LAUNCH(k_lidar_loss_patch, dim3(1), dim3(kLossThreads), 0, (hipStream_t)stream, depth, image, gt, N, py,
                1.0f / scale, alpha_d, alpha_r, alpha_i, alpha_grad, grad_scale, loss, grad_depth, grad_image);
     return lnh_check_launch("lnh_lidar_loss_patch");
+}
+
+
+uint64_t lnh_lidar_loss_ex_workspace_bytes(uint32_t N) {
+    return (uint64_t)(div_up(N, kLossExThreads) + 3) / 4 * 16;  // one float per workgroup, rounded up to 16 bytes
+}
+
+int lnh_lidar_loss_ex(const float *depth, const float *image, const float *gt, uint32_t N,
+                      const lnh_lidar_loss_options *options, const float *grad_scale, void *workspace,
+                      uint64_t workspace_bytes, float *loss, float *grad_depth, float *grad_image, lnh_stream_t stream) {
+    LNH_REQUIRE(depth && image && gt && options && workspace && loss && grad_depth && grad_image, LNH_ERR_INVALID_ARG,
+                "lidar_loss_ex: null pointer");
+    const lnh_lidar_loss_options &a = *options;
+    const int32_t crit[4] = {a.depth_loss, a.raydrop_loss, a.intensity_loss, a.grad_loss};
+    const char *slot[4] = {"depth", "raydrop", "intensity", "grad"};
+    for (int i = 0; i < 4; i++) {
+        LNH_REQUIRE(crit[i] >= LNH_LOSS_L1 && crit[i] <= (i == 3 ? LNH_LOSS_COS : LNH_LOSS_BCE), LNH_ERR_INVALID_ARG,
+                    "lidar_loss_ex: unknown %s criterion %d (L1 0, MSE 1, HUBER 2, BCE 3%s)", slot[i], (int)crit[i],
+                    i == 3 ? ", COS 4" : "; COS only in the grad slot");
+    }
+    LNH_REQUIRE(a.px >= 1 && a.py >= 1 && N % ((uint64_t)a.px * a.py) == 0, LNH_ERR_INVALID_ARG,
+                "lidar_loss_ex: N (%u) must be a multiple of px * py (%u x %u)", N, a.px, a.py);
+    LNH_REQUIRE(a.px <= 1 || a.py >= 2, LNH_ERR_INVALID_ARG, "lidar_loss_ex: px > 1 needs py >= 2 (px %u, py %u)", a.px,
+                a.py);
+    LNH_REQUIRE(a.px <= 1 || a.scale > 0.0f, LNH_ERR_INVALID_ARG, "lidar_loss_ex: patch epochs need scale > 0");
+    LNH_REQUIRE((a.flags & ~31u) == 0, LNH_ERR_INVALID_ARG, "lidar_loss_ex: unknown flag bits 0x%x", a.flags & ~31u);
+    LNH_REQUIRE(N <= (1u << 26), LNH_ERR_UNSUPPORTED, "lidar_loss_ex: at most 2^26 rays per call");
+    LNH_REQUIRE(workspace_bytes >= lnh_lidar_loss_ex_workspace_bytes(N) && ((uintptr_t)workspace & 3) == 0,
+                LNH_ERR_INVALID_ARG, "lidar_loss_ex: workspace of %llu bytes, need %llu (4-byte aligned)",
+                (unsigned long long)workspace_bytes, (unsigned long long)lnh_lidar_loss_ex_workspace_bytes(N));
+    if (N == 0) return lnh_zero_async(loss, sizeof(float), (hipStream_t)stream, "lidar_loss_ex (no rays)");
+    LossEx o{};
+    for (int i = 0; i < 4; i++) o.crit[i] = crit[i];
+    o.flags = a.flags;
+    o.px = a.px;
+    o.py = a.py;
+    o.S = a.px * a.py;
+    o.scale = a.scale;
+    o.delta = a.huber_delta;
+    o.a_d = a.alpha_d;
+    o.a_r = a.alpha_r;
+    o.a_i = a.alpha_i;
+    o.a_g = a.alpha_grad;
+    o.a_gn = a.alpha_grad_norm;
+    o.a_sp = a.alpha_spatial;
+    o.a_tv = a.alpha_tv;
+    o.inv_n = 1.0f / (float)N;
+    if (a.px > 1) {
+        const float P = (float)(N / o.S), sob = (a.flags & LNH_LOSS_SOBEL) ? 1.0f : 0.0f;
+        const float nx = P * (float)a.px * ((float)a.py - 1.0f + sob), ny = P * ((float)a.px - 1.0f + sob) * (float)a.py;
+        o.inv_nx = 1.0f / nx;
+        o.inv_ny = 1.0f / ny;
+        o.inv_ng = a.grad_loss == LNH_LOSS_COS ? 1.0f / P : o.inv_nx;
+    }
+    const uint32_t blocks = div_up(N, kLossExThreads);
+    float *partials = (float *)workspace;
+    LNH_LAUNCH(k_lidar_loss_ex, dim3(blocks), dim3(kLossExThreads), 0, (hipStream_t)stream, depth, image, gt, N, o,
+               grad_scale, partials, grad_depth, grad_image);
+    LNH_LAUNCH(k_lidar_loss_ex_sum, dim3(1), dim3(kLossThreads), 0, (hipStream_t)stream, partials, blocks, loss);
+    return lnh_check_launch("lnh_lidar_loss_ex");
 }
 
 }  // extern "C"

@@ -95,6 +95,7 @@ _SIGS = {
     "lnh_ragged_color_output": [P, U32, P],
     "lnh_ragged_color_output_backward": [P, P, U32, P],
     "lnh_ragged_grad_rows": [P, F32, P, P, U32, U32, P],
+    "lnh_lidar_loss_ex": [P, P, P, U32, P, P, P, C.c_uint64, P, P, P],
 }
 for _n in ("lnh_mlp_forward", "lnh_mlp_backward", "lnh_mlp_backward_data", "lnh_mlp_wgrad", "lnh_density_mlp_forward", "lnh_density_mlp_backward",
            "lnh_lidar_dir_term", "lnh_lidar_pack_weights", "lnh_lidar_step_prologue", "lnh_lidar_color_forward", "lnh_lidar_color_backward",
@@ -105,7 +106,8 @@ for _n in ("lnh_mlp_forward", "lnh_mlp_backward", "lnh_mlp_backward_data", "lnh_
 EXPORTS = sorted(list(_SIGS) + ["lnh_version", "lnh_last_error", "lnh_arch", "lnh_build_variant",
                                  "lnh_grid_backward_workspace_size", "lnh_grid_backward_workspace_size_min",
                                  "lnh_grid_backward_plan_info", "lnh_grid_backward_workspace_clear_bytes",
-                                 "lnh_grid_backward_set_slice_entries", "lnh_wgrad_workspace_bytes"])
+                                 "lnh_grid_backward_set_slice_entries", "lnh_wgrad_workspace_bytes",
+                                 "lnh_lidar_loss_ex_workspace_bytes"])
 
 LNH_F32, LNH_F16 = 0, 1
 LNH_BWD_WS_CLEARED, LNH_BWD_TABLE_ZERO = 1, 2
@@ -142,6 +144,8 @@ def lib():
         L.lnh_grid_backward_set_slice_entries.restype = None
         L.lnh_wgrad_workspace_bytes.argtypes = []
         L.lnh_wgrad_workspace_bytes.restype = C.c_uint64
+        L.lnh_lidar_loss_ex_workspace_bytes.argtypes = [U32]
+        L.lnh_lidar_loss_ex_workspace_bytes.restype = C.c_uint64
         L.lnh_last_error.restype = C.c_char_p
         L.lnh_arch.restype = C.c_char_p
         L.lnh_build_variant.restype = C.c_char_p
@@ -172,6 +176,44 @@ def require_gridtype(gridtype):
         raise RuntimeError(f"{_LIB_PATH} reports lnh_version() {have}; gridtype {gridtype} (tiny-cuda-nn lattice) needs "
                            f"{need} or later — rebuild the library (python lidar-nerf_amd/build.py)")
     _gridtype_ok.add(gridtype)
+
+
+_version_ok = set()
+
+
+def require_version(need, what):
+    """Refuse a feature the loaded library predates (an older library lacks the entry point, or would misread it)."""
+    if need in _version_ok:
+        return
+    have = lib().lnh_version()
+    if have < need:
+        raise RuntimeError(f"{_LIB_PATH} reports lnh_version() {have}; {what} needs {need} or later — rebuild the library "
+                           "(python lidar-nerf_amd/build.py)")
+    _version_ok.add(need)
+
+
+# lnh_lidar_loss_options (include/lidarnerf_hip.h): criterion codes, flags, the struct
+LOSS_CODES = {"l1": 0, "mse": 1, "huber": 2, "bce": 3, "cos": 4}
+LOSS_SOBEL, LOSS_GRAD, LOSS_GRAD_NORM_SMOOTH, LOSS_SPATIAL, LOSS_TV = 1, 2, 4, 8, 16
+
+
+class LidarLossOptionsC(C.Structure):
+    _fields_ = [("depth_loss", C.c_int32), ("raydrop_loss", C.c_int32), ("intensity_loss", C.c_int32),
+                ("grad_loss", C.c_int32), ("flags", C.c_uint32), ("px", C.c_uint32), ("py", C.c_uint32),
+                ("scale", C.c_float), ("huber_delta", C.c_float), ("alpha_d", C.c_float), ("alpha_r", C.c_float),
+                ("alpha_i", C.c_float), ("alpha_grad", C.c_float), ("alpha_grad_norm", C.c_float),
+                ("alpha_spatial", C.c_float), ("alpha_tv", C.c_float)]
+
+
+def loss_options(o, px, py, scale, huber_delta, alpha_d, alpha_r, alpha_i, alpha_grad):
+    """The C struct of a nerf.train_step.LidarLossOptions for one call."""
+    flags = ((LOSS_SOBEL if o.sobel_grad else 0) | (LOSS_GRAD if o.grad_loss else 0) |
+             (LOSS_GRAD_NORM_SMOOTH if o.grad_norm_smooth else 0) | (LOSS_SPATIAL if o.spatial_smooth else 0) |
+             (LOSS_TV if o.tv_loss else 0))
+    return LidarLossOptionsC(LOSS_CODES[o.depth_loss], LOSS_CODES[o.raydrop_loss], LOSS_CODES[o.intensity_loss],
+                             LOSS_CODES[o.depth_grad_loss], flags, int(px), int(py), float(scale), float(huber_delta),
+                             float(alpha_d), float(alpha_r), float(alpha_i), float(alpha_grad), o.alpha_grad_norm,
+                             o.alpha_spatial, o.alpha_tv)
 
 
 def ptr(t):
