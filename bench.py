@@ -10,11 +10,14 @@ hash grid L=16 F=2 (2^19 rows/level, finest 32768) + 64-wide fused MLPs, fp16 ta
 accumulation (the reference's documented `--fp16` mode), Adam + GradScaler.  One step = one pass of the hot path over
 one batch of rays: render forward, LiDAR loss, backward, (DP: gradient all-reduce), optimizer step.
 
-Prints ONE JSON line on rank 0 (see the contract in the task description): metric/value/unit, roofline of the
-dominant kernel (algorithmic bytes / HIP-event duration measured inside the timed region) with the forward encode and
-the MFMA utilisation of the MLP kernels beside it, and a CPU baseline (BASELINE config 1 — the reference's CPU-runnable
-path: pure-torch frequency encoder + nn.Linear stacks — restated in oracle/render_ref.py, timed on the host cores, N=1
-only).  `--gpus N` without torchrun's environment re-launches itself under torch.distributed.run with N ranks.
+Prints ONE JSON line on rank 0: metric/value/unit, ms_per_step and the configuration.  A plain run does only what that
+headline needs: set up, warm up, time the K steps (and the two repeat regions `ms_per_step` takes its median over), write
+--dump-outputs, print.  `--full` adds everything else the benchmark measures: the roofline of the dominant kernel
+(algorithmic bytes / HIP-event duration) with the forward encode, the encode + composite path and the MFMA utilisation of
+the MLP kernels beside it (also at two fixed training states), the 100-step protocol figure, the full-frame evaluation,
+the all-reduce cost under data parallel, and a CPU baseline (BASELINE config 1 — the reference's CPU-runnable path:
+pure-torch frequency encoder + nn.Linear stacks — restated in oracle/render_ref.py, timed on the host cores, N=1 only).
+`--gpus N` without torchrun's environment re-launches itself under torch.distributed.run with N ranks.
 """
 import argparse
 import json
@@ -159,7 +162,7 @@ def _cpu_config1(n_rays, threads, warmup, steps, budget_s):
 def cpu_baseline(full=False):
     """config 1, N = 1024 rays x 832 samples, forward + loss + backward, fp32, median step time on k = 1 and
     k = ALL usable host cores (see usable_cores(): os.cpu_count() capped by affinity and cgroup quota — both stated).
-    `full` (the default of bench.py) runs the protocol as written there (10 warm-up + 30 timed steps per leg, ~2 min of CPU
+    `full` (the default of bench.py --full) runs the protocol as written there (10 warm-up + 30 timed steps per leg, ~2 min of CPU
     time); --cpu-baseline-quick takes a bounded sample of it (1 + up to 10 steps per leg inside ~12 s each, at least 3
     timed).  `value` / `cores` = the FASTER leg; both legs are listed.  Validated against the imported reference in the build
     container (tests/test_config1_cpu.py, golden vector G7) and pinned on the GPU box by golden vectors G2 / G4 / G7."""
@@ -474,11 +477,15 @@ def main():
     ap.add_argument("--dp-windows", action="store_true",
                     help="1 GPU: run the table-gradient backward the way data parallel does (one scatter pass + the reduce pass per level window, the exchange a "
                          "no-op) to price the compute side of the DP pipeline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-baseline-full", action="store_true", help="(default since round 4) BASELINE.md 3 protocol in full: 10 warm-up + 30 timed steps per leg")
-    ap.add_argument("--cpu-baseline-quick", action="store_true", help="bounded sample of that protocol (1 + up to 10 steps per leg, ~12 s each)")
-    ap.add_argument("--no-mfma-states", action="store_true", help="skip the two fixed-state MFMA measurements (fresh table with a frozen optimizer; 600-step trained table)")
-    ap.add_argument("--no-eval", action="store_true", help="skip the secondary full-frame evaluation measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well: rooflines and per-entry-point timings, MFMA "
+                         "utilisation (as run and at two fixed states), the 100-step figure, full-frame evaluation, the "
+                         "all-reduce cost (data parallel) and the CPU baseline; the --no-* options below trim it")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--cpu-baseline-full", action="store_true", help="(--full, default since round 4) BASELINE.md 3 protocol in full: 10 warm-up + 30 timed steps per leg")
+    ap.add_argument("--cpu-baseline-quick", action="store_true", help="(--full) bounded sample of that protocol (1 + up to 10 steps per leg, ~12 s each)")
+    ap.add_argument("--no-mfma-states", action="store_true", help="(--full) skip the two fixed-state MFMA measurements (fresh table with a frozen optimizer; 600-step trained table)")
+    ap.add_argument("--no-eval", action="store_true", help="(--full) skip the secondary full-frame evaluation measurement")
     ap.add_argument("--kernel-timers", action="store_true", help="HIP-event timing of every C-ABI call (adds ~4 %%)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32): the "
@@ -605,19 +612,25 @@ def main():
     loss_val = float(loss.detach().float().item())
     # (outside the timed region, before any further step: the state the last timed step left)
     dumped = snapshot_outputs(trainer, model, loss) if args.dump_outputs else None
+    # A plain run (no --full) takes the launch-by-launch region and the MFMA-pass steps below as well, only without the HIP
+    # events and the statistics it does not report: the two repeat regions behind `ms_per_step` follow them, so in either
+    # kind of run those regions time the same point of training, launch by launch.
     graph_info = None
     if use_graph:
         # the same number of steps launch by launch: entry-point timings for the rooflines, and the eager step time beside it
         graph_info = {"graphs_captured": len(trainer._graphs), "host_enqueue_ms_per_step_graph": round(host_ms, 4)}
         trainer.graph = False
-        _hip.enable_timers(all_calls if args.kernel_timers else path_calls)
+        if args.full:
+            _hip.enable_timers(all_calls if args.kernel_timers else path_calls)
         t1 = time.perf_counter()
         for s in range(args.steps):
             trainer.step(*batches[(args.warmup + args.steps + s) % len(batches)], **step_kw)
-        graph_info["host_enqueue_ms_per_step_eager"] = round((time.perf_counter() - t1) * 1e3 / args.steps, 4)
+        host_eager = (time.perf_counter() - t1) * 1e3 / args.steps
         sync()
-        graph_info["ms_per_step_eager"] = round((time.perf_counter() - t1) * 1e3 / args.steps, 3)
-        timers = _hip.disable_timers()
+        if args.full:
+            graph_info["host_enqueue_ms_per_step_eager"] = round(host_eager, 4)
+            graph_info["ms_per_step_eager"] = round((time.perf_counter() - t1) * 1e3 / args.steps, 3)
+            timers = _hip.disable_timers()
 
     def event_table(tm):
         out = {}
@@ -632,15 +645,17 @@ def main():
     #      points and the fraction of samples the colour head really evaluates (weights > 1e-4) recorded per step
     from lidarnerf.nerf import fused
     n_prof = min(args.steps, 5)
-    fused.MASK_STATS = []
-    _hip.enable_timers(mlp_calls)
+    if args.full:
+        fused.MASK_STATS = []
+        _hip.enable_timers(mlp_calls)
     for s in range(n_prof):
         trainer.step(*batches[(args.warmup + args.steps + s) % len(batches)], **step_kw)
     sync()
-    mlp_timers = event_table(_hip.disable_timers())
-    # (the mask fraction belongs to the steps the MLP kernels were timed in: close the collection before anything else runs)
-    mask_frac = float(torch.stack(fused.MASK_STATS).mean().item()) if fused.MASK_STATS else 1.0
-    fused.MASK_STATS = None
+    if args.full:
+        mlp_timers = event_table(_hip.disable_timers())
+        # (the mask fraction belongs to the steps the MLP kernels were timed in: close the collection before anything else runs)
+        mask_frac = float(torch.stack(fused.MASK_STATS).mean().item()) if fused.MASK_STATS else 1.0
+        fused.MASK_STATS = None
     # ---- the same MFMA measurement at two FIXED states (the fraction of samples above the colour mask moves with the
     #      training trajectory, so the as-run figure above depends on --steps / --warmup): (a) a fresh table with the
     #      optimizer frozen (lr = 0: every step sees the initial field, mask ~ 1.0), (b) the 'trained-like' table (the field
@@ -657,7 +672,7 @@ def main():
         return tm, mf, n
 
     mfma_states = {}
-    if world == 1 and not args.no_mfma_states:
+    if args.full and world == 1 and not args.no_mfma_states:
         mk = dict(iters=30000, fp16=True, scale=SCALE, world_size=1,
                   render_kwargs=dict(num_steps=NUM_STEPS, upsample_steps=UPSAMPLE),
                   mlp_dtype=torch.bfloat16 if args.mlp_dtype == "bf16" else torch.float16)
@@ -680,6 +695,10 @@ def main():
                 t3.step(*bats_a[s % 60], **step_kw)
             mfma_states["trained"] = mfma_pass(t3, bats_a, 5)
             del m3, t3
+    if world == 1 and not args.no_mfma_states:
+        # the fixed-state passes end by handing their memory back; a plain run, which skips them, empties the allocator cache
+        # all the same, so that the repeat regions below start from the same allocator state in either kind of run (their
+        # first launch-by-launch steps allocate afresh: ~0.04 ms per step of a 20-step region)
         torch.cuda.empty_cache()
     # ---- spread: the timed region is short (K x ~2.3 ms); repeat it twice more (outside the reported number) and list all
     spread = [round(1e3 * elapsed / args.steps, 3)]
@@ -694,7 +713,7 @@ def main():
     #      100 steps is timed the same way (barrier + synchronize on both sides, MAX over ranks) and reported next to the K-step
     #      figure as `value_100` / `ms_per_step_100` — `value` stays the K-step number the driver's own clock brackets
     ms_100 = None
-    if args.steps < 100:
+    if args.full and args.steps < 100:
         sync()
         t_r = time.perf_counter()
         for s in range(100):
@@ -702,15 +721,16 @@ def main():
         sync()
         ms_100 = round(1e3 * parallel.max_over_ranks(time.perf_counter() - t_r, device) / 100, 4)
     # the roofline below divides by the time of ALL MLP kernels of a step: a renamed entry point must not drop out silently
-    for role in ("density_mlp_forward", "density_mlp_backward", "color_backward", "color_"):
-        fw = [k for k in mlp_timers if role in k and (role != "color_" or "forward" in k)]
-        if not fw:
-            raise RuntimeError(f"bench: no '{role}' entry point was timed in the MFMA pass (got {sorted(mlp_timers)})")
+    if args.full:
+        for role in ("density_mlp_forward", "density_mlp_backward", "color_backward", "color_"):
+            fw = [k for k in mlp_timers if role in k and (role != "color_" or "forward" in k)]
+            if not fw:
+                raise RuntimeError(f"bench: no '{role}' entry point was timed in the MFMA pass (got {sorted(mlp_timers)})")
 
     # ---- data parallel: the same step with the gradient exchange switched off (every rank keeps its own gradient;
     #      timing only, the replicas are not used afterwards) -> all-reduce cost = inclusive - exclusive
     comm = None
-    if world > 1:
+    if args.full and world > 1:
         saved_ws, saved_dp, trainer.world, trainer.dp = parallel.world_size, parallel.dp_active, 1, False
         parallel.world_size = lambda: 1
         parallel.dp_active = lambda: False
@@ -757,119 +777,120 @@ def main():
     if args.steps < 100:
         elapsed = sorted(spread)[1] * args.steps / 1e3
     rays_total = args.rays * world * args.steps
-    kernels = event_table(timers)
-    if "lnh_grid_encode_backward_ws_begin" in kernels:  # DP: one scatter (begin) + the window reduces (finish) = one logical launch
-        kb, kf = kernels.pop("lnh_grid_encode_backward_ws_begin"), kernels.pop("lnh_grid_encode_backward_ws_finish")
-        tot = kb["total_ms"] + kf["total_ms"]
-        kernels["lnh_grid_encode_backward_ws"] = {"calls": args.steps, "total_ms": round(tot, 3),
-                                                  "avg_us": round(1e3 * tot / args.steps, 2),
-                                                  "points": args.rays * (NUM_STEPS + UPSAMPLE) * args.steps,
-                                                  "note": "begin (scatter pass) + one finish call (reduce pass) per level window, per step",
-                                                  "begin_avg_us": kb["avg_us"], "finish_avg_us": kf["avg_us"]}
-    fwd_names = ("lnh_grid_encode_forward", "lnh_grid_encode_forward_mapped")
-    bwd_names = ("lnh_grid_encode_backward", "lnh_grid_encode_backward_ws")
-    dom = max(fwd_names + bwd_names, key=lambda k: kernels.get(k, {}).get("total_ms", 0))
-    pmc_file, pmc, pmc_lib = _latest_pmc()
-    this_lib = lib_sha16()
-    # (round 4: the plain level classes have their own scatter kernel; older PMC files know k_grid_bwd_scatter only)
-    scatter_name = "k_grid_bwd_scatter_plain" if "k_grid_bwd_scatter_plain" in pmc else "k_grid_bwd_scatter"
-    pmc_names = {"lnh_grid_encode_backward_ws": (scatter_name, "k_grid_bwd_reduce"),
-                 "lnh_grid_encode_forward_mapped": ("k_grid_forward",), "lnh_grid_encode_forward": ("k_grid_forward",)}
+    if args.full:  # ---- the figures beside the headline: per-entry-point table, rooflines, MFMA utilisation
+        kernels = event_table(timers)
+        if "lnh_grid_encode_backward_ws_begin" in kernels:  # DP: one scatter (begin) + the window reduces (finish) = one logical launch
+            kb, kf = kernels.pop("lnh_grid_encode_backward_ws_begin"), kernels.pop("lnh_grid_encode_backward_ws_finish")
+            tot = kb["total_ms"] + kf["total_ms"]
+            kernels["lnh_grid_encode_backward_ws"] = {"calls": args.steps, "total_ms": round(tot, 3),
+                                                      "avg_us": round(1e3 * tot / args.steps, 2),
+                                                      "points": args.rays * (NUM_STEPS + UPSAMPLE) * args.steps,
+                                                      "note": "begin (scatter pass) + one finish call (reduce pass) per level window, per step",
+                                                      "begin_avg_us": kb["avg_us"], "finish_avg_us": kf["avg_us"]}
+        fwd_names = ("lnh_grid_encode_forward", "lnh_grid_encode_forward_mapped")
+        bwd_names = ("lnh_grid_encode_backward", "lnh_grid_encode_backward_ws")
+        dom = max(fwd_names + bwd_names, key=lambda k: kernels.get(k, {}).get("total_ms", 0))
+        pmc_file, pmc, pmc_lib = _latest_pmc()
+        this_lib = lib_sha16()
+        # (round 4: the plain level classes have their own scatter kernel; older PMC files know k_grid_bwd_scatter only)
+        scatter_name = "k_grid_bwd_scatter_plain" if "k_grid_bwd_scatter_plain" in pmc else "k_grid_bwd_scatter"
+        pmc_names = {"lnh_grid_encode_backward_ws": (scatter_name, "k_grid_bwd_reduce"),
+                     "lnh_grid_encode_forward_mapped": ("k_grid_forward",), "lnh_grid_encode_forward": ("k_grid_forward",)}
 
-    def hbm_roofline(name):
-        k = kernels[name]
-        per_pt = GRID_FWD_BYTES if "forward" in name else GRID_BWD_BYTES
-        avg_points = k["points"] / k["calls"]
-        achieved = per_pt * k["points"] / (k["total_ms"] * 1e-3) / 1e9  # GB/s over all launches of that entry point
-        # HBM bytes per launch from the newest committed PMC pass of this same command (profiles/collect.sh);
-        # bench.py itself cannot run rocprofv3.  Scaled to this call's points (the PMC pass profiles whole launches).
-        traffic, src = None, None
-        parts = [pmc.get(n, {}).get("hbm_bytes_per_launch") for n in pmc_names.get(name, ())]
-        if not (pmc_file and parts and all(p is not None for p in parts)):
-            src = "no committed PMC pass (profiles/r*_pmc.json) covers this entry point: traffic not reported"
-        elif args.rays != 4096 or args.table != "init" or args.patch.lower() != "1x1" or args.dp_windows:
-            # the PMC passes profile the default command (4096 rays, fresh table): bytes per launch of another workload
-            # are not that number scaled — say so instead of quoting it
-            src = f"{pmc_file} was collected on the default workload (4096 rays, fresh table, 1x1 rays): not quoted for this one"
-        else:
-            traffic, src = int(sum(parts)), f"{pmc_file} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes: " + \
-                " + ".join(pmc_names[name]) + ")"
-            if pmc_lib is None:
-                src += "; that file does not record which library it profiled"
-            elif pmc_lib != this_lib:
-                src += f"; COLLECTED ON ANOTHER BUILD of the library (sha256 {pmc_lib} there, {this_lib} running now): " \
-                       "re-run profiles/collect.sh"
+        def hbm_roofline(name):
+            k = kernels[name]
+            per_pt = GRID_FWD_BYTES if "forward" in name else GRID_BWD_BYTES
+            avg_points = k["points"] / k["calls"]
+            achieved = per_pt * k["points"] / (k["total_ms"] * 1e-3) / 1e9  # GB/s over all launches of that entry point
+            # HBM bytes per launch from the newest committed PMC pass of this same command (profiles/collect.sh);
+            # bench.py itself cannot run rocprofv3.  Scaled to this call's points (the PMC pass profiles whole launches).
+            traffic, src = None, None
+            parts = [pmc.get(n, {}).get("hbm_bytes_per_launch") for n in pmc_names.get(name, ())]
+            if not (pmc_file and parts and all(p is not None for p in parts)):
+                src = "no committed PMC pass (profiles/r*_pmc.json) covers this entry point: traffic not reported"
+            elif args.rays != 4096 or args.table != "init" or args.patch.lower() != "1x1" or args.dp_windows:
+                # the PMC passes profile the default command (4096 rays, fresh table): bytes per launch of another workload
+                # are not that number scaled — say so instead of quoting it
+                src = f"{pmc_file} was collected on the default workload (4096 rays, fresh table, 1x1 rays): not quoted for this one"
             else:
-                src += f"; same library as the one running now (sha256 {this_lib})"
-        return {"bound": "hbm", "kernel": name, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": src,
-                "traffic_lib_matches": (pmc_lib == this_lib) if (traffic is not None and pmc_lib is not None) else None,
-                "algorithmic_bytes_per_launch": int(per_pt * avg_points), "bytes_per_point": per_pt,
-                "points_per_launch": int(avg_points), "avg_launch_us": k["avg_us"]}
+                traffic, src = int(sum(parts)), f"{pmc_file} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes: " + \
+                    " + ".join(pmc_names[name]) + ")"
+                if pmc_lib is None:
+                    src += "; that file does not record which library it profiled"
+                elif pmc_lib != this_lib:
+                    src += f"; COLLECTED ON ANOTHER BUILD of the library (sha256 {pmc_lib} there, {this_lib} running now): " \
+                           "re-run profiles/collect.sh"
+                else:
+                    src += f"; same library as the one running now (sha256 {this_lib})"
+            return {"bound": "hbm", "kernel": name, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": src,
+                    "traffic_lib_matches": (pmc_lib == this_lib) if (traffic is not None and pmc_lib is not None) else None,
+                    "algorithmic_bytes_per_launch": int(per_pt * avg_points), "bytes_per_point": per_pt,
+                    "points_per_launch": int(avg_points), "avg_launch_us": k["avg_us"]}
 
-    # MFMA utilisation of the MLP kernels: BASELINE.md §4 flops (6 144 sigma + 22 528 * mask fraction colour per sample
-    # forward, backward = 2x) over the summed HIP-event time of the four MLP entry points, against the dense fp16 peak
-    pts = args.rays * (NUM_STEPS + UPSAMPLE)
+        # MFMA utilisation of the MLP kernels: BASELINE.md §4 flops (6 144 sigma + 22 528 * mask fraction colour per sample
+        # forward, backward = 2x) over the summed HIP-event time of the four MLP entry points, against the dense fp16 peak
+        pts = args.rays * (NUM_STEPS + UPSAMPLE)
 
-    def mfma_entry(tm, mf, n):
-        tm = {k: v for k, v in tm.items() if k in mlp_calls}  # (the fixed-state passes time the encoder calls as well)
-        ms = sum(v["total_ms"] for v in tm.values()) / max(n, 1)
-        fl = 3 * pts * (SIGMA_FLOPS + COLOR_FLOPS * mf)
-        fl_exec = 3 * pts * (SIGMA_FLOPS + COLOR_FLOPS_EXECUTED * mf)
-        tf_ = fl / (ms * 1e-3) / 1e12 if ms else 0.0
-        tf_exec = fl_exec / (ms * 1e-3) / 1e12 if ms else 0.0
-        return {"achieved": round(tf_, 1), "frac": round(tf_ / MFMA_PEAK_TFLOPS, 4), "flops_per_step": int(fl),
-                "mask_fraction": round(mf, 4), "mlp_kernel_ms_per_step": round(ms, 4),
-                "executed_tflops": round(tf_exec, 1), "executed_frac": round(tf_exec / MFMA_PEAK_TFLOPS, 4),
-                "per_kernel_us": {k: v["avg_us"] for k, v in tm.items()}}
+        def mfma_entry(tm, mf, n):
+            tm = {k: v for k, v in tm.items() if k in mlp_calls}  # (the fixed-state passes time the encoder calls as well)
+            ms = sum(v["total_ms"] for v in tm.values()) / max(n, 1)
+            fl = 3 * pts * (SIGMA_FLOPS + COLOR_FLOPS * mf)
+            fl_exec = 3 * pts * (SIGMA_FLOPS + COLOR_FLOPS_EXECUTED * mf)
+            tf_ = fl / (ms * 1e-3) / 1e12 if ms else 0.0
+            tf_exec = fl_exec / (ms * 1e-3) / 1e12 if ms else 0.0
+            return {"achieved": round(tf_, 1), "frac": round(tf_ / MFMA_PEAK_TFLOPS, 4), "flops_per_step": int(fl),
+                    "mask_fraction": round(mf, 4), "mlp_kernel_ms_per_step": round(ms, 4),
+                    "executed_tflops": round(tf_exec, 1), "executed_frac": round(tf_exec / MFMA_PEAK_TFLOPS, 4),
+                    "per_kernel_us": {k: v["avg_us"] for k, v in tm.items()}}
 
-    # the headline MFMA figure is the one of THIS run (round 4 headlined the favourable fixed state; the fixed states stay
-    # beside it so that the number can be compared across rounds whatever --steps / --warmup the caller chose)
-    as_run = mfma_entry(mlp_timers, mask_frac, n_prof)
-    roofline_mfma = dict({"bound": "mfma", "kernel": "+".join(sorted(mlp_timers)), "peak": MFMA_PEAK_TFLOPS,
-                          "unit": "TFLOP/s", "state": "as_run"}, **as_run)
-    roofline_mfma["states"] = dict({"as_run": dict(as_run, note=f"the {n_prof} steps after the timed region of THIS run "
-                                                                   f"(--warmup {args.warmup} --steps {args.steps}): the mask "
-                                                                   "fraction depends on how far training got")},
-                                   **{k: mfma_entry(*v) for k, v in mfma_states.items()})
-    roofline_mfma["note"] = ("flops per SURVEY 8(d): 3 x points x (6144 + 22528 x mask fraction), 'frac' = that nominal count over "
-                             "the dense fp16 peak; 'executed_frac' counts the colour head at the K = 16 per sample the kernels "
-                             "really multiply (the 75 direction columns are folded into a per-ray term) and is the hardware "
-                             "figure; the headline is the state 'as_run' (the steps right after the timed region of this run); "
-                             "'fresh_frozen' = fresh table with the optimizer frozen at lr = 0 (every step sees the initial "
-                             "field, mask ~ 1.0), 'trained' = after --pretrain-steps untimed steps on the analytic scene (mask "
-                             "~ 0.1); the MLP kernels also read the encoder output and write activations: at 61 flop/B the sigma "
-                             "net is HBM-bound by construction (DESIGN.md)")
+        # the headline MFMA figure is the one of THIS run (round 4 headlined the favourable fixed state; the fixed states stay
+        # beside it so that the number can be compared across rounds whatever --steps / --warmup the caller chose)
+        as_run = mfma_entry(mlp_timers, mask_frac, n_prof)
+        roofline_mfma = dict({"bound": "mfma", "kernel": "+".join(sorted(mlp_timers)), "peak": MFMA_PEAK_TFLOPS,
+                              "unit": "TFLOP/s", "state": "as_run"}, **as_run)
+        roofline_mfma["states"] = dict({"as_run": dict(as_run, note=f"the {n_prof} steps after the timed region of THIS run "
+                                                                       f"(--warmup {args.warmup} --steps {args.steps}): the mask "
+                                                                       "fraction depends on how far training got")},
+                                       **{k: mfma_entry(*v) for k, v in mfma_states.items()})
+        roofline_mfma["note"] = ("flops per SURVEY 8(d): 3 x points x (6144 + 22528 x mask fraction), 'frac' = that nominal count over "
+                                 "the dense fp16 peak; 'executed_frac' counts the colour head at the K = 16 per sample the kernels "
+                                 "really multiply (the 75 direction columns are folded into a per-ray term) and is the hardware "
+                                 "figure; the headline is the state 'as_run' (the steps right after the timed region of this run); "
+                                 "'fresh_frozen' = fresh table with the optimizer frozen at lr = 0 (every step sees the initial "
+                                 "field, mask ~ 1.0), 'trained' = after --pretrain-steps untimed steps on the analytic scene (mask "
+                                 "~ 0.1); the MLP kernels also read the encoder output and write activations: at 61 flop/B the sigma "
+                                 "net is HBM-bound by construction (DESIGN.md)")
 
-    # ---- path-level HBM roofline (north_star states its 60 % bar on encode + composite together): algorithmic bytes of the
-    #      encode forward (588 B), the encode backward (1100 B) and the compositing (44 B) per sample point of a step over
-    #      the summed HIP-event time of the kernels that do that work.  The forward compositing sums are formed inside the
-    #      fused forward tail (merged weights + colour head + sums, one kernel per ray): 'frac' charges that kernel's WHOLE
-    #      time to the path (conservative), 'frac_encode_only' is encode forward + backward alone.
-    def path_entry(tm, n, note):
-        def ms_of(names):
-            return sum(tm[k]["total_ms"] for k in names if k in tm) / max(n, 1)
-        t_fwd = ms_of(fwd_names)
-        t_bwd = ms_of(bwd_names + ("lnh_grid_encode_backward_ws_begin", "lnh_grid_encode_backward_ws_finish"))
-        t_cb, t_tail = ms_of(("lnh_lidar_composite_backward",)), ms_of(("lnh_lidar_color_composite_forward" + sfx,))
-        b_enc = (GRID_FWD_BYTES + GRID_BWD_BYTES) * pts
-        b_all = b_enc + COMPOSITE_BYTES * pts
-        t_all = t_fwd + t_bwd + t_cb + t_tail
-        if not (t_fwd and t_bwd):
-            return None
-        return {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "achieved": round(b_all / (t_all * 1e-3) / 1e9, 1), "frac": round(b_all / (t_all * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                "frac_encode_only": round(b_enc / ((t_fwd + t_bwd) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                "algorithmic_bytes_per_step": int(b_all), "bytes_per_point": GRID_FWD_BYTES + GRID_BWD_BYTES + COMPOSITE_BYTES,
-                "kernel_ms_per_step": {"encode_forward": round(t_fwd, 4), "encode_backward": round(t_bwd, 4),
-                                       "composite_backward": round(t_cb, 4), "fused_forward_tail": round(t_tail, 4)},
-                "note": note}
+        # ---- path-level HBM roofline (north_star states its 60 % bar on encode + composite together): algorithmic bytes of the
+        #      encode forward (588 B), the encode backward (1100 B) and the compositing (44 B) per sample point of a step over
+        #      the summed HIP-event time of the kernels that do that work.  The forward compositing sums are formed inside the
+        #      fused forward tail (merged weights + colour head + sums, one kernel per ray): 'frac' charges that kernel's WHOLE
+        #      time to the path (conservative), 'frac_encode_only' is encode forward + backward alone.
+        def path_entry(tm, n, note):
+            def ms_of(names):
+                return sum(tm[k]["total_ms"] for k in names if k in tm) / max(n, 1)
+            t_fwd = ms_of(fwd_names)
+            t_bwd = ms_of(bwd_names + ("lnh_grid_encode_backward_ws_begin", "lnh_grid_encode_backward_ws_finish"))
+            t_cb, t_tail = ms_of(("lnh_lidar_composite_backward",)), ms_of(("lnh_lidar_color_composite_forward" + sfx,))
+            b_enc = (GRID_FWD_BYTES + GRID_BWD_BYTES) * pts
+            b_all = b_enc + COMPOSITE_BYTES * pts
+            t_all = t_fwd + t_bwd + t_cb + t_tail
+            if not (t_fwd and t_bwd):
+                return None
+            return {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "achieved": round(b_all / (t_all * 1e-3) / 1e9, 1), "frac": round(b_all / (t_all * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                    "frac_encode_only": round(b_enc / ((t_fwd + t_bwd) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                    "algorithmic_bytes_per_step": int(b_all), "bytes_per_point": GRID_FWD_BYTES + GRID_BWD_BYTES + COMPOSITE_BYTES,
+                    "kernel_ms_per_step": {"encode_forward": round(t_fwd, 4), "encode_backward": round(t_bwd, 4),
+                                           "composite_backward": round(t_cb, 4), "fused_forward_tail": round(t_tail, 4)},
+                    "note": note}
 
-    roofline_path = path_entry(kernels, args.steps, "as run: the launch-by-launch region of this run (the timed workload)")
-    if roofline_path is not None:
-        roofline_path["state"] = "as_run"
-        roofline_path["states"] = {k: path_entry(v[0], v[2], "fixed state, see roofline_mfma.note") for k, v in mfma_states.items()
-                                   if path_entry(v[0], v[2], "") is not None}
+        roofline_path = path_entry(kernels, args.steps, "as run: the launch-by-launch region of this run (the timed workload)")
+        if roofline_path is not None:
+            roofline_path["state"] = "as_run"
+            roofline_path["states"] = {k: path_entry(v[0], v[2], "fixed state, see roofline_mfma.note") for k, v in mfma_states.items()
+                                       if path_entry(v[0], v[2], "") is not None}
     result = {
         "metric": "train rays/sec (encode+MLP+composite+bwd), KITTI-360 66x1030",
         "value": round(rays_total / elapsed, 1), "unit": "rays/s", "n_gpus": world, "steps": args.steps,
@@ -886,17 +907,20 @@ def main():
                    "patch": args.patch, "dp_windows_forced": bool(args.dp_windows),
                    "optimizer": "Adam + dynamic loss scaling + lr schedule, in the timed region (lnh_train_check + lnh_train_step: the hash table and the MLP tensors in two launches)", "final_loss": round(loss_val, 5)},
         "ms_per_step_repeats": spread,  # three timed regions of K steps each; `value` / `ms_per_step` = their median when K < 100
-        "ms_per_step_100": ms_100 if ms_100 is not None else round(1e3 * elapsed / args.steps, 4),
-        "value_100": round(args.rays * world / ((ms_100 if ms_100 is not None else 1e3 * elapsed / args.steps) * 1e-3), 1),
-        "value_100_note": "SURVEY 8(d) protocol figure: one timed region of 100 steps (the K-step region itself when K >= 100), "
-                          "same bracketing as `value`",
         "ms_per_step_first_region": round(1e3 * elapsed_first / args.steps, 3),
-        "roofline": hbm_roofline(dom),
-        "roofline_fwd": hbm_roofline(max(fwd_names, key=lambda k: kernels.get(k, {}).get("total_ms", 0))),
-        "roofline_mfma": roofline_mfma,
-        "roofline_path": roofline_path,
-        "kernels": kernels,
     }
+    if args.full:
+        result.update({
+            "ms_per_step_100": ms_100 if ms_100 is not None else round(1e3 * elapsed / args.steps, 4),
+            "value_100": round(args.rays * world / ((ms_100 if ms_100 is not None else 1e3 * elapsed / args.steps) * 1e-3), 1),
+            "value_100_note": "SURVEY 8(d) protocol figure: one timed region of 100 steps (the K-step region itself when K >= 100), "
+                              "same bracketing as `value`",
+            "roofline": hbm_roofline(dom),
+            "roofline_fwd": hbm_roofline(max(fwd_names, key=lambda k: kernels.get(k, {}).get("total_ms", 0))),
+            "roofline_mfma": roofline_mfma,
+            "roofline_path": roofline_path,
+            "kernels": kernels,
+        })
     if getattr(trainer, "graph_error", None):
         result["graph"] = {"error": trainer.graph_error, "note": "capture failed: every step was issued launch by launch"}
     if graph_info is not None:
@@ -913,7 +937,7 @@ def main():
         result["pretrain"] = pretrain
     # secondary number of SURVEY §8(d): full-frame evaluation (67 980 rays of a 66 x 1030 range image, staged in
     # chunks of 4096, no perturbation, no gradient) — reported beside the headline metric, never instead of it
-    if world == 1 and not args.no_eval:
+    if args.full and world == 1 and not args.no_eval:
         model.eval()
         frame = make_batch(poses, 0, 66 * 1030, rank, device)
         with torch.no_grad(), torch.autocast("cuda", dtype=trainer.amp_dtype):
@@ -931,7 +955,7 @@ def main():
         result["eval"] = {"metric": "full-frame eval rays/sec (66x1030, staged 4096)", "value": round(66 * 1030 / dt, 1),
                           "unit": "rays/s", "ms_per_frame": round(1e3 * dt, 3)}
         model.train()
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(full=not args.cpu_baseline_quick)
     _flush_c_stdout()  # (RCCL prints its version banner through C stdio: it must not land BEHIND the line)
     print(json.dumps(result), flush=True)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # MFMA / issue counters of the four MLP kernels of a training step:  bash profiles/collect_mfma.sh r02
-# (rocprofv3 --pmc passes over `python bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-eval`, kernel trace only)
+# (rocprofv3 --pmc passes over `python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-eval`, kernel trace only)
 tag=${1:-r06}
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-/root/repo}"
 out=gpurun_out/profiles; mkdir -p $out
@@ -12,7 +12,7 @@ groups=(
 i=0
 for g in "${groups[@]}"; do
   rm -rf /tmp/mf_$i
-  timeout 300 rocprofv3 --pmc $g --kernel-trace --output-format csv -d /tmp/mf_$i -o r -- python bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-eval > /tmp/mf_$i.log 2>&1 || echo "group $i failed"
+  timeout 300 rocprofv3 --pmc $g --kernel-trace --output-format csv -d "$TMPDIR/mf_$i" -o r -- python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-eval > "$TMPDIR/mf_$i.log" 2>&1 || echo "group $i failed"
   i=$((i+1))
 done
 python - $out/${tag}_mfma_counters.json <<'PY'
@@ -33,7 +33,7 @@ for k, c in res.items():
     if "SQ_VALU_MFMA_BUSY_CYCLES" in c and "GRBM_GUI_ACTIVE" in c:
         # MFMA-busy cycles are summed over the 1024 SIMDs of the chip; GUI_ACTIVE over the 8 XCDs
         c["mfma_busy_fraction"] = round(c["SQ_VALU_MFMA_BUSY_CYCLES"] / 1024 / (c["GRBM_GUI_ACTIVE"] / 8), 4)
-json.dump({"command": "rocprofv3 --pmc <group> --kernel-trace -- python bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-eval "
+json.dump({"command": "rocprofv3 --pmc <group> --kernel-trace -- python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-eval "
                       "(average per launch; k_mlp_forward runs twice per step: 3.15 M coarse + 0.26 M fine points)",
            "kernels": res}, open(sys.argv[1], "w"), indent=1, sort_keys=True)
 print(json.dumps(res, indent=1, sort_keys=True))

@@ -32,14 +32,14 @@ def test_data_parallel_training_step_matches_single_process(ranks):
 
 
 def test_bench_launches_its_own_ranks_and_reports_the_exchange():
-    """`python bench.py --gpus 2` outside torchrun re-launches itself with 2 ranks (here: gloo, both on GPU 0), prints ONE
-    JSON line for the whole job with the all-reduce cost reported separately; a rank/`--gpus` mismatch is refused."""
+    """`python bench.py --gpus 2 --full` outside torchrun re-launches itself with 2 ranks (here: gloo, both on GPU 0), prints
+    ONE JSON line for the whole job with the all-reduce cost reported separately; a rank/`--gpus` mismatch is refused."""
     import json
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(LNH_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--rays", "256",
-           "--no-eval", "--no-cpu-baseline"]
+           "--full", "--no-eval", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -2,7 +2,7 @@
 2-rank gloo tests cannot cover.  SKIPS on a box with fewer than 2 visible GPUs (every box this build has seen so far); it runs
 the day a multi-GPU node exists: tests/dp_worker.py under torch.distributed.run with LNH_DIST_BACKEND=nccl — windowed fp16
 all-reduce == single-process gradient, identical tables after DP steps, sharded table optimizer == replicated, sharded
-evaluation == whole-frame evaluation — and `bench.py --gpus 2` with its `comm` block."""
+evaluation == whole-frame evaluation — and `bench.py --gpus 2 --full` with its `comm` block."""
 import json
 import os
 import subprocess
@@ -46,8 +46,8 @@ def test_rccl_bench_two_gpus():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT",
                                                             "LNH_DIST_BACKEND")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--no-eval",
-           "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--full",
+           "--no-eval", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])

@@ -1,6 +1,6 @@
 #!/bin/bash
 # One GPU call for profiles/: bash tools/collect_all.sh r04  (from the repository root on a GPU box).
-#   profiles/collect.sh            default bench line (with cpu_baseline: BASELINE.md 3's 10 + 30 protocol), kernel trace,
+#   profiles/collect.sh            default bench line with --full (cpu_baseline: BASELINE.md 3's 10 + 30 protocol), kernel trace,
 #                                  FETCH / WRITE_SIZE passes (the PMC file records the library hash it was collected on)
 #   bench variants: 16 384 rays, bf16 MLP operands, both (BASELINE config 5), the occupancy-grid workload (config 4) as a
 #   replayed hipGraph and launch by launch, the 'trained-like' table of SURVEY 8(d), the data-parallel backward priced on
@@ -17,13 +17,13 @@ if [ -n "$WITH_COUNTERS" ]; then
   timeout 250 bash profiles/collect_mfma.sh $tag > gpurun_out/cm.log 2>&1
 fi
 b() { name=$1; shift; timeout 300 python bench.py "$@" > $out/${tag}_bench_$name.json 2> /dev/null; }
-b 16384 --rays 16384 --no-cpu-baseline
-b bf16 --mlp-dtype bf16 --no-cpu-baseline
-b 16384_bf16 --rays 16384 --mlp-dtype bf16 --no-cpu-baseline
+b 16384 --full --rays 16384 --no-cpu-baseline
+b bf16 --full --mlp-dtype bf16 --no-cpu-baseline
+b 16384_bf16 --full --rays 16384 --mlp-dtype bf16 --no-cpu-baseline
 b nerfmvl --workload nerfmvl --steps 128 --warmup 16
 b nerfmvl_nograph --workload nerfmvl --steps 128 --warmup 16 --no-graph
-b trained --table trained --no-cpu-baseline
-b dpwindows --dp-windows --no-cpu-baseline --no-eval
+b trained --full --table trained --no-cpu-baseline
+b dpwindows --full --dp-windows --no-cpu-baseline --no-eval
 # kernel trace of the config-4 step (replayed graph): per-kernel time per step
 rm -rf /tmp/prof_mvl
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_mvl -o r -- python bench.py --workload nerfmvl --steps 128 --warmup 16 > /dev/null 2>&1
