@@ -100,53 +100,35 @@ LNH_API uint64_t lnh_grid_backward_workspace_size(const int32_t *offsets_host, u
 LNH_API uint64_t lnh_grid_backward_workspace_size_min(const int32_t *offsets_host, uint32_t B, uint32_t D, uint32_t C,
                                                       uint32_t L, float S, uint32_t H, uint32_t gridtype,
                                                       int align_corners, int dtype);
-/* Host-side description of that workspace's bucket plan for `level` (no device work): out[0] = table buckets of the
- * level, out[1] = pool slots per bucket (what exceeds them goes to the level's spill list), out[2] = rows per bucket,
- * out[3] = entries per reduce slice (a bucket with more is reduced by several workgroups).  The sum the call produces
- * never depends on these numbers — integer accumulation (see grid.hip) — the tests use them to build inputs that
- * overflow a bucket by a few entries or split one.  Returns LNH_ERR_UNSUPPORTED where workspace_size returns 0. */
 /* Testing knob, process-wide: entries per reduce slice (0 restores the default, 512 K; clamped to [1024, 512 K]) — with the
  * default only a concentrated batch of more than half a million entries per bucket is reduced in slices; a small value
  * lets the tests reach that path with small inputs.  Set it BEFORE lnh_grid_backward_workspace_size (more slices need
  * more image slots).  Never changes a result. */
 LNH_API void lnh_grid_backward_set_slice_entries(uint32_t entries);
+/* Host-side description of that workspace's bucket plan for `level` (no device work): out[0] = table buckets of the
+ * level, out[1] = pool slots per bucket (what exceeds them goes to the level's spill list), out[2] = rows per bucket,
+ * out[3] = entries per reduce slice (a bucket with more is reduced by several workgroups).  The sum the call produces
+ * never depends on these numbers — integer accumulation (see grid.hip) — the tests use them to build inputs that
+ * overflow a bucket by a few entries or split one.  Returns LNH_ERR_UNSUPPORTED where workspace_size returns 0. */
 LNH_API int lnh_grid_backward_plan_info(const int32_t *offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
                                         float S, uint32_t H, uint32_t gridtype, int align_corners, int dtype,
                                         uint32_t level, uint32_t *out4);
-LNH_API int lnh_grid_encode_backward_ws(const void *grad, const float *inputs, const int32_t *offsets_host,
-                                        void *grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S,
-                                        uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp, int dtype,
-                                        void *workspace, uint64_t workspace_bytes, lnh_stream_t stream);
-/* Same, restricted to the levels [level_begin, level_end): rows of other levels are not touched.  Lets a data-parallel
- * caller hand the gradient of finished levels to the all-reduce while later levels are still being reduced. */
-LNH_API int lnh_grid_encode_backward_ws_levels(const void *grad, const float *inputs, const int32_t *offsets_host,
-                                               void *grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
-                                               float S, uint32_t H, uint32_t gridtype, int align_corners,
-                                               uint32_t interp, int dtype, void *workspace, uint64_t workspace_bytes,
-                                               uint32_t level_begin, uint32_t level_end, lnh_stream_t stream);
-/* The same backward in two steps for a data-parallel caller (bit-identical result): `_begin` runs everything except the
- * reduce pass of the (last) chunk; `_finish` runs that reduce pass for the levels [level_begin, level_end), after which
- * their rows of grad_embeddings are final.  Call `_begin` once, then `_finish` for consecutive level windows covering
- * [0, L), with the same arguments and the same workspace on the same stream: the gradient of a finished window can go to
- * the all-reduce while the next window is being reduced, and the scatter pass is NOT cut into windows (which costs it a
- * quarter of its speed). */
-LNH_API int lnh_grid_encode_backward_ws_begin(const void *grad, const float *inputs, const int32_t *offsets_host,
-                                              void *grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
-                                              float S, uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp,
-                                              int dtype, void *workspace, uint64_t workspace_bytes, lnh_stream_t stream);
-LNH_API int lnh_grid_encode_backward_ws_finish(const void *grad, const float *inputs, const int32_t *offsets_host,
-                                               void *grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
-                                               float S, uint32_t H, uint32_t gridtype, int align_corners,
-                                               uint32_t interp, int dtype, void *workspace, uint64_t workspace_bytes,
-                                               uint32_t level_begin, uint32_t level_end, lnh_stream_t stream);
-/* The same entry points behind ONE signature, for a caller that has just cleared its buffers itself (a training step that
- * clears every accumulated-into buffer of its backward pass with one lnh_zero_regions launch):
- *   split  0 = lnh_grid_encode_backward_ws_levels, 1 = ..._begin (level_begin / level_end ignored), 2 = ..._finish
- *   flags  LNH_BWD_WS_CLEARED: the first lnh_grid_backward_workspace_clear_bytes(...) bytes of `workspace` are zero on
+/* The bucketed backward.  One implementation, lnh_grid_encode_backward_ws_ex; the four entry points after it forward to it.
+ *   level_begin, level_end   only the levels [level_begin, level_end) are worked on; rows of other levels are not touched.
+ *          level_end > L is clamped to L; level_begin > level_end returns LNH_ERR_INVALID_ARG.
+ *   split  0: the whole backward of those levels.
+ *          1 ("begin"): everything except the reduce pass of the (last) chunk, for ALL levels (the window is checked, then
+ *          ignored); 2 ("finish"): that reduce pass for the levels of the window, after which their rows of grad_embeddings
+ *          are final.  A data-parallel caller runs begin once, then finish for consecutive windows covering [0, L), with the
+ *          same arguments and the same workspace on the same stream: the gradient of a finished window can go to the
+ *          all-reduce while the next window is being reduced, and the scatter pass is NOT cut into windows (which costs it a
+ *          quarter of its speed).  The result is bit-identical to split 0.
+ *   flags  for a caller that has just cleared its buffers itself (a training step that clears every accumulated-into buffer
+ *          of its backward pass with one lnh_zero_regions launch); a caller that sets one without having cleared gets garbage.
+ *          LNH_BWD_WS_CLEARED: the first lnh_grid_backward_workspace_clear_bytes(...) bytes of `workspace` are zero on
  *          entry (the cursors of the batch's FIRST chunk: that chunk's clear launch is skipped);
  *          LNH_BWD_TABLE_ZERO: grad_embeddings holds zeros on entry — the reduce pass of the first chunk stores its sums
  *          instead of adding them to rows it would have to read first (the same values: 0 + x).
- * A caller that sets a flag without having cleared gets garbage; without flags this is exactly the entry point `split` names.
  * lnh_grid_backward_workspace_clear_bytes: size of that head for the chunk plan the call will choose for `workspace_bytes`
  * (0: unsupported configuration / workspace too small). */
 #define LNH_BWD_WS_CLEARED 1u
@@ -160,6 +142,28 @@ LNH_API uint64_t lnh_grid_backward_workspace_clear_bytes(const int32_t *offsets_
                                                          uint32_t L, float S, uint32_t H, uint32_t gridtype,
                                                          int align_corners, uint32_t interp, int dtype,
                                                          uint64_t workspace_bytes);
+/* = lnh_grid_encode_backward_ws_ex(..., 0, L, 0, 0): all levels in one call. */
+LNH_API int lnh_grid_encode_backward_ws(const void *grad, const float *inputs, const int32_t *offsets_host,
+                                        void *grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S,
+                                        uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp, int dtype,
+                                        void *workspace, uint64_t workspace_bytes, lnh_stream_t stream);
+/* = ..._ws_ex(..., level_begin, level_end, 0, 0), except that level_end > L returns LNH_ERR_INVALID_ARG (not clamped). */
+LNH_API int lnh_grid_encode_backward_ws_levels(const void *grad, const float *inputs, const int32_t *offsets_host,
+                                               void *grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
+                                               float S, uint32_t H, uint32_t gridtype, int align_corners,
+                                               uint32_t interp, int dtype, void *workspace, uint64_t workspace_bytes,
+                                               uint32_t level_begin, uint32_t level_end, lnh_stream_t stream);
+/* = ..._ws_ex(..., 0, L, 1, 0). */
+LNH_API int lnh_grid_encode_backward_ws_begin(const void *grad, const float *inputs, const int32_t *offsets_host,
+                                              void *grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
+                                              float S, uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp,
+                                              int dtype, void *workspace, uint64_t workspace_bytes, lnh_stream_t stream);
+/* = ..._ws_ex(..., level_begin, level_end, 2, 0), except that level_end > L returns LNH_ERR_INVALID_ARG (not clamped). */
+LNH_API int lnh_grid_encode_backward_ws_finish(const void *grad, const float *inputs, const int32_t *offsets_host,
+                                               void *grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
+                                               float S, uint32_t H, uint32_t gridtype, int align_corners,
+                                               uint32_t interp, int dtype, void *workspace, uint64_t workspace_bytes,
+                                               uint32_t level_begin, uint32_t level_end, lnh_stream_t stream);
 /*
  * Replaces grad_total_variation  gridencoder.h:43-55 (gridencoder.cu:695-910): adds the TV-regulariser gradient
  * of the cells visited by `inputs` into `grad` (same layout as embeddings).

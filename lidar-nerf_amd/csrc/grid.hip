@@ -1762,9 +1762,21 @@ k_grid_bwd_reduce(T *__restrict__ grad_table, GridMeta meta, BucketPlan plan, co
 // whatever does not fit goes to the level's spill list (1/16 of the level's worst case B * 2^D), and beyond that into the
 // table with device atomics.
 constexpr uint32_t kCursorAlign = 256;
+// the head of the workspace (cursors and arrival counters): what a launch, or a caller that promises LNH_BWD_WS_CLEARED, zeroes
+inline uint64_t cursor_head_bytes(uint32_t n_buckets, uint32_t L) {
+    return ((uint64_t)(2 * n_buckets + L) * 4 + kCursorAlign - 1) / kCursorAlign * kCursorAlign;
+}
+// the two sizes the layout takes from the table type, read off the types the kernels store
+struct PoolElem {
+    uint32_t v2_bytes, spill_bytes;
+};
 template <typename T>
-uint64_t plan_buckets(BucketPlan &plan, const GridMeta &m, uint32_t L, uint32_t B, uint32_t D, bool plain,
-                      uint32_t &total_buckets) {
+constexpr PoolElem pool_elem() {
+    return {sizeof(v2_t<T>), sizeof(SpillEntry<T>)};
+}
+inline PoolElem pool_elem(bool fp16) { return fp16 ? pool_elem<half_t>() : pool_elem<float>(); }
+
+uint64_t plan_buckets(BucketPlan &plan, const GridMeta &m, uint32_t L, uint32_t B, uint32_t D, bool plain, PoolElem elem) {
     const uint64_t worst = (uint64_t)B << D;  // worst-case entries of one level (all singles)
     uint64_t bytes = 0;
     uint32_t nbt = 0;
@@ -1787,13 +1799,12 @@ uint64_t plan_buckets(BucketPlan &plan, const GridMeta &m, uint32_t L, uint32_t 
         const uint64_t slots = cap * nb;
         // value stream (2 V2 per slot) | row stream (2 B per slot), each padded so that aligned quad reads stay inside
         plan.pool_off[l] = bytes;
-        const uint64_t vals_bytes = (slots * 2 * sizeof(v2_t<T>) + 64 + 15) / 16 * 16;
+        const uint64_t vals_bytes = (slots * 2 * elem.v2_bytes + 64 + 15) / 16 * 16;
         plan.rows_off[l] = bytes + vals_bytes;
         bytes += vals_bytes + (slots * 2 + 8 + 15) / 16 * 16;
         nbt += nb;
     }
     plan.first_bucket[L] = nbt;
-    total_buckets = nbt;
     // spill list of a level: 1/16 of its worst case (every entry of the level overflowing), at least 1 M entries (or the worst case itself: small batches never reach the atomics); what
     // does not fit there either is added with device atomics by the scatter pass itself (see to_global)
     uint64_t spill_cap = std::max<uint64_t>(worst / 16, 1u << 20);
@@ -1801,7 +1812,7 @@ uint64_t plan_buckets(BucketPlan &plan, const GridMeta &m, uint32_t L, uint32_t 
     plan.spill_cap = spill_cap > 0xffffffffull ? 0xffffffffu : (uint32_t)spill_cap;
     for (uint32_t l = 0; l < L; l++) {
         plan.spill_off[l] = bytes;
-        bytes += ((uint64_t)plan.spill_cap * sizeof(SpillEntry<T>) + 15) / 16 * 16;
+        bytes += ((uint64_t)plan.spill_cap * elem.spill_bytes + 15) / 16 * 16;
     }
     // slice images: a split bucket has n > S entries (S = slice length of its level) and ceil(n / S) < 2 n / S slices, so
     // the split buckets of a level together have fewer than 2 * (entries of the level) / S of them
@@ -1810,8 +1821,7 @@ uint64_t plan_buckets(BucketPlan &plan, const GridMeta &m, uint32_t L, uint32_t 
     plan.partial_slots = (uint32_t)slots;
     plan.partial_off = bytes;
     bytes += slots * kBucketRows * 2 * sizeof(unsigned long long);
-    const uint64_t cursor_bytes = ((uint64_t)(2 * nbt + L) * 4 + kCursorAlign - 1) / kCursorAlign * kCursorAlign;
-    return cursor_bytes + bytes;
+    return cursor_head_bytes(nbt, L) + bytes;
 }
 
 // 128 KiB of dynamic LDS needs an opt-in per kernel and DEVICE (a process may drive several devices)
@@ -1842,12 +1852,6 @@ __host__ inline uint32_t chunk_points(uint32_t B, bool plain = true) {
     return n <= 1 ? B : div_up(div_up(B, n), 1024) * 1024;
 }
 
-template <typename T>
-int launch_backward_bucketed_chunk(const T *grad, const float *inputs, T *ge, uint32_t B, uint32_t L, const GridMeta &m,
-                                   uint32_t align, uint32_t interp, void *workspace, uint64_t workspace_bytes,
-                                   hipStream_t s, uint32_t level_begin, uint32_t level_end, uint32_t b_begin,
-                                   uint32_t B_all, uint32_t B_plan, int phase = 0);
-
 // Shortest chunk the call will use for a batch (256 K points, or the batch itself), and the longest chunk whose plan fits
 // `workspace_bytes` (0: not even the shortest does).
 constexpr uint32_t kMinChunkPoints = 256u << 10;
@@ -1859,85 +1863,25 @@ __host__ inline uint32_t min_chunk_points(uint32_t B, bool plain) {
     while (step > kMinChunkPoints) step = halve_chunk(B, step);
     return step;
 }
-template <typename T>
-uint32_t fit_chunk(uint32_t B, const GridMeta &m, uint32_t L, bool plain, uint64_t workspace_bytes) {
-    BucketPlan plan;
-    uint32_t nbt = 0;
+uint32_t fit_chunk(BucketPlan &plan, uint32_t B, const GridMeta &m, uint32_t L, bool plain, PoolElem elem,
+                   uint64_t workspace_bytes) {
     for (uint32_t step = chunk_points(B, plain);; step = halve_chunk(B, step)) {
-        if (plan_buckets<T>(plan, m, L, step, 3, plain, nbt) <= workspace_bytes) return step;
+        if (plan_buckets(plan, m, L, step, 3, plain, elem) <= workspace_bytes) return step;  // `plan` is that chunk's
         if (step <= kMinChunkPoints) return 0;
     }
 }
 
-// split = 0: the whole backward of the levels [level_begin, level_end).
-// split = 1 ("begin"): every chunk but the last completely (all levels), then the SCATTER pass of the last chunk.
-// split = 2 ("finish"): the REDUCE pass of the last chunk for the levels [level_begin, level_end) — after it the gradient of
-//           those levels is final.  A data-parallel caller runs begin once and finish per level window, handing each window
-//           to the all-reduce while the next is being reduced: the scatter pass stays in one piece (cut into level windows it
-//           loses its level-fastest interleave: 2 windows cost 444 + 453 us against 707 us, profiles/r03_bwd_pipeline.txt).
-template <typename T>
-int launch_backward_bucketed(const T *grad, const float *inputs, T *ge, uint32_t B, uint32_t L, const GridMeta &m,
-                             uint32_t align, uint32_t interp, void *workspace, uint64_t workspace_bytes,
-                             hipStream_t s, uint32_t level_begin = 0, uint32_t level_end = 0xffffffffu, int split = 0,
-                             uint32_t flags = 0) {
-    // flags (lnh_grid_encode_backward_ws_ex): LNH_BWD_WS_CLEARED — the head of the workspace is zero on entry (serves the
-    // FIRST chunk's scatter pass); LNH_BWD_TABLE_ZERO — grad_embeddings is zero on entry (serves the first chunk's reduce pass)
-    if (level_end > L) level_end = L;
-    if (level_begin >= level_end) return LNH_OK;
-    // The workspace serves one chunk at a time, so a SMALLER workspace than lnh_grid_backward_workspace_size() asks for is
-    // not an error: the batch is walked in shorter chunks (fit_chunk halves the chunk until its plan fits; 3.09 GB / 1.60 /
-    // 0.91 GB at 4096 rays x 832 cost 897 / 922 / 992 us, profiles/r04_workspace_chunks.txt).  Below the plan of the
-    // shortest chunk the call fails and names that size.
-    const uint32_t step = fit_chunk<T>(B, m, L, align == 0 && interp == 0, workspace_bytes);
-    if (step == 0) {
-        BucketPlan plan;
-        uint32_t nbt = 0;
-        const uint64_t least = plan_buckets<T>(plan, m, L, min_chunk_points(B, align == 0 && interp == 0), 3,
-                                               align == 0 && interp == 0, nbt);
-        lnh_set_error("grid backward: workspace too small (%llu bytes; this batch needs at least %llu — "
-                      "lnh_grid_backward_workspace_size_min — and runs fastest with lnh_grid_backward_workspace_size)",
-                      (unsigned long long)workspace_bytes, (unsigned long long)least);
-        return LNH_ERR_INVALID_ARG;
-    }
-    for (uint32_t b0 = 0; b0 < B; b0 += step) {
-        const bool last = b0 + step >= B;
-        int phase = 0;
-        uint32_t l0 = level_begin, l1 = level_end;
-        if (split == 1) {
-            l0 = 0;
-            l1 = L;
-            phase = last ? 1 : 0;
-        } else if (split == 2) {
-            if (!last) continue;
-            phase = 2;
-        }
-        const bool first = b0 == 0;
-        const int rc = launch_backward_bucketed_chunk<T>(grad, inputs, ge, std::min(step, B - b0), L, m, align, interp,
-                                                         workspace, workspace_bytes, s, l0, l1, b0, B, step, phase,
-                                                         first && (flags & LNH_BWD_WS_CLEARED),
-                                                         first && (flags & LNH_BWD_TABLE_ZERO));
-        if (rc) return rc;
-    }
-    return LNH_OK;
-}
-
+// One chunk of B points starting at b_begin, in a workspace laid out by `plan` (a full chunk's plan serves the last, shorter one).
 template <typename T>
 int launch_backward_bucketed_chunk(const T *grad, const float *inputs, T *ge, uint32_t B, uint32_t L, const GridMeta &m,
-                                   uint32_t align, uint32_t interp, void *workspace, uint64_t workspace_bytes,
-                                   hipStream_t s, uint32_t level_begin, uint32_t level_end, uint32_t b_begin,
-                                   uint32_t B_all, uint32_t B_plan, int phase, bool cursors_cleared, bool table_zero) {
+                                   uint32_t align, uint32_t interp, void *workspace, const BucketPlan &plan, hipStream_t s,
+                                   uint32_t level_begin, uint32_t level_end, uint32_t b_begin, uint32_t B_all, int phase,
+                                   bool cursors_cleared, bool table_zero) {
     // phase 0: scatter + reduce; 1: (zeroed cursors +) scatter only; 2: reduce only, of a scatter an earlier call has run
     // cursors_cleared: the caller has zeroed the head of the workspace (lnh_grid_backward_workspace_clear_bytes) for this
     // chunk; table_zero: grad_table holds zeros — the reduce pass stores its sums instead of adding them to what it reads
-    BucketPlan plan;
-    uint32_t nbt = 0;
+    const uint32_t nbt = plan.first_bucket[L];
     const bool plain = align == 0 && interp == 0;
-    const uint64_t need = plan_buckets<T>(plan, m, L, B_plan, 3, plain, nbt);  // (a full chunk's plan serves the last, shorter one)
-    if (workspace == nullptr || workspace_bytes < need) {
-        lnh_set_error("grid backward: workspace too small (%llu < %llu bytes)", (unsigned long long)workspace_bytes,
-                      (unsigned long long)need);
-        return LNH_ERR_INVALID_ARG;
-    }
     if (((uint64_t)B << 3) > 0xffffffffull) {
         lnh_set_error("grid backward (bucketed): B = %u is too large for 32-bit pool slots", B);
         return LNH_ERR_UNSUPPORTED;
@@ -1952,7 +1896,7 @@ int launch_backward_bucketed_chunk(const T *grad, const float *inputs, T *ge, ui
             lnh_set_error("grid backward (bucketed): level %u has more than %u buckets", l, kMaxBucketsPerLevel);
             return LNH_ERR_UNSUPPORTED;
         }
-    const uint64_t cursor_bytes = ((uint64_t)(2 * nbt + L) * 4 + kCursorAlign - 1) / kCursorAlign * kCursorAlign;
+    const uint64_t cursor_bytes = cursor_head_bytes(nbt, L);
     uint32_t *cursor = reinterpret_cast<uint32_t *>(workspace);
     uint32_t *spill_cursor = cursor + nbt, *done = spill_cursor + L;
     char *pool = reinterpret_cast<char *>(workspace) + cursor_bytes;
@@ -2009,6 +1953,52 @@ int launch_backward_bucketed_chunk(const T *grad, const float *inputs, T *ge, ui
     LNH_LAUNCH(k, dim3(ord.n_extra + ord.n_buckets), dim3(1024), lds, s, ge, m, plan, pool, cursor, spill_cursor, done, L,
                ord, table_zero ? 1u : 0u);
     return lnh_check_launch("lnh_grid_encode_backward_ws(reduce)");
+}
+
+// split = 0: the whole backward of the levels [level_begin, level_end).
+// split = 1 ("begin"): every chunk but the last completely, then the SCATTER pass of the last chunk (the caller passes all levels).
+// split = 2 ("finish"): the REDUCE pass of the last chunk for the levels [level_begin, level_end) — after it the gradient of
+//           those levels is final.  A data-parallel caller runs begin once and finish per level window, handing each window
+//           to the all-reduce while the next is being reduced: the scatter pass stays in one piece (cut into level windows it
+//           loses its level-fastest interleave: 2 windows cost 444 + 453 us against 707 us, profiles/r03_bwd_pipeline.txt).
+template <typename T>
+int launch_backward_bucketed(const T *grad, const float *inputs, T *ge, uint32_t B, uint32_t L, const GridMeta &m,
+                             uint32_t align, uint32_t interp, void *workspace, uint64_t workspace_bytes,
+                             hipStream_t s, uint32_t level_begin, uint32_t level_end, int split, uint32_t flags) {
+    // flags (lnh_grid_encode_backward_ws_ex): LNH_BWD_WS_CLEARED — the head of the workspace is zero on entry (serves the
+    // FIRST chunk's scatter pass); LNH_BWD_TABLE_ZERO — grad_embeddings is zero on entry (serves the first chunk's reduce pass)
+    if (level_begin >= level_end) return LNH_OK;
+    // The workspace serves one chunk at a time, so a SMALLER workspace than lnh_grid_backward_workspace_size() asks for is
+    // not an error: the batch is walked in shorter chunks (fit_chunk halves the chunk until its plan fits; 3.09 GB / 1.60 /
+    // 0.91 GB at 4096 rays x 832 cost 897 / 922 / 992 us, profiles/r04_workspace_chunks.txt).  Below the plan of the
+    // shortest chunk the call fails and names that size.
+    const bool plain = align == 0 && interp == 0;
+    BucketPlan plan;
+    const uint32_t step = fit_chunk(plan, B, m, L, plain, pool_elem<T>(), workspace_bytes);
+    if (step == 0) {
+        const uint64_t least = plan_buckets(plan, m, L, min_chunk_points(B, plain), 3, plain, pool_elem<T>());
+        lnh_set_error("grid backward: workspace too small (%llu bytes; this batch needs at least %llu — "
+                      "lnh_grid_backward_workspace_size_min — and runs fastest with lnh_grid_backward_workspace_size)",
+                      (unsigned long long)workspace_bytes, (unsigned long long)least);
+        return LNH_ERR_INVALID_ARG;
+    }
+    if (workspace == nullptr) {
+        lnh_set_error("grid backward: workspace too small (%llu < %llu bytes)", (unsigned long long)workspace_bytes,
+                      (unsigned long long)plan_buckets(plan, m, L, step, 3, plain, pool_elem<T>()));
+        return LNH_ERR_INVALID_ARG;
+    }
+    for (uint32_t b0 = 0; b0 < B; b0 += step) {
+        const bool last = b0 + step >= B;
+        if (split == 2 && !last) continue;
+        const int phase = last ? split : 0;
+        const bool first = b0 == 0;
+        const int rc = launch_backward_bucketed_chunk<T>(grad, inputs, ge, std::min(step, B - b0), L, m, align, interp,
+                                                         workspace, plan, s, level_begin, level_end, b0, B, phase,
+                                                         first && (flags & LNH_BWD_WS_CLEARED),
+                                                         first && (flags & LNH_BWD_TABLE_ZERO));
+        if (rc) return rc;
+    }
+    return LNH_OK;
 }
 
 // gridencoder.cu:364-390
@@ -2111,95 +2101,98 @@ k_grad_tv(const T *__restrict__ inputs, const T *__restrict__ table, T *__restri
     }
 }
 
+// Host dispatch on the runtime values the kernels take as template arguments: f receives the value as a
+// std::integral_constant (the element type as a value of that type), and is instantiated for the listed cases only.
+template <int N>
+using Int = std::integral_constant<int, N>;
+template <typename F>
+int with_channels(uint32_t C, F f) {
+    switch (C) {
+        case 1: return f(Int<1>{});
+        case 2: return f(Int<2>{});
+        case 4: return f(Int<4>{});
+        case 8: return f(Int<8>{});
+    }
+    lnh_set_error("GridEncoding: C must be 1, 2, 4, or 8 (got %u)", C);
+    return LNH_ERR_UNSUPPORTED;
+}
+template <typename F>
+int with_dim(uint32_t D, F f) {
+    switch (D) {
+        case 2: return f(Int<2>{});
+        case 3: return f(Int<3>{});
+        case 4: return f(Int<4>{});
+        case 5: return f(Int<5>{});
+    }
+    return LNH_ERR_UNSUPPORTED;
+}
+template <typename F>
+int with_dtype(int dtype, F f) {  // dtype has passed check_common
+    return dtype == LNH_F32 ? f(float{}) : f(half_t{});
+}
+
 template <typename T, int D>
 int launch_forward_c(const float *inputs, const T *emb, T *out, T *dy_dx, uint32_t B, uint32_t C, uint32_t L,
                      const GridMeta &m, uint32_t align, uint32_t interp, hipStream_t s, RowMap map = RowMap{0, 0, 0, 0}) {
     dim3 grid(div_up(B, 256), /* levels */ L), block(256);
-#define LNH_FWD(CC)                                                                                               \
-    if (dy_dx)                                                                                                    \
-        LNH_LAUNCH((k_grid_forward<T, D, CC, true>), grid, block, 0, s, inputs, emb, out, dy_dx, B, L, m, \
-                           align, interp, map);                                                                   \
-    else                                                                                                          \
-        LNH_LAUNCH((k_grid_forward<T, D, CC, false>), grid, block, 0, s, inputs, emb, out, dy_dx, B, L, m, \
-                           align, interp, map);
-    switch (C) {
-        case 1: LNH_FWD(1) break;
-        case 2: LNH_FWD(2) break;
-        case 4: LNH_FWD(4) break;
-        case 8: LNH_FWD(8) break;
-        default: lnh_set_error("GridEncoding: C must be 1, 2, 4, or 8 (got %u)", C); return LNH_ERR_UNSUPPORTED;
-    }
-#undef LNH_FWD
-    return lnh_check_launch("lnh_grid_encode_forward");
+    const int rc = with_channels(C, [&](auto c) {
+        constexpr int CC = decltype(c)::value;
+        if (dy_dx)
+            LNH_LAUNCH((k_grid_forward<T, D, CC, true>), grid, block, 0, s, inputs, emb, out, dy_dx, B, L, m, align, interp, map);
+        else
+            LNH_LAUNCH((k_grid_forward<T, D, CC, false>), grid, block, 0, s, inputs, emb, out, dy_dx, B, L, m, align, interp, map);
+        return LNH_OK;
+    });
+    return rc ? rc : lnh_check_launch("lnh_grid_encode_forward");
 }
-
 
 template <typename T, int D>
 int launch_backward_c(const T *grad, const float *inputs, T *ge, uint32_t B, uint32_t C, uint32_t L,
                       const GridMeta &m, uint32_t align, uint32_t interp, hipStream_t s) {
-    dim3 block(256);
-    switch (C) {
-        case 1:
-            if constexpr (sizeof(T) == 2) {
-                lnh_set_error("grid backward: fp16 tables need an even C (the reference forces fp32 when C is odd, "
-                              "grid.py:54-57)");
-                return LNH_ERR_UNSUPPORTED;
-            } else {
-                LNH_LAUNCH((k_grid_backward<T, D, 1, 1, true>), dim3(div_up(B, 256), L), block, 0, s, grad,
-                                   inputs, ge, B, m, align, interp);
-            }
-            break;
-        case 2:
-            LNH_LAUNCH((k_grid_backward<T, D, 2, 2, true>), dim3(div_up(B, 256), L), block, 0, s, grad, inputs,
-                               ge, B, m, align, interp);
-            break;
-        case 4:
-            LNH_LAUNCH((k_grid_backward<T, D, 4, 2, false>), dim3(div_up((uint64_t)B * 2, 256), L), block, 0, s,
-                               grad, inputs, ge, B, m, align, interp);
-            break;
-        case 8:
-            LNH_LAUNCH((k_grid_backward<T, D, 8, 2, false>), dim3(div_up((uint64_t)B * 4, 256), L), block, 0, s,
-                               grad, inputs, ge, B, m, align, interp);
-            break;
-        default: lnh_set_error("GridEncoding: C must be 1, 2, 4, or 8 (got %u)", C); return LNH_ERR_UNSUPPORTED;
-    }
-    return lnh_check_launch("lnh_grid_encode_backward");
+    const int rc = with_channels(C, [&](auto c) {
+        // a thread owns NC channels of a point (a packed pair where there is one); the run-merge serves C <= 2
+        constexpr int CC = decltype(c)::value, NC = CC == 1 ? 1 : 2;
+        if constexpr (CC == 1 && sizeof(T) == 2) {
+            lnh_set_error("grid backward: fp16 tables need an even C (the reference forces fp32 when C is odd, "
+                          "grid.py:54-57)");
+            return LNH_ERR_UNSUPPORTED;
+        } else {
+            LNH_LAUNCH((k_grid_backward<T, D, CC, NC, (CC <= 2)>), dim3(div_up((uint64_t)B * (CC / NC), 256), L), dim3(256), 0,
+                       s, grad, inputs, ge, B, m, align, interp);
+            return LNH_OK;
+        }
+    });
+    return rc ? rc : lnh_check_launch("lnh_grid_encode_backward");
 }
 
 template <typename T, int D>
 int launch_input_backward_c(const T *grad, const T *dy_dx, T *gi, uint32_t B, uint32_t C, uint32_t L, hipStream_t s) {
-    dim3 grid(div_up((uint64_t)B * D, 256)), block(256);
-    switch (C) {
-        case 1: LNH_LAUNCH((k_grid_input_backward<T, D, 1>), grid, block, 0, s, grad, dy_dx, gi, B, L); break;
-        case 2: LNH_LAUNCH((k_grid_input_backward<T, D, 2>), grid, block, 0, s, grad, dy_dx, gi, B, L); break;
-        case 4: LNH_LAUNCH((k_grid_input_backward<T, D, 4>), grid, block, 0, s, grad, dy_dx, gi, B, L); break;
-        case 8: LNH_LAUNCH((k_grid_input_backward<T, D, 8>), grid, block, 0, s, grad, dy_dx, gi, B, L); break;
-        default: return LNH_ERR_UNSUPPORTED;
-    }
-    return lnh_check_launch("lnh_grid_encode_backward(inputs)");
+    const int rc = with_channels(C, [&](auto c) {
+        LNH_LAUNCH((k_grid_input_backward<T, D, decltype(c)::value>), dim3(div_up((uint64_t)B * D, 256)), dim3(256), 0, s, grad,
+                   dy_dx, gi, B, L);
+        return LNH_OK;
+    });
+    return rc ? rc : lnh_check_launch("lnh_grid_encode_backward(inputs)");
 }
 
 template <typename T, int D>
 int launch_tv_c(const T *inputs, const T *emb, T *grad, float weight, uint32_t B, uint32_t C, uint32_t L,
                 const GridMeta &m, uint32_t align, hipStream_t s) {
-    dim3 grid(div_up(B, 256), L), block(256);
-    switch (C) {
-        case 1:
-            if constexpr (sizeof(T) == 2) {
-                lnh_set_error("grad_total_variation: fp16 needs an even C");
-                return LNH_ERR_UNSUPPORTED;
-            } else {
-                LNH_LAUNCH((k_grad_tv<T, D, 1>), grid, block, 0, s, inputs, emb, grad, weight, B, m, align);
-            }
-            break;
-        case 2: LNH_LAUNCH((k_grad_tv<T, D, 2>), grid, block, 0, s, inputs, emb, grad, weight, B, m, align); break;
-        case 4: LNH_LAUNCH((k_grad_tv<T, D, 4>), grid, block, 0, s, inputs, emb, grad, weight, B, m, align); break;
-        case 8: LNH_LAUNCH((k_grad_tv<T, D, 8>), grid, block, 0, s, inputs, emb, grad, weight, B, m, align); break;
-        default: lnh_set_error("GridEncoding: C must be 1, 2, 4, or 8 (got %u)", C); return LNH_ERR_UNSUPPORTED;
-    }
-    return lnh_check_launch("lnh_grad_total_variation");
+    const int rc = with_channels(C, [&](auto c) {
+        constexpr int CC = decltype(c)::value;
+        if constexpr (CC == 1 && sizeof(T) == 2) {
+            lnh_set_error("grad_total_variation: fp16 needs an even C");
+            return LNH_ERR_UNSUPPORTED;
+        } else {
+            LNH_LAUNCH((k_grad_tv<T, D, CC>), dim3(div_up(B, 256), L), dim3(256), 0, s, inputs, emb, grad, weight, B, m, align);
+            return LNH_OK;
+        }
+    });
+    return rc ? rc : lnh_check_launch("lnh_grad_total_variation");
 }
 
+// The front of every entry point is check_common, the entry point's own argument checks, `B == 0` (nothing to do: LNH_OK
+// whatever the geometry), then resolve_levels — in that order, which is the order callers see errors in.
 int check_common(const void *inputs, const int32_t *offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
                  int dtype) {
     LNH_REQUIRE(inputs && offsets_host, LNH_ERR_INVALID_ARG, "grid: null inputs/offsets");
@@ -2210,17 +2203,43 @@ int check_common(const void *inputs, const int32_t *offsets_host, uint32_t B, ui
     (void)B;
     return LNH_OK;
 }
+int resolve_levels(GridMeta &m, const int32_t *offsets_host, uint32_t D, uint32_t L, float S, uint32_t H, uint32_t gridtype,
+                   int align_corners) {
+    LNH_REQUIRE(build_meta(m, offsets_host, D, L, S, H, gridtype, align_corners != 0) == 0, LNH_ERR_INVALID_ARG,
+                "grid: offsets must be increasing and non-negative, gridtype 0 / 1 / 2 (2: align_corners off)");
+    return LNH_OK;
+}
+
+// The sizing functions' version of that front (they answer 0, not an error): the geometry of a configuration the bucketed
+// backward may serve.
+bool bucketed_levels(GridMeta &m, const int32_t *offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S,
+                     uint32_t H, uint32_t gridtype, int align_corners) {
+    if (!offsets_host || L < 1 || L > LNH_MAX_LEVELS || D != 3 || C != 2 || B == 0) return false;
+    return build_meta(m, offsets_host, D, L, S, H, gridtype, align_corners != 0) == 0;
+}
+// The interpolation mode is not an argument of the sizing functions: they size for the larger of the two pool layouts it
+// can select — each with ITS chunk length (`chunk`: chunk_points or min_chunk_points).
+uint64_t larger_layout_bytes(const GridMeta &m, uint32_t L, uint32_t B, int align_corners, int dtype,
+                             uint32_t (*chunk)(uint32_t, bool)) {
+    BucketPlan plan;
+    uint64_t need = 0;
+    for (int plain = 0; plain <= (align_corners ? 0 : 1); plain++)
+        need = std::max(need, plan_buckets(plan, m, L, chunk(B, plain != 0), 3, plain != 0, pool_elem(dtype == LNH_F16)));
+    return need;
+}
+
+// what the bucketed backward checks before it looks at the level window
+int check_bucketed(const void *grad, const float *inputs, const int32_t *offsets_host, const void *grad_embeddings, uint32_t B,
+                   uint32_t D, uint32_t C, uint32_t L, int dtype) {
+    const int rc = check_common(inputs, offsets_host, B, D, C, L, dtype);
+    if (rc) return rc;
+    LNH_REQUIRE(grad && grad_embeddings, LNH_ERR_INVALID_ARG, "grid backward: null grad/grad_embeddings");
+    LNH_REQUIRE(D == 3 && C == 2, LNH_ERR_UNSUPPORTED,
+                "grid backward (bucketed): only D == 3, C == 2 (use lnh_grid_encode_backward otherwise)");
+    return LNH_OK;
+}
 
 }  // namespace
-
-#define LNH_DISPATCH_D(D, CALL)                                   \
-    switch (D) {                                                  \
-        case 2: { constexpr int DD = 2; rc = CALL; } break;       \
-        case 3: { constexpr int DD = 3; rc = CALL; } break;       \
-        case 4: { constexpr int DD = 4; rc = CALL; } break;       \
-        case 5: { constexpr int DD = 5; rc = CALL; } break;       \
-        default: rc = LNH_ERR_UNSUPPORTED;                        \
-    }
 
 extern "C" {
 
@@ -2232,17 +2251,14 @@ int lnh_grid_encode_forward(const float *inputs, const void *embeddings, const i
     LNH_REQUIRE(embeddings && outputs, LNH_ERR_INVALID_ARG, "grid forward: null embeddings/outputs");
     if (B == 0) return LNH_OK;
     GridMeta m;
-    LNH_REQUIRE(build_meta(m, offsets_host, D, L, S, H, gridtype, align_corners != 0) == 0, LNH_ERR_INVALID_ARG,
-                "grid: offsets must be increasing and non-negative, gridtype 0 / 1 / 2 (2: align_corners off)");
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == LNH_F32) {
-        LNH_DISPATCH_D(D, (launch_forward_c<float, DD>(inputs, (const float *)embeddings, (float *)outputs,
-                                                       (float *)dy_dx, B, C, L, m, align_corners != 0, interp, s)))
-    } else {
-        LNH_DISPATCH_D(D, (launch_forward_c<half_t, DD>(inputs, (const half_t *)embeddings, (half_t *)outputs,
-                                                        (half_t *)dy_dx, B, C, L, m, align_corners != 0, interp, s)))
-    }
-    return rc;
+    if ((rc = resolve_levels(m, offsets_host, D, L, S, H, gridtype, align_corners))) return rc;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return with_dim(D, [&](auto d) {
+            return launch_forward_c<T, decltype(d)::value>(inputs, (const T *)embeddings, (T *)outputs, (T *)dy_dx, B, C, L, m,
+                                                           align_corners != 0, interp, (hipStream_t)stream);
+        });
+    });
 }
 
 int lnh_grid_encode_forward_mapped_ex(const float *inputs_all, const void *embeddings, const int32_t *offsets_host,
@@ -2255,18 +2271,16 @@ int lnh_grid_encode_forward_mapped_ex(const float *inputs_all, const void *embed
     LNH_REQUIRE(T_cur >= 1 && slot_off + T_cur <= T_tot && B % T_cur == 0 && (uint64_t)(B / T_cur) * T_tot <= B_all,
                 LNH_ERR_INVALID_ARG, "grid forward (mapped): inconsistent row map");
     if (B == 0) return LNH_OK;
-    GridMeta m;
     LNH_REQUIRE(gridtype == kGridHash || gridtype == kGridTcnn, LNH_ERR_INVALID_ARG,
                 "grid forward (mapped): gridtype must be 0 (hash) or 2 (tiny-cuda-nn lattice), got %u", gridtype);
-    LNH_REQUIRE(build_meta(m, offsets_host, 3, L, S, H, gridtype, false) == 0, LNH_ERR_INVALID_ARG,
-                "grid: offsets must be increasing and non-negative, gridtype 0 / 1 / 2 (2: align_corners off)");
+    GridMeta m;
+    if ((rc = resolve_levels(m, offsets_host, 3, L, S, H, gridtype, 0))) return rc;
     const RowMap map{T_cur, T_tot, slot_off, B_all};
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == LNH_F32)
-        return launch_forward_c<float, 3>(inputs_all, (const float *)embeddings, (float *)outputs_all, nullptr, B, C, L, m,
-                                          0, 0, s, map);
-    return launch_forward_c<half_t, 3>(inputs_all, (const half_t *)embeddings, (half_t *)outputs_all, nullptr, B, C, L, m, 0,
-                                       0, s, map);
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_forward_c<T, 3>(inputs_all, (const T *)embeddings, (T *)outputs_all, nullptr, B, C, L, m, 0, 0,
+                                      (hipStream_t)stream, map);
+    });
 }
 
 int lnh_grid_encode_forward_mapped(const float *inputs_all, const void *embeddings, const int32_t *offsets_host,
@@ -2289,61 +2303,37 @@ int lnh_grid_encode_backward(const void *grad, const float *inputs, const void *
                 "grid backward: dy_dx and grad_inputs must be given together");
     if (B == 0) return LNH_OK;
     GridMeta m;
-    LNH_REQUIRE(build_meta(m, offsets_host, D, L, S, H, gridtype, align_corners != 0) == 0, LNH_ERR_INVALID_ARG,
-                "grid: offsets must be increasing and non-negative, gridtype 0 / 1 / 2 (2: align_corners off)");
+    if ((rc = resolve_levels(m, offsets_host, D, L, S, H, gridtype, align_corners))) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == LNH_F32) {
-        LNH_DISPATCH_D(D, (launch_backward_c<float, DD>((const float *)grad, inputs, (float *)grad_embeddings, B, C, L,
-                                                        m, align_corners != 0, interp, s)))
-        if (rc == LNH_OK && dy_dx)
-            LNH_DISPATCH_D(D, (launch_input_backward_c<float, DD>((const float *)grad, (const float *)dy_dx,
-                                                                  (float *)grad_inputs, B, C, L, s)))
-    } else {
-        LNH_DISPATCH_D(D, (launch_backward_c<half_t, DD>((const half_t *)grad, inputs, (half_t *)grad_embeddings, B, C,
-                                                         L, m, align_corners != 0, interp, s)))
-        if (rc == LNH_OK && dy_dx)
-            LNH_DISPATCH_D(D, (launch_input_backward_c<half_t, DD>((const half_t *)grad, (const half_t *)dy_dx,
-                                                                   (half_t *)grad_inputs, B, C, L, s)))
-    }
-    return rc;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        const int rc = with_dim(D, [&](auto d) {
+            return launch_backward_c<T, decltype(d)::value>((const T *)grad, inputs, (T *)grad_embeddings, B, C, L, m,
+                                                            align_corners != 0, interp, s);
+        });
+        if (rc != LNH_OK || !dy_dx) return rc;
+        return with_dim(D, [&](auto d) {
+            return launch_input_backward_c<T, decltype(d)::value>((const T *)grad, (const T *)dy_dx, (T *)grad_inputs, B, C, L, s);
+        });
+    });
 }
 
 uint64_t lnh_grid_backward_workspace_size(const int32_t *offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
                                           float S, uint32_t H, uint32_t gridtype, int align_corners, int dtype) {
-    if (!offsets_host || L < 1 || L > LNH_MAX_LEVELS || D != 3 || C != 2 || B == 0) return 0;
     GridMeta m;
-    if (build_meta(m, offsets_host, D, L, S, H, gridtype, align_corners != 0) != 0) return 0;
-    BucketPlan plan;
-    uint32_t nbt = 0;
+    if (!bucketed_levels(m, offsets_host, B, D, C, L, S, H, gridtype, align_corners)) return 0;
     for (uint32_t l = 0; l < L; l++)
         if ((m.lv[l].hashmap_size + kBucketRows - 1) / kBucketRows > kMaxBucketsPerLevel) return 0;
-    // the workspace serves one chunk at a time.  (The interpolation mode is not an argument here: size for the larger of the
-    // two pool layouts it can select — each with ITS chunk length, see chunk_points.)
-    uint64_t need = 0;
-    for (int plain = 0; plain <= (align_corners ? 0 : 1); plain++) {
-        const uint32_t Bc = chunk_points(B, plain != 0);
-        const uint64_t n = dtype == LNH_F16 ? plan_buckets<half_t>(plan, m, L, Bc, D, plain != 0, nbt)
-                                            : plan_buckets<float>(plan, m, L, Bc, D, plain != 0, nbt);
-        need = n > need ? n : need;
-    }
-    return need;
+    return larger_layout_bytes(m, L, B, align_corners, dtype, chunk_points);  // the workspace serves one chunk at a time
 }
 
 uint64_t lnh_grid_backward_workspace_size_min(const int32_t *offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
                                               float S, uint32_t H, uint32_t gridtype, int align_corners, int dtype) {
-    if (lnh_grid_backward_workspace_size(offsets_host, B, D, C, L, S, H, gridtype, align_corners, dtype) == 0) return 0;
     GridMeta m;
-    (void)build_meta(m, offsets_host, D, L, S, H, gridtype, align_corners != 0);
-    BucketPlan plan;
-    uint32_t nbt = 0;
-    uint64_t need = 0;
-    for (int plain = 0; plain <= (align_corners ? 0 : 1); plain++) {
-        const uint32_t Bc = min_chunk_points(B, plain != 0);
-        const uint64_t n = dtype == LNH_F16 ? plan_buckets<half_t>(plan, m, L, Bc, D, plain != 0, nbt)
-                                            : plan_buckets<float>(plan, m, L, Bc, D, plain != 0, nbt);
-        need = n > need ? n : need;
-    }
-    return need;
+    if (lnh_grid_backward_workspace_size(offsets_host, B, D, C, L, S, H, gridtype, align_corners, dtype) == 0 ||
+        !bucketed_levels(m, offsets_host, B, D, C, L, S, H, gridtype, align_corners))
+        return 0;
+    return larger_layout_bytes(m, L, B, align_corners, dtype, min_chunk_points);
 }
 
 void lnh_grid_backward_set_slice_entries(uint32_t entries) {
@@ -2354,14 +2344,13 @@ int lnh_grid_backward_plan_info(const int32_t *offsets_host, uint32_t B, uint32_
                                 uint32_t H, uint32_t gridtype, int align_corners, int dtype, uint32_t level,
                                 uint32_t *out4) {
     LNH_REQUIRE(out4 && offsets_host, LNH_ERR_INVALID_ARG, "grid backward plan: null argument");
-    LNH_REQUIRE(lnh_grid_backward_workspace_size(offsets_host, B, D, C, L, S, H, gridtype, align_corners, dtype) != 0 &&
-                    level < L, LNH_ERR_UNSUPPORTED, "grid backward plan: configuration not served by the bucketed path");
     GridMeta m;
-    (void)build_meta(m, offsets_host, D, L, S, H, gridtype, align_corners != 0);
+    LNH_REQUIRE(lnh_grid_backward_workspace_size(offsets_host, B, D, C, L, S, H, gridtype, align_corners, dtype) != 0 &&
+                    level < L && bucketed_levels(m, offsets_host, B, D, C, L, S, H, gridtype, align_corners),
+                LNH_ERR_UNSUPPORTED, "grid backward plan: configuration not served by the bucketed path");
+    // (the layout of linear interpolation alone, unlike workspace_size: the plan the usual call runs with)
     BucketPlan plan;
-    uint32_t nbt = 0;
-    if (dtype == LNH_F16) (void)plan_buckets<half_t>(plan, m, L, chunk_points(B, align_corners == 0), D, align_corners == 0, nbt);
-    else (void)plan_buckets<float>(plan, m, L, chunk_points(B, align_corners == 0), D, align_corners == 0, nbt);
+    (void)plan_buckets(plan, m, L, chunk_points(B, align_corners == 0), D, align_corners == 0, pool_elem(dtype == LNH_F16));
     out4[0] = plan.first_bucket[level + 1] - plan.first_bucket[level];
     out4[1] = plan.cap[level];
     out4[2] = kBucketRows;
@@ -2369,137 +2358,59 @@ int lnh_grid_backward_plan_info(const int32_t *offsets_host, uint32_t B, uint32_
     return LNH_OK;
 }
 
-int lnh_grid_encode_backward_ws(const void *grad, const float *inputs, const int32_t *offsets_host,
-                                void *grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S,
-                                uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp, int dtype,
-                                void *workspace, uint64_t workspace_bytes, lnh_stream_t stream) {
-    int rc = check_common(inputs, offsets_host, B, D, C, L, dtype);
-    if (rc) return rc;
-    LNH_REQUIRE(grad && grad_embeddings, LNH_ERR_INVALID_ARG, "grid backward: null grad/grad_embeddings");
-    LNH_REQUIRE(D == 3 && C == 2, LNH_ERR_UNSUPPORTED,
-                "grid backward (bucketed): only D == 3, C == 2 (use lnh_grid_encode_backward otherwise)");
-    if (B == 0) return LNH_OK;
-    GridMeta m;
-    LNH_REQUIRE(build_meta(m, offsets_host, D, L, S, H, gridtype, align_corners != 0) == 0, LNH_ERR_INVALID_ARG,
-                "grid: offsets must be increasing and non-negative, gridtype 0 / 1 / 2 (2: align_corners off)");
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == LNH_F32)
-        return launch_backward_bucketed<float>((const float *)grad, inputs, (float *)grad_embeddings, B, L, m,
-                                               align_corners != 0, interp, workspace, workspace_bytes, s);
-    return launch_backward_bucketed<half_t>((const half_t *)grad, inputs, (half_t *)grad_embeddings, B, L, m,
-                                            align_corners != 0, interp, workspace, workspace_bytes, s);
-}
-
-int lnh_grid_encode_backward_ws_levels(const void *grad, const float *inputs, const int32_t *offsets_host,
-                                       void *grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S,
-                                       uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp, int dtype,
-                                       void *workspace, uint64_t workspace_bytes, uint32_t level_begin,
-                                       uint32_t level_end, lnh_stream_t stream) {
-    int rc = check_common(inputs, offsets_host, B, D, C, L, dtype);
-    if (rc) return rc;
-    LNH_REQUIRE(grad && grad_embeddings, LNH_ERR_INVALID_ARG, "grid backward: null grad/grad_embeddings");
-    LNH_REQUIRE(D == 3 && C == 2, LNH_ERR_UNSUPPORTED,
-                "grid backward (bucketed): only D == 3, C == 2 (use lnh_grid_encode_backward otherwise)");
-    LNH_REQUIRE(level_begin <= level_end && level_end <= L, LNH_ERR_INVALID_ARG,
-                "grid backward: need level_begin <= level_end <= L");
-    if (B == 0) return LNH_OK;
-    GridMeta m;
-    LNH_REQUIRE(build_meta(m, offsets_host, D, L, S, H, gridtype, align_corners != 0) == 0, LNH_ERR_INVALID_ARG,
-                "grid: offsets must be increasing and non-negative, gridtype 0 / 1 / 2 (2: align_corners off)");
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == LNH_F32)
-        return launch_backward_bucketed<float>((const float *)grad, inputs, (float *)grad_embeddings, B, L, m,
-                                               align_corners != 0, interp, workspace, workspace_bytes, s, level_begin,
-                                               level_end);
-    return launch_backward_bucketed<half_t>((const half_t *)grad, inputs, (half_t *)grad_embeddings, B, L, m,
-                                            align_corners != 0, interp, workspace, workspace_bytes, s, level_begin,
-                                            level_end);
-}
-
-static int backward_ws_split(const void *grad, const float *inputs, const int32_t *offsets_host, void *grad_embeddings,
-                             uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, uint32_t gridtype,
-                             int align_corners, uint32_t interp, int dtype, void *workspace, uint64_t workspace_bytes,
-                             uint32_t level_begin, uint32_t level_end, int split, lnh_stream_t stream) {
-    int rc = check_common(inputs, offsets_host, B, D, C, L, dtype);
-    if (rc) return rc;
-    LNH_REQUIRE(grad && grad_embeddings, LNH_ERR_INVALID_ARG, "grid backward: null grad/grad_embeddings");
-    LNH_REQUIRE(D == 3 && C == 2, LNH_ERR_UNSUPPORTED,
-                "grid backward (bucketed): only D == 3, C == 2 (use lnh_grid_encode_backward otherwise)");
-    LNH_REQUIRE(level_begin <= level_end && level_end <= L, LNH_ERR_INVALID_ARG,
-                "grid backward: need level_begin <= level_end <= L");
-    if (B == 0) return LNH_OK;
-    GridMeta m;
-    LNH_REQUIRE(build_meta(m, offsets_host, D, L, S, H, gridtype, align_corners != 0) == 0, LNH_ERR_INVALID_ARG,
-                "grid: offsets must be increasing and non-negative, gridtype 0 / 1 / 2 (2: align_corners off)");
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == LNH_F32)
-        return launch_backward_bucketed<float>((const float *)grad, inputs, (float *)grad_embeddings, B, L, m,
-                                               align_corners != 0, interp, workspace, workspace_bytes, s, level_begin,
-                                               level_end, split);
-    return launch_backward_bucketed<half_t>((const half_t *)grad, inputs, (half_t *)grad_embeddings, B, L, m,
-                                            align_corners != 0, interp, workspace, workspace_bytes, s, level_begin,
-                                            level_end, split);
-}
-
+// The bucketed backward's one implementation; the four entry points below are forwards to it.
 int lnh_grid_encode_backward_ws_ex(const void *grad, const float *inputs, const int32_t *offsets_host, void *grad_embeddings,
                                    uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, uint32_t gridtype,
                                    int align_corners, uint32_t interp, int dtype, void *workspace, uint64_t workspace_bytes,
                                    uint32_t level_begin, uint32_t level_end, int split, uint32_t flags, lnh_stream_t stream) {
     LNH_REQUIRE(split >= 0 && split <= 2 && (flags & ~(uint32_t)(LNH_BWD_WS_CLEARED | LNH_BWD_TABLE_ZERO)) == 0,
                 LNH_ERR_INVALID_ARG, "grid backward: split must be 0 (whole) / 1 (begin) / 2 (finish), flags LNH_BWD_*");
-    int rc = check_common(inputs, offsets_host, B, D, C, L, dtype);
+    int rc = check_bucketed(grad, inputs, offsets_host, grad_embeddings, B, D, C, L, dtype);
     if (rc) return rc;
-    LNH_REQUIRE(grad && grad_embeddings, LNH_ERR_INVALID_ARG, "grid backward: null grad/grad_embeddings");
-    LNH_REQUIRE(D == 3 && C == 2, LNH_ERR_UNSUPPORTED,
-                "grid backward (bucketed): only D == 3, C == 2 (use lnh_grid_encode_backward otherwise)");
     if (level_end > L) level_end = L;
     LNH_REQUIRE(level_begin <= level_end, LNH_ERR_INVALID_ARG, "grid backward: need level_begin <= level_end <= L");
     if (B == 0) return LNH_OK;
     GridMeta m;
-    LNH_REQUIRE(build_meta(m, offsets_host, D, L, S, H, gridtype, align_corners != 0) == 0, LNH_ERR_INVALID_ARG,
-                "grid: offsets must be increasing and non-negative, gridtype 0 / 1 / 2 (2: align_corners off)");
-    hipStream_t s = (hipStream_t)stream;
+    if ((rc = resolve_levels(m, offsets_host, D, L, S, H, gridtype, align_corners))) return rc;
     if (split == 1) {  // begin: everything but the last reduce pass, over all levels
         level_begin = 0;
         level_end = L;
     }
-    if (dtype == LNH_F32)
-        return launch_backward_bucketed<float>((const float *)grad, inputs, (float *)grad_embeddings, B, L, m,
-                                               align_corners != 0, interp, workspace, workspace_bytes, s, level_begin,
-                                               level_end, split, flags);
-    return launch_backward_bucketed<half_t>((const half_t *)grad, inputs, (half_t *)grad_embeddings, B, L, m,
-                                            align_corners != 0, interp, workspace, workspace_bytes, s, level_begin,
-                                            level_end, split, flags);
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_backward_bucketed<T>((const T *)grad, inputs, (T *)grad_embeddings, B, L, m, align_corners != 0, interp,
+                                           workspace, workspace_bytes, (hipStream_t)stream, level_begin, level_end, split, flags);
+    });
 }
 
-uint64_t lnh_grid_backward_workspace_clear_bytes(const int32_t *offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
-                                                 float S, uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp,
-                                                 int dtype, uint64_t workspace_bytes) {
-    if (!offsets_host || D != 3 || C != 2 || L == 0 || L > LNH_MAX_LEVELS || B == 0) return 0;
-    GridMeta m;
-    if (build_meta(m, offsets_host, D, L, S, H, gridtype, align_corners != 0) != 0) return 0;
-    const bool plain = align_corners == 0 && interp == 0;
-    BucketPlan plan;
-    uint32_t nbt = 0;
-    uint32_t step;
-    if (dtype == LNH_F32) {
-        step = fit_chunk<float>(B, m, L, plain, workspace_bytes);
-        if (step == 0) return 0;
-        (void)plan_buckets<float>(plan, m, L, step, 3, plain, nbt);
-    } else {
-        step = fit_chunk<half_t>(B, m, L, plain, workspace_bytes);
-        if (step == 0) return 0;
-        (void)plan_buckets<half_t>(plan, m, L, step, 3, plain, nbt);
-    }
-    return ((uint64_t)(2 * nbt + L) * 4 + kCursorAlign - 1) / kCursorAlign * kCursorAlign;
+int lnh_grid_encode_backward_ws(const void *grad, const float *inputs, const int32_t *offsets_host,
+                                void *grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S,
+                                uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp, int dtype,
+                                void *workspace, uint64_t workspace_bytes, lnh_stream_t stream) {
+    return lnh_grid_encode_backward_ws_ex(grad, inputs, offsets_host, grad_embeddings, B, D, C, L, S, H, gridtype, align_corners,
+                                          interp, dtype, workspace, workspace_bytes, 0, L, 0, 0, stream);
 }
 
 int lnh_grid_encode_backward_ws_begin(const void *grad, const float *inputs, const int32_t *offsets_host,
                                       void *grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S,
                                       uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp, int dtype,
                                       void *workspace, uint64_t workspace_bytes, lnh_stream_t stream) {
-    return backward_ws_split(grad, inputs, offsets_host, grad_embeddings, B, D, C, L, S, H, gridtype, align_corners, interp,
-                             dtype, workspace, workspace_bytes, 0, L, 1, stream);
+    return lnh_grid_encode_backward_ws_ex(grad, inputs, offsets_host, grad_embeddings, B, D, C, L, S, H, gridtype, align_corners,
+                                          interp, dtype, workspace, workspace_bytes, 0, L, 1, 0, stream);
+}
+
+// _ws_levels and _ws_finish REFUSE a window that ends beyond L, where _ws_ex clamps it: they make that one check themselves,
+// after the checks that precede the window's in _ws_ex, so that a call wrong in two ways still reports the same error first.
+int lnh_grid_encode_backward_ws_levels(const void *grad, const float *inputs, const int32_t *offsets_host,
+                                       void *grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S,
+                                       uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp, int dtype,
+                                       void *workspace, uint64_t workspace_bytes, uint32_t level_begin,
+                                       uint32_t level_end, lnh_stream_t stream) {
+    const int rc = check_bucketed(grad, inputs, offsets_host, grad_embeddings, B, D, C, L, dtype);
+    if (rc) return rc;
+    LNH_REQUIRE(level_end <= L, LNH_ERR_INVALID_ARG, "grid backward: need level_begin <= level_end <= L");
+    return lnh_grid_encode_backward_ws_ex(grad, inputs, offsets_host, grad_embeddings, B, D, C, L, S, H, gridtype, align_corners,
+                                          interp, dtype, workspace, workspace_bytes, level_begin, level_end, 0, 0, stream);
 }
 
 int lnh_grid_encode_backward_ws_finish(const void *grad, const float *inputs, const int32_t *offsets_host,
@@ -2507,8 +2418,22 @@ int lnh_grid_encode_backward_ws_finish(const void *grad, const float *inputs, co
                                        uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp, int dtype,
                                        void *workspace, uint64_t workspace_bytes, uint32_t level_begin, uint32_t level_end,
                                        lnh_stream_t stream) {
-    return backward_ws_split(grad, inputs, offsets_host, grad_embeddings, B, D, C, L, S, H, gridtype, align_corners, interp,
-                             dtype, workspace, workspace_bytes, level_begin, level_end, 2, stream);
+    const int rc = check_bucketed(grad, inputs, offsets_host, grad_embeddings, B, D, C, L, dtype);
+    if (rc) return rc;
+    LNH_REQUIRE(level_end <= L, LNH_ERR_INVALID_ARG, "grid backward: need level_begin <= level_end <= L");
+    return lnh_grid_encode_backward_ws_ex(grad, inputs, offsets_host, grad_embeddings, B, D, C, L, S, H, gridtype, align_corners,
+                                          interp, dtype, workspace, workspace_bytes, level_begin, level_end, 2, 0, stream);
+}
+
+uint64_t lnh_grid_backward_workspace_clear_bytes(const int32_t *offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
+                                                 float S, uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp,
+                                                 int dtype, uint64_t workspace_bytes) {
+    GridMeta m;
+    if (!bucketed_levels(m, offsets_host, B, D, C, L, S, H, gridtype, align_corners)) return 0;
+    // (the layout and chunk the call will run with, for any workspace it accepts; any dtype but LNH_F32 sizes as fp16)
+    BucketPlan plan;
+    if (fit_chunk(plan, B, m, L, align_corners == 0 && interp == 0, pool_elem(dtype != LNH_F32), workspace_bytes) == 0) return 0;
+    return cursor_head_bytes(plan.first_bucket[L], L);
 }
 
 int lnh_grad_total_variation(const void *inputs, const void *embeddings, void *grad, const int32_t *offsets_host,
@@ -2519,17 +2444,14 @@ int lnh_grad_total_variation(const void *inputs, const void *embeddings, void *g
     LNH_REQUIRE(embeddings && grad, LNH_ERR_INVALID_ARG, "grad_total_variation: null embeddings/grad");
     if (B == 0) return LNH_OK;
     GridMeta m;
-    LNH_REQUIRE(build_meta(m, offsets_host, D, L, S, H, gridtype, align_corners != 0) == 0, LNH_ERR_INVALID_ARG,
-                "grid: offsets must be increasing and non-negative, gridtype 0 / 1 / 2 (2: align_corners off)");
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == LNH_F32) {
-        LNH_DISPATCH_D(D, (launch_tv_c<float, DD>((const float *)inputs, (const float *)embeddings, (float *)grad,
-                                                  weight, B, C, L, m, align_corners != 0, s)))
-    } else {
-        LNH_DISPATCH_D(D, (launch_tv_c<half_t, DD>((const half_t *)inputs, (const half_t *)embeddings, (half_t *)grad,
-                                                   weight, B, C, L, m, align_corners != 0, s)))
-    }
-    return rc;
+    if ((rc = resolve_levels(m, offsets_host, D, L, S, H, gridtype, align_corners))) return rc;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return with_dim(D, [&](auto d) {
+            return launch_tv_c<T, decltype(d)::value>((const T *)inputs, (const T *)embeddings, (T *)grad, weight, B, C, L, m,
+                                                      align_corners != 0, (hipStream_t)stream);
+        });
+    });
 }
 
 int lnh_grid_corner_indices(const float *inputs, const int32_t *offsets_host, uint32_t *out_idx, uint32_t B,
@@ -2540,17 +2462,13 @@ int lnh_grid_corner_indices(const float *inputs, const int32_t *offsets_host, ui
     LNH_REQUIRE(out_idx, LNH_ERR_INVALID_ARG, "grid indices: null output");
     if (B == 0) return LNH_OK;
     GridMeta m;
-    LNH_REQUIRE(build_meta(m, offsets_host, D, L, S, H, gridtype, align_corners != 0) == 0, LNH_ERR_INVALID_ARG,
-                "grid: offsets must be increasing and non-negative, gridtype 0 / 1 / 2 (2: align_corners off)");
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid(div_up(B, 256), L), block(256);
-    switch (D) {
-        case 2: LNH_LAUNCH((k_grid_indices<2>), grid, block, 0, s, inputs, out_idx, B, C, m, (uint32_t)(align_corners != 0)); break;
-        case 3: LNH_LAUNCH((k_grid_indices<3>), grid, block, 0, s, inputs, out_idx, B, C, m, (uint32_t)(align_corners != 0)); break;
-        case 4: LNH_LAUNCH((k_grid_indices<4>), grid, block, 0, s, inputs, out_idx, B, C, m, (uint32_t)(align_corners != 0)); break;
-        case 5: LNH_LAUNCH((k_grid_indices<5>), grid, block, 0, s, inputs, out_idx, B, C, m, (uint32_t)(align_corners != 0)); break;
-    }
-    return lnh_check_launch("lnh_grid_corner_indices");
+    if ((rc = resolve_levels(m, offsets_host, D, L, S, H, gridtype, align_corners))) return rc;
+    rc = with_dim(D, [&](auto d) {
+        LNH_LAUNCH((k_grid_indices<decltype(d)::value>), dim3(div_up(B, 256), L), dim3(256), 0, (hipStream_t)stream, inputs,
+                   out_idx, B, C, m, (uint32_t)(align_corners != 0));
+        return LNH_OK;
+    });
+    return rc ? rc : lnh_check_launch("lnh_grid_corner_indices");
 }
 
 }  // extern "C"

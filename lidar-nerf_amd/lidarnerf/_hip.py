@@ -13,19 +13,18 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.environ.get("LNH_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "lib", "liblidarnerf_hip.so")
 
 P, U32, I32, F32 = C.c_void_p, C.c_uint32, C.c_int, C.c_float
+# the bucketed grid backward's arguments up to the workspace, shared by its five entry points
+_GRID_BWD_WS = [P, P, P, P, U32, U32, U32, U32, F32, U32, U32, I32, U32, I32, P, C.c_uint64]
 
 # name -> argument ctypes (stream is appended automatically)
 _SIGS = {
     "lnh_grid_encode_forward": [P, P, P, P, U32, U32, U32, U32, F32, U32, P, U32, I32, U32, I32],
     "lnh_grid_encode_backward": [P, P, P, P, P, U32, U32, U32, U32, F32, U32, P, P, U32, I32, U32, I32],
-    "lnh_grid_encode_backward_ws": [P, P, P, P, U32, U32, U32, U32, F32, U32, U32, I32, U32, I32, P, C.c_uint64],
-    "lnh_grid_encode_backward_ws_levels": [P, P, P, P, U32, U32, U32, U32, F32, U32, U32, I32, U32, I32, P, C.c_uint64,
-                                           U32, U32],
-    "lnh_grid_encode_backward_ws_begin": [P, P, P, P, U32, U32, U32, U32, F32, U32, U32, I32, U32, I32, P, C.c_uint64],
-    "lnh_grid_encode_backward_ws_finish": [P, P, P, P, U32, U32, U32, U32, F32, U32, U32, I32, U32, I32, P, C.c_uint64,
-                                           U32, U32],
-    "lnh_grid_encode_backward_ws_ex": [P, P, P, P, U32, U32, U32, U32, F32, U32, U32, I32, U32, I32, P, C.c_uint64, U32, U32,
-                                       I32, U32],
+    "lnh_grid_encode_backward_ws": _GRID_BWD_WS,
+    "lnh_grid_encode_backward_ws_levels": _GRID_BWD_WS + [U32, U32],
+    "lnh_grid_encode_backward_ws_begin": _GRID_BWD_WS,
+    "lnh_grid_encode_backward_ws_finish": _GRID_BWD_WS + [U32, U32],
+    "lnh_grid_encode_backward_ws_ex": _GRID_BWD_WS + [U32, U32, I32, U32],
     "lnh_grad_total_variation": [P, P, P, P, F32, U32, U32, U32, U32, F32, U32, U32, I32, I32],
     "lnh_grid_corner_indices": [P, P, P, U32, U32, U32, U32, F32, U32, U32, I32],
     "lnh_freq_encode_forward": [P, U32, U32, U32, U32, P],
@@ -132,10 +131,8 @@ def lib():
             fn = getattr(L, name)
             fn.argtypes = sig + [P]
             fn.restype = C.c_int
-        L.lnh_grid_backward_workspace_size.argtypes = [P, U32, U32, U32, U32, F32, U32, U32, I32, I32]
-        L.lnh_grid_backward_workspace_size.restype = C.c_uint64
-        L.lnh_grid_backward_workspace_size_min.argtypes = [P, U32, U32, U32, U32, F32, U32, U32, I32, I32]
-        L.lnh_grid_backward_workspace_size_min.restype = C.c_uint64
+        for fn in (L.lnh_grid_backward_workspace_size, L.lnh_grid_backward_workspace_size_min):
+            fn.argtypes, fn.restype = [P, U32, U32, U32, U32, F32, U32, U32, I32, I32], C.c_uint64
         L.lnh_grid_backward_workspace_clear_bytes.argtypes = [P, U32, U32, U32, U32, F32, U32, U32, I32, U32, I32, C.c_uint64]
         L.lnh_grid_backward_workspace_clear_bytes.restype = C.c_uint64
         L.lnh_grid_backward_plan_info.argtypes = [P, U32, U32, U32, U32, F32, U32, U32, I32, I32, U32, P]

@@ -89,6 +89,17 @@ def _workspace(device, nbytes):
     return ws
 
 
+def grid_backward_bucketed(grad_lbc, inputs, offsets_host, grad_table, S, H, gridtype, align_corners, interp, ws,
+                           window=None, split=0, flags=0, timer="lnh_grid_encode_backward_ws", tag=None):
+    """Table gradient of grad [L,B,2] at inputs [B,3], added into grad_table (scratch: ws) by lnh_grid_encode_backward_ws_ex,
+    which documents window = (level_begin, level_end) (default: all levels), split and flags; `timer`: the name it is timed as."""
+    L, B = grad_lbc.shape[:2]
+    _hip.call("lnh_grid_encode_backward_ws_ex", grad_lbc.data_ptr(), inputs.data_ptr(), offsets_host.data_ptr(),
+              grad_table.data_ptr(), B, 3, 2, L, float(S), int(H), gridtype, int(align_corners), interp,
+              _hip.dtype_code(grad_lbc.dtype), ws.data_ptr(), ws.numel(), *(window or (0, L)), split, int(flags), tag=tag,
+              timer=timer)
+
+
 def grid_backward_raw(grad_lbc, inputs, rows, offsets_host, S, H, gridtype, align_corners, interp, dy_dx):
     """grad [L,B,C] -> (grad_embeddings [rows,C] in grad's dtype, grad_inputs [B,D] or None)."""
     L, B, C = grad_lbc.shape
@@ -97,14 +108,11 @@ def grid_backward_raw(grad_lbc, inputs, rows, offsets_host, S, H, gridtype, alig
     ge = torch.zeros((rows, C), device=grad_lbc.device, dtype=grad_lbc.dtype)
     if dy_dx is None and D == 3 and C == 2:
         # hot configuration: bucketed scatter-reduce, no atomic adds to HBM (lnh_grid_encode_backward_ws)
-        code = _hip.dtype_code(grad_lbc.dtype)
-        need = _hip.lib().lnh_grid_backward_workspace_size(offsets_host.data_ptr(), B, D, C, L, float(S), int(H),
-                                                           gridtype, int(align_corners), code)
+        need = _hip.lib().lnh_grid_backward_workspace_size(offsets_host.data_ptr(), B, D, C, L, float(S), int(H), gridtype,
+                                                           int(align_corners), _hip.dtype_code(grad_lbc.dtype))
         if need > 0:
             ws = _workspace(grad_lbc.device, need)
-            _hip.call("lnh_grid_encode_backward_ws", grad_lbc.data_ptr(), inputs.data_ptr(), offsets_host.data_ptr(),
-                      ge.data_ptr(), B, D, C, L, float(S), int(H), gridtype, int(align_corners), interp, code,
-                      ws.data_ptr(), ws.numel(), tag=B)
+            grid_backward_bucketed(grad_lbc, inputs, offsets_host, ge, S, H, gridtype, align_corners, interp, ws, tag=B)
             return ge, None
     gi = torch.zeros((B, D), device=grad_lbc.device, dtype=grad_lbc.dtype) if dy_dx is not None else None
     _hip.call("lnh_grid_encode_backward", grad_lbc.data_ptr(), inputs.data_ptr(), None, offsets_host.data_ptr(),

@@ -26,7 +26,7 @@ import torch
 from torch.autograd import Function
 
 from .. import _hip, parallel
-from ..gridencoder.grid import _workspace
+from ..gridencoder.grid import _workspace, grid_backward_bucketed
 
 
 class FieldSpec:
@@ -115,14 +115,10 @@ def _grid_bwd_workspace(dev, enc, B):
 def _grid_bwd(g_feat, x01, g_table16, enc, B, ws=None, flags=0):
     """Table gradient of B points.  ws / flags: the caller has cleared the head of the workspace and / or the gradient table
     itself (lnh_grid_encode_backward_ws_ex: LNH_BWD_WS_CLEARED, LNH_BWD_TABLE_ZERO)."""
-    L = enc.num_levels
-    off = enc._offsets_host
     if ws is None:
         ws, _ = _grid_bwd_workspace(g_feat.device, enc, B)
-    _hip.call("lnh_grid_encode_backward_ws_ex", g_feat.data_ptr(), x01.data_ptr(), off.data_ptr(), g_table16.data_ptr(),
-              B, 3, 2, L, enc.log2_scale, enc.base_resolution, enc.gridtype_id, 0, 0, _hip.LNH_F16, ws.data_ptr(), ws.numel(),
-              0, L, 0,
-              int(flags), tag=B, timer="lnh_grid_encode_backward_ws")
+    grid_backward_bucketed(g_feat, x01, enc._offsets_host, g_table16, enc.log2_scale, enc.base_resolution, enc.gridtype_id,
+                           0, 0, ws, flags=flags, tag=B)
 
 
 # Data parallel: level windows of the table gradient.  The scatter pass of the backward runs once for all levels
@@ -154,15 +150,13 @@ def _grid_bwd_windows(g_feat, x01, g_table16, enc, B, ws=None, flags=0):
     points, profiles/r03_bench_dpwindows*.json of the first cut), then `..._finish` per window; yields (l0, l1) when the rows
     of that window are final, so that the caller can hand them to a collective while the next window is being reduced."""
     L = enc.num_levels
-    off = enc._offsets_host
     if ws is None:
         ws, _ = _grid_bwd_workspace(g_feat.device, enc, B)
-    args = (g_feat.data_ptr(), x01.data_ptr(), off.data_ptr(), g_table16.data_ptr(), B, 3, 2, L, enc.log2_scale,
-            enc.base_resolution, enc.gridtype_id, 0, 0, _hip.LNH_F16, ws.data_ptr(), ws.numel())
-    _hip.call("lnh_grid_encode_backward_ws_ex", *args, 0, L, 1, int(flags), tag=B, timer="lnh_grid_encode_backward_ws_begin")
-    for l0, l1 in (_DP_LEVEL_WINDOWS if L == 16 else ((0, L),)):
-        _hip.call("lnh_grid_encode_backward_ws_ex", *args, l0, l1, 2, int(flags), timer="lnh_grid_encode_backward_ws_finish")
-        yield l0, l1
+    args = (g_feat, x01, enc._offsets_host, g_table16, enc.log2_scale, enc.base_resolution, enc.gridtype_id, 0, 0, ws)
+    grid_backward_bucketed(*args, split=1, flags=flags, timer="lnh_grid_encode_backward_ws_begin", tag=B)
+    for window in (_DP_LEVEL_WINDOWS if L == 16 else ((0, L),)):
+        grid_backward_bucketed(*args, window=window, split=2, flags=flags, timer="lnh_grid_encode_backward_ws_finish")
+        yield window
 
 
 def _grid_bwd_overlapped(g_feat, x01, g_table16, enc, B, table_param, ws=None, flags=0):

@@ -240,3 +240,45 @@ def test_bench_refuses_to_run_without_a_gpu():
                        capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "no CPU fallback" in (r.stdout + r.stderr)
     assert not any(line.startswith("{") for line in r.stdout.splitlines())  # no result line
+
+
+def _grid_host_record():
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "grid_host.json")) as f:
+        return json.load(f)
+
+
+def test_grid_backward_plan_functions_answer_as_recorded():
+    """lnh_grid_backward_workspace_size / _size_min / _clear_bytes (full size, minimum, one byte below) / _plan_info (levels 0,
+    5, 15) for the table of tests/grid_host_cases.py — default hash grid, tiny-cuda-nn lattice, tiled, align_corners, a 2^20
+    table (not served: 0), fp32 / fp16, 1024 to 13.6 M points (chunked), and the arguments each of the four answers with 0 —
+    against tests/golden/grid_host.json, recorded from the library of the commit named in that file."""
+    import grid_host_cases as cases
+    from lidarnerf import _hip
+    want = _grid_host_record()["plan"]
+    got = cases.plan_answers(_hip.lib())
+    assert set(got) == set(want) and len(got) >= 5 * 2 * 4 + 9
+    for name in sorted(want):
+        assert got[name] == want[name], (name, got[name], want[name])
+    # the record itself holds what it is meant to pin
+    assert want["hash/dtype1/B3407872"]["size"] > want["hash/dtype1/B3407872"]["size_min"] > 0
+    assert want["hash_log2_20/dtype1/B1024"]["size"] == 0 and want["hash_log2_20/dtype1/B1024"]["plan_info"]["0"]["rc"] == -2
+
+
+def test_grid_backward_ws_entry_points_check_arguments_as_recorded():
+    """All five lnh_grid_encode_backward_ws* entry points with B == 0 and with every argument they reject (and calls wrong in
+    two ways, which pin the order of the checks): return code and lnh_last_error() text against tests/golden/grid_host.json.
+    A call that succeeds leaves the error text of the call before it."""
+    import grid_host_cases as cases
+    from lidarnerf import _hip
+    lib = _hip.lib()
+    assert lib.lnh_version() == 102
+    want = _grid_host_record()["ws"]
+    got = cases.ws_answers(lib)
+    assert set(got) == set(want) and len(got) >= 5 * 21 + 7
+    for name in sorted(want):
+        assert got[name] == want[name], (name, got[name], want[name])
+    # level_end = L + 1: the window entry points refuse it, _ex clamps it
+    for fn in ("lnh_grid_encode_backward_ws_levels", "lnh_grid_encode_backward_ws_finish"):
+        assert want[fn + "/end_L_plus_1"] == {"rc": -1, "error": "grid backward: need level_begin <= level_end <= L"}
+    assert want["lnh_grid_encode_backward_ws_ex/end_L_plus_1"]["rc"] == 0

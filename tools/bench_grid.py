@@ -5,7 +5,7 @@ geometry: rays leave one sensor position, samples 1 m .. 81 m in scene units, st
     python tools/bench_grid.py [--rays 4096] [--per-level] [--reps 5]
 
 Prints HIP-event times (min over reps) of the whole forward / backward and, with --per-level, of every level on its own
-(backward: lnh_grid_encode_backward_ws_levels(l, l+1); forward: a one-level call on the level's table slice).  Run it
+(backward: the level window [l, l+1) of the bucketed backward; forward: a one-level call on the level's table slice).  Run it
 under `rocprofv3 --kernel-trace` to split the backward into its scatter / reduce / finalize kernels."""
 import argparse
 import os
@@ -17,7 +17,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "lidar-nerf_amd")]
 from lidarnerf import _hip  # noqa: E402
-from lidarnerf.gridencoder.grid import level_offsets  # noqa: E402
+from lidarnerf.gridencoder.grid import grid_backward_bucketed, level_offsets  # noqa: E402
 
 SCALE = 0.010784853507573345
 
@@ -87,8 +87,7 @@ def main():
                   None, 0, 0, 0, 1)
 
     def bwd(l0=0, l1=Lv):
-        _hip.call("lnh_grid_encode_backward_ws_levels", g.data_ptr(), x.data_ptr(), off.data_ptr(), ge.data_ptr(), B, 3, 2,
-                  Lv, S, 16, 0, 0, 0, 1, ws.data_ptr(), need, l0, l1)
+        grid_backward_bucketed(g, x, off, ge, S, 16, 0, 0, 0, ws, window=(l0, l1), timer="lnh_grid_encode_backward_ws_levels")
 
     if not a.skip_fwd:
         fwd()
