@@ -333,6 +333,58 @@ LNH_API int lnh_composite_rays(uint32_t n_alive, uint32_t n_step, float T_thresh
                                const float *sigmas, const float *rgbs, const float *deltas, float *weights_sum,
                                float *depth, float *image, lnh_stream_t stream);
 
+/*
+ * Alive-ray evaluation of LiDAR rays (NeRFRenderer.run_cuda_alive): one round = lnh_lidar_march_rays, the field on the
+ * round's samples, lnh_lidar_composite_rays, lnh_alive_compact; repeat until no ray is alive.  The loop is the one of
+ * march_rays / composite_rays above (raymarching.cu:808-928, 966-1053; raymarching.py:362-512); the sample lattice is the
+ * one of lnh_march_rays_train (raymarching.cu:379-439), the compositing the one of lnh_lidar_composite_rays_train_forward.
+ * No entry point here touches MLP element types: the same three serve the fp16 and the bf16 build of the field (no _bf16
+ * twins); the field itself is the existing ragged chain (lnh_ragged_points, lnh_grid_encode_forward,
+ * lnh_density_mlp_forward[_bf16], lnh_ragged_color_forward[_bf16]) on the table lnh_lidar_march_rays writes.
+ *
+ * State, all caller-allocated, N = rays of the call:
+ *   rays_alive [N] int32 x 2, alive_count [1] int32 x 2   ping-pong halves: ray ids of the alive rays in slot order and
+ *                                     how many.  The caller starts with 0 .. N-1 / N.  Every kernel clips the count to
+ *                                     n_alive_max, the HOST's upper bound, which sizes launches and sample buffers.
+ *   rays_t [N] f32                    resume parameter; the caller starts it at the ray's near.  lnh_lidar_march_rays
+ *                                     stores the exact t behind the ray's last sample when the ray got all n_step samples
+ *                                     of the round, else +inf = "left the box" (the walk passed far, or the ray holds its
+ *                                     max_steps samples): t < far never holds again.
+ *   rays_steps [N] int32              samples so far, ZEROED by the caller (the lattice walk emits at most max_steps per
+ *                                     ray, raymarching.cu:436, over all rounds together).
+ *   weights_sum [N], depth [N], image [N,K] f32   ZEROED by the caller;  transmittance [N] f32 set to ONE by the caller.
+ *
+ * lnh_lidar_march_rays: slot n < min(alive_count[0], n_alive_max) marches ray rays_alive[n] for at most n_step occupied
+ * samples into rows [n * n_step, (n + 1) * n_step) of xyzs [n_alive_max * n_step, 3] / deltas [.., 2] (no clearing needed:
+ * deltas of the rows a slot does not fill are written as 0, the end-of-ray mark of raymarching.cu:1003; their xyzs keep
+ * whatever finite values they held) and writes ALL N rows of rays [N,3] = (ray id, first row, count) — (0, 0, 0) beyond
+ * the alive count — the table the ragged field kernels and lnh_lidar_composite_rays walk.  Concatenated over the rounds,
+ * a ray's xyzs / deltas are bit for bit the samples lnh_march_rays_train emits for it with noises = 0, whatever the
+ * sequence of n_step.  samples_total (NULL or [1] int32, caller-zeroed) += samples of the round (integer atomic).
+ *
+ * lnh_lidar_composite_rays: sigmas [rows] (density_scale applied), feats [rows, K], K <= 3:
+ *   alpha = 1 - exp(-sigma dt),  w = alpha T,  weights_sum += w,  depth += w ((xyz - o) . d),  image += w feat,
+ *   T *= 1 - alpha, stop AFTER the sample that takes T below T_thresh (renderer.py:233-271 on ragged samples; the carried
+ *   T, not the template's 1 - weights_sum).  A ray is dead — rays_alive[n] = -1 — when it stopped, when its round came back
+ *   short of n_step samples, or when rays_t holds the mark.  One group of min(64, n_step rounded up to a power of two) lanes
+ *   per ray, one lane per sample.
+ *
+ * lnh_alive_compact: the entries >= 0 of rays_alive[0 .. min(alive_count[0], n_alive_max)), in slot order, to
+ * rays_alive_out; their number to alive_count_out[0].  One workgroup; the order never depends on timing.
+ */
+LNH_API int lnh_lidar_march_rays(uint32_t n_alive_max, uint32_t n_step, uint32_t N, const int32_t *alive_count,
+                                 const int32_t *rays_alive, float *rays_t, int32_t *rays_steps, const float *rays_o,
+                                 const float *rays_d, const uint8_t *grid, float bound, float dt_gamma,
+                                 uint32_t max_steps, uint32_t C, uint32_t H, const float *fars, float *xyzs,
+                                 float *deltas, int32_t *rays, int32_t *samples_total, lnh_stream_t stream);
+LNH_API int lnh_lidar_composite_rays(uint32_t n_alive_max, uint32_t n_step, uint32_t N, uint32_t K, float T_thresh,
+                                     const int32_t *alive_count, int32_t *rays_alive, const float *rays_t,
+                                     const int32_t *rays, const float *sigmas, const float *feats, const float *deltas,
+                                     const float *xyzs, const float *rays_o, const float *rays_d, float *weights_sum,
+                                     float *depth, float *image, float *transmittance, lnh_stream_t stream);
+LNH_API int lnh_alive_compact(uint32_t n_alive_max, const int32_t *alive_count, const int32_t *rays_alive,
+                              int32_t *rays_alive_out, int32_t *alive_count_out, lnh_stream_t stream);
+
 /* ------------------------------------------------------------------ LiDAR renderer kernels ------------------ */
 /*
  * The reference composites LiDAR rays with ~40 PyTorch launches (lidarnerf/nerf/renderer.py:180-271).  These

@@ -711,3 +711,61 @@ def render_lidar_ragged(model, xyzs, dirs, deltas, rays, rays_o, rays_d, T_thres
     return FusedLidarRagged.apply(xyzs.contiguous(), dirs.contiguous(), deltas.contiguous(), rays.contiguous(),
                                   rays_o.contiguous(), rays_d.contiguous(), sp.table, sp.ws0, sp.ws1, sp.wc0, sp.wc1, sp.wc2,
                                   model, sp, mlp_dtype(), T_thresh)
+
+
+class RaggedEvalField:
+    """The field half of FusedLidarRagged.forward for the alive-ray evaluation loop (renderer.run_cuda_alive), no autograd:
+    what does not change between the rounds of a call — the fp16 table, the packed weights, the per-ray direction term —
+    is made once, the per-sample buffers are allocated once for `rows` samples and reused; a round is lnh_ragged_points ->
+    lnh_grid_encode_forward -> lnh_density_mlp_forward -> lnh_ragged_color_forward on the marcher's table.  The same kernels
+    per sample as the existing evaluation, so a sample's sigma and colour carry the same bits on both paths."""
+
+    def __init__(self, model, rays_d, rows):
+        from ..ffmlp.ffmlp import mlp_dtype
+        self._setup(model, rays_d.contiguous(), int(rows), mlp_dtype())  # (the MLP build follows the caller's autocast dtype)
+
+    @_no_autocast
+    def _setup(self, model, rays_d, rows, mdt):
+        sp = model.fused_spec()
+        self.mdt = mdt
+        self.sfx = sfx = _hip.mlp_suffix(mdt)
+        self.enc = enc = sp.grid
+        self.bound, self.ds = float(model.bound), float(model.density_scale)
+        dev, N, L = rays_d.device, rays_d.shape[0], enc.num_levels
+        self.table16 = table16_of(sp.table_param, sp.table, False)
+        kd, deg = sp.n_dir, int(sp.dir_freq_degree)
+        mats = [m.detach() if m.dtype == torch.float32 and m.stride(-1) == 1 else m.detach().float().contiguous()
+                for m in (sp.ws0, sp.ws1, sp.wc0, sp.wc1, sp.wc2)]
+        self.wsig16 = torch.empty(64 * 32 + 16 * 64, dtype=mdt, device=dev)
+        self.wcol16 = torch.empty(64 * 16 + 64 * 64 + 16 * 64, dtype=mdt, device=dev)
+        _hip.call("lnh_lidar_pack_weights" + sfx, mats[0].data_ptr(), mats[0].stride(0), mats[1].data_ptr(),
+                  mats[1].stride(0), mats[2].data_ptr(), mats[2].stride(0), kd, mats[3].data_ptr(), mats[3].stride(0),
+                  mats[4].data_ptr(), mats[4].stride(0), self.wsig16.data_ptr(), self.wcol16.data_ptr())
+        enc_d16 = torch.empty((N, kd), dtype=torch.float32, device=dev)
+        self.cdir = torch.empty((N, 64), dtype=torch.float32, device=dev)
+        _hip.call("lnh_lidar_dir_term_freq" + sfx, rays_d.data_ptr(), deg, mats[2].data_ptr(), mats[2].stride(0), N,
+                  enc_d16.data_ptr(), self.cdir.data_ptr())
+        self.N, self.rows = N, rows
+        self.x01 = torch.empty(rows * 3, dtype=torch.float32, device=dev)
+        self.feat = torch.empty(L * rows * 2, dtype=torch.half, device=dev)
+        self.h16 = torch.empty(rows * 16, dtype=mdt, device=dev)
+        self.sigma = torch.empty(rows, dtype=torch.float32, device=dev)
+        self.rgb = torch.empty(rows * 2, dtype=torch.float32, device=dev)
+
+    @_no_autocast
+    def __call__(self, xyzs, rays, M):
+        """(sigma [M] with density_scale applied, rgb [M, 2]) of the first M rows of xyzs; rgb rows no ray of the table owns
+        keep stale values (the compositor reads owned rows only)."""
+        if M > self.rows or rays.shape[0] != self.N:
+            raise RuntimeError("RaggedEvalField: more samples than the buffers were sized for, or another ray table")
+        enc, sfx, L = self.enc, self.sfx, self.enc.num_levels
+        _hip.call("lnh_ragged_points", xyzs.data_ptr(), self.bound, M, self.x01.data_ptr())
+        _hip.call("lnh_grid_encode_forward", self.x01.data_ptr(), self.table16.data_ptr(), enc._offsets_host.data_ptr(),
+                  self.feat.data_ptr(), M, 3, 2, L, enc.log2_scale, enc.base_resolution, None, enc.gridtype_id, 0, 0,
+                  _hip.LNH_F16, tag=M)
+        _hip.call("lnh_density_mlp_forward" + sfx, self.feat.data_ptr(), self.wsig16.data_ptr(), M, M, M, 0, 0,
+                  self.h16.data_ptr(), self.sigma.data_ptr())
+        _hip.call("lnh_ragged_color_forward" + sfx, self.h16.data_ptr(), rays.data_ptr(), self.cdir.data_ptr(),
+                  self.wcol16.data_ptr(), self.N, M, self.rgb.data_ptr())
+        sigma = self.sigma[:M]
+        return (sigma * self.ds if self.ds != 1.0 else sigma), self.rgb[:M * 2].view(M, 2)

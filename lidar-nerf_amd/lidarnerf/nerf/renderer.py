@@ -89,6 +89,8 @@ class NeRFRenderer(nn.Module):
         # cascade / grid_size above) and the raymarching kernels of torch-ngp but dropped the caller (SURVEY.md §0.6:
         # no density_grid / run_cuda / update_extra_state in renderer.py); this is that caller, for the LiDAR outputs.
         self.cuda_ray = cuda_ray
+        self.alive_march = False  # evaluation through run_cuda_alive (see run_cuda); opt-in
+        self.alive_stats = None
         if cuda_ray:
             self.register_buffer("density_grid", torch.zeros(self.cascade, self.grid_size ** 3))
             self.register_buffer("density_bitfield", torch.zeros(self.cascade * self.grid_size ** 3 // 8, dtype=torch.uint8))
@@ -247,13 +249,21 @@ class NeRFRenderer(nn.Module):
         self.local_step = 0
 
     def run_cuda(self, rays_o, rays_d, cal_lidar_color=True, dt_gamma=0, perturb=False, force_all_rays=False,
-                 max_steps=1024, T_thresh=1e-4, **kwargs):
+                 max_steps=1024, T_thresh=1e-4, alive_march=None, **kwargs):
         """Occupancy-grid render of LiDAR rays: march through the occupied cells between 1 m and 81 m (scene units,
         renderer.py:129-138) with lnh_march_rays_train, evaluate density + LiDAR colour on the ragged samples, composite
         with the K = 2 / absolute-depth kernel.  Training mode keeps autograd; evaluation marches the same way (all rays)
-        under no_grad.  Same result keys as run()."""
+        under no_grad.  Same result keys as run().
+
+        `alive_march=True` (or the module attribute `self.alive_march`; the keyword wins) sends an EVALUATION call through
+        run_cuda_alive instead — the alive-ray loop that stops shading behind the first opaque surface.  Off by default;
+        training mode ignores it."""
         if not cal_lidar_color:
             raise NotImplementedError("occupancy-grid rendering is built for the LiDAR outputs (cal_lidar_color=True)")
+        if not self.training and (self.alive_march if alive_march is None else alive_march):
+            return self.run_cuda_alive(rays_o, rays_d, dt_gamma=dt_gamma, perturb=perturb, max_steps=max_steps,
+                                       T_thresh=T_thresh, n_step0=kwargs.get("alive_n_step0"),
+                                       n_step_max=kwargs.get("alive_n_step_max"))
         self.out_dim = self.out_lidar_color_dim
         prefix = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3).float()
@@ -323,6 +333,92 @@ class NeRFRenderer(nn.Module):
                                                                  T_thresh)
         return {"depth_lidar": depth.view(*prefix), "image_lidar": image.view(*prefix, self.out_dim),
                 "weights_sum_lidar": ws}
+
+    @torch.no_grad()
+    def run_cuda_alive(self, rays_o, rays_d, dt_gamma=0, perturb=False, max_steps=1024, T_thresh=1e-4,
+                       n_step0=None, n_step_max=None):
+        """Evaluation of LiDAR rays as torch-ngp's alive-ray loop (raymarching.py:362-512 of the reference ships its two
+        kernels), on this renderer's own round (csrc/lidar_infer.hip): all rays alive -> { march at most n_step samples per
+        alive ray, field on those samples, composite into per-ray state, compact the survivors } until none is alive.
+        A ray stops being shaded in the round its transmittance falls below T_thresh — run_cuda's evaluation marches and
+        shades every occupied sample up to `far` and lets only the compositor stop.
+
+        Same ranges (lnh_lidar_march_prologue), same lattice and samples (bit for bit the prefix of lnh_march_rays_train's),
+        same field kernels per sample and the same compositing arithmetic as run_cuda in eval mode: results differ from
+        it by float summation order only.  Sample buffers hold N * n_step0 rows (5 floats each), allocated once; the
+        schedule is raymarching.alive_n_step.  One 4-byte host read per round (the alive count).  `self.alive_stats`
+        afterwards: rounds, n_step per round, samples shaded (one more read, after the loop), sample-buffer bytes."""
+        from . import fused
+        self.out_dim = self.out_lidar_color_dim
+        prefix = rays_o.shape[:-1]
+        rays_o = rays_o.contiguous().view(-1, 3).float()
+        rays_d = rays_d.contiguous().view(-1, 3).float()
+        N = rays_o.shape[0]
+        _hip.require_cuda(rays_o, rays_d)
+        dev, K = rays_o.device, self.out_dim
+        n_step0 = int(n_step0 or raymarching.ALIVE_N_STEP0)
+        n_step_max = max(int(n_step_max or raymarching.ALIVE_N_STEP_MAX), n_step0)
+        ws = torch.zeros(N, dtype=torch.float32, device=dev)
+        depth = torch.zeros(N, dtype=torch.float32, device=dev)
+        image = torch.zeros((N, K), dtype=torch.float32, device=dev)
+        out = {"depth_lidar": depth.view(*prefix), "image_lidar": image.view(*prefix, K), "weights_sum_lidar": ws}
+        self.alive_stats = {"rounds": 0, "n_steps": [], "samples": 0, "sample_buffer_bytes": 0, "rays": N}
+        if N == 0:
+            return out
+        aabb = self.aabb_infer.contiguous().float()
+        nears = torch.empty(N, dtype=torch.float32, device=dev)
+        fars = torch.empty(N, dtype=torch.float32, device=dev)
+        _hip.call("lnh_lidar_march_prologue", rays_o.data_ptr(), rays_d.data_ptr(), aabb.data_ptr(), N,
+                  float(self.min_near_lidar), 81.0, nears.data_ptr(), fars.data_ptr(), None, None, 0)
+        rays_t = nears  # resume parameter, starts at near
+        if perturb:  # the marcher's start jitter (raymarching.cu:372-376): a fraction of the first step
+            dt_min, dt_max = 2 * math.sqrt(3) / max_steps, 2 * math.sqrt(3) * 2 ** (self.cascade - 1) / self.grid_size
+            rays_t = nears + (nears * dt_gamma).clamp(dt_min, dt_max) * torch.rand(N, dtype=torch.float32, device=dev)
+        rows = N * n_step0
+        samples = torch.zeros(rows * 5, dtype=torch.float32, device=dev)  # xyzs 3 | deltas 2, reused by every round
+        xyzs, deltas = samples[:rows * 3], samples[rows * 3:]
+        ints = torch.zeros(2 * N + N + 3 * N + 4, dtype=torch.int32, device=dev)
+        alive = [ints[:N], ints[N:2 * N]]              # ping-pong ray lists ...
+        rays_steps, table = ints[2 * N:3 * N], ints[3 * N:6 * N].view(N, 3)
+        counts = [ints[6 * N:6 * N + 1], ints[6 * N + 1:6 * N + 2]]  # ... and their counts
+        total = ints[6 * N + 2:6 * N + 3]
+        alive[0].copy_(torch.arange(N, dtype=torch.int32, device=dev))
+        counts[0].fill_(N)
+        trans = torch.ones(N, dtype=torch.float32, device=dev)
+        self.alive_stats["sample_buffer_bytes"] = samples.numel() * 4
+        use_fused = (getattr(self, "fused_lidar", False) and torch.is_autocast_enabled() and fused.ragged_supported(self))
+        field = fused.RaggedEvalField(self, rays_d, rows) if use_fused else None
+        bits = self.density_bitfield.contiguous()
+        n_alive, cur = N, 0
+        for _ in range(raymarching.alive_max_rounds(max_steps, n_step0)):
+            n_step = raymarching.alive_n_step(n_alive, N, n_step0, n_step_max)
+            M = n_alive * n_step  # (<= rows: n_step <= n_step0 * (N // n_alive))
+            raymarching.lidar_march_rays(n_alive, n_step, counts[cur], alive[cur], rays_t, rays_steps, rays_o, rays_d,
+                                         self.bound, bits, self.cascade, self.grid_size, fars, xyzs, deltas, table,
+                                         dt_gamma, max_steps, total)
+            x = xyzs[:M * 3].view(M, 3)
+            if field is not None:
+                sigmas, feats = field(x, table, M)
+            else:
+                dens = self.density(x)
+                sigmas = (dens["sigma"].float() * self.density_scale).contiguous()
+                dirs = rays_d[table[:n_alive, 0].long()].unsqueeze(1).expand(n_alive, n_step, 3).reshape(M, 3)
+                feats = self.color(x, dirs, cal_lidar_color=True, mask=None, geo_feat=dens["geo_feat"]).float().contiguous()
+            raymarching.lidar_composite_rays(n_alive, n_step, counts[cur], alive[cur], rays_t, table, sigmas, feats, deltas,
+                                             xyzs, rays_o, rays_d, ws, depth, image, trans, T_thresh)
+            raymarching.alive_compact(n_alive, counts[cur], alive[cur], alive[1 - cur], counts[1 - cur])
+            cur = 1 - cur
+            self.alive_stats["rounds"] += 1
+            self.alive_stats["n_steps"].append(n_step)
+            n_alive = int(counts[cur].item())  # the round's one host read
+            if n_alive == 0:
+                break
+        if n_alive != 0:
+            raise RuntimeError(f"run_cuda_alive: {n_alive} rays still alive after the worst-case number of rounds")
+        self.alive_stats["samples"] = int(total.item())
+        if isinstance(getattr(self, "alive_stats_log", None), list):  # (a staged frame is many calls: tools sum over them)
+            self.alive_stats_log.append(self.alive_stats)
+        return out
 
     def render(self, rays_o, rays_d, cal_lidar_color=False, staged=False, max_ray_batch=4096, **kwargs):
         if self.cuda_ray and cal_lidar_color:

@@ -216,3 +216,70 @@ def composite_rays(n_alive, n_step, rays_alive, rays_t, sigmas, rgbs, deltas, we
               sigmas.data_ptr(), rgbs.data_ptr(), deltas.data_ptr(), weights_sum.data_ptr(), depth.data_ptr(),
               image.data_ptr())
     return tuple()
+
+
+# ----------------------------------------------------------------------------------------
+# alive-ray evaluation of LiDAR rays (NeRFRenderer.run_cuda_alive; include/lidarnerf_hip.h)
+# ----------------------------------------------------------------------------------------
+ALIVE_N_STEP0 = 32    # samples per ray in a round while every ray is alive: the SMALLEST round of the schedule
+ALIVE_N_STEP_MAX = 128
+
+
+def alive_n_step(n_alive, n_total, n_step0=ALIVE_N_STEP0, n_step_max=ALIVE_N_STEP_MAX):
+    """Samples per alive ray in the next round: n_step0 * (n_total // n_alive), capped at n_step_max.
+
+    The sample buffers of a call hold n_total * n_step0 rows and never grow: as rays die the survivors share the rows the
+    dead ones gave up (torch-ngp's run_cuda has the same shape, max(min(N // n_alive, 8), 1), with 1 .. 8 samples).  A round
+    here costs a host read of the alive count and ~8 launches, ~0.13 ms whatever it holds: a full NeRF-MVL-shaped frame took
+    10.1 / 7.0 / 5.4 ms with n_step0 = 8 / 16 / 32 (90 / 54 / 33 rounds), hence 32.  n_step is never below n_step0,
+    which bounds the loop: see alive_max_rounds."""
+    if n_alive <= 0 or n_total <= 0:
+        return int(n_step0)
+    return int(max(n_step0, min(n_step0 * (n_total // n_alive), n_step_max)))
+
+
+def alive_max_rounds(max_steps, n_step0=ALIVE_N_STEP0):
+    """Worst-case rounds of the alive loop: an alive ray takes n_step >= n_step0 samples per round or dies in it, and the
+    marcher retires a ray that holds max_steps samples."""
+    return -(-int(max_steps) // int(n_step0))
+
+
+def lidar_march_rays(n_alive_max, n_step, alive_count, rays_alive, rays_t, rays_steps, rays_o, rays_d, bound,
+                     density_bitfield, C, H, fars, xyzs, deltas, rays, dt_gamma=0, max_steps=1024, samples_total=None):
+    """One marching round of the alive loop, in place (lnh_lidar_march_rays): the alive rays' next n_step occupied samples
+    into xyzs / deltas [n_alive_max * n_step, 3 | 2], the round's (ray id, first row, count) table into rays [N, 3], the
+    resume parameter into rays_t, the running sample count into rays_steps."""
+    _hip.require_cuda(alive_count, rays_alive, rays_t, rays_steps, rays_o, rays_d, density_bitfield, fars, xyzs, deltas, rays)
+    N = rays.shape[0]
+    if xyzs.numel() < n_alive_max * n_step * 3 or deltas.numel() < n_alive_max * n_step * 2:
+        raise RuntimeError("lidar_march_rays: sample buffers hold fewer than n_alive_max * n_step rows")
+    _hip.call("lnh_lidar_march_rays", int(n_alive_max), int(n_step), N, alive_count.data_ptr(), rays_alive.data_ptr(),
+              rays_t.data_ptr(), rays_steps.data_ptr(), rays_o.data_ptr(), rays_d.data_ptr(), density_bitfield.data_ptr(),
+              float(bound), float(dt_gamma), int(max_steps), int(C), int(H), fars.data_ptr(), xyzs.data_ptr(),
+              deltas.data_ptr(), rays.data_ptr(), _hip.ptr(samples_total))
+
+
+def lidar_composite_rays(n_alive_max, n_step, alive_count, rays_alive, rays_t, rays, sigmas, feats, deltas, xyzs, rays_o,
+                         rays_d, weights_sum, depth, image, transmittance, T_thresh=1e-4):
+    """Accumulate one round in place into weights_sum [N], depth [N], image [N, K], transmittance [N]; the rays that ended
+    get rays_alive[n] = -1 (lnh_lidar_composite_rays)."""
+    _hip.require_cuda(alive_count, rays_alive, rays_t, rays, sigmas, feats, deltas, xyzs, rays_o, rays_d, weights_sum, depth,
+                      image, transmittance)
+    for t in (sigmas, feats, weights_sum, depth, image, transmittance):
+        if t.dtype != torch.float32:
+            raise RuntimeError("lidar_composite_rays: sigmas / feats / the per-ray state must be float32")
+    N, K = rays.shape[0], image.shape[-1]
+    if sigmas.numel() < n_alive_max * n_step or feats.numel() < n_alive_max * n_step * K:
+        raise RuntimeError("lidar_composite_rays: sigmas / feats hold fewer than n_alive_max * n_step rows")
+    _hip.call("lnh_lidar_composite_rays", int(n_alive_max), int(n_step), N, K, float(T_thresh), alive_count.data_ptr(),
+              rays_alive.data_ptr(), rays_t.data_ptr(), rays.data_ptr(), sigmas.data_ptr(), feats.data_ptr(),
+              deltas.data_ptr(), xyzs.data_ptr(), rays_o.data_ptr(), rays_d.data_ptr(), weights_sum.data_ptr(),
+              depth.data_ptr(), image.data_ptr(), transmittance.data_ptr())
+
+
+def alive_compact(n_alive_max, alive_count, rays_alive, rays_alive_out, alive_count_out):
+    """The surviving ray ids (entries >= 0) of the first min(alive_count, n_alive_max) slots, in slot order, into the other
+    half of the ping-pong pair (lnh_alive_compact)."""
+    _hip.require_cuda(alive_count, rays_alive, rays_alive_out, alive_count_out)
+    _hip.call("lnh_alive_compact", int(n_alive_max), alive_count.data_ptr(), rays_alive.data_ptr(),
+              rays_alive_out.data_ptr(), alive_count_out.data_ptr())
