@@ -1,6 +1,6 @@
 """Fused LiDAR render step: the whole `NeRFRenderer.run` + `NeRFNetwork.density/color` chain of the reference
-(lidarnerf/nerf/renderer.py:99-298, lidarnerf/nerf/network.py:162-237) as ~16 kernel launches forward and ~10
-backward, with explicit gradients.
+(lidarnerf/nerf/renderer.py:99-298, lidarnerf/nerf/network.py:162-237) as 7 kernel launches forward (with the step
+prologue) and their mirror image backward, with explicit gradients.
 
 Used by NeRFNetwork.render (both flavours: `network` and the tcnn-shaped `network_tcnn`, through `model.fused_spec()`)
 for the configuration the reference trains (`cal_lidar_color=True`, hash-grid L=16 F=2, 64-wide sigma net with one
@@ -8,19 +8,21 @@ hidden layer, 64-wide LiDAR colour net with two) under fp16 autocast.  Anything 
 renderer.py / network.py, which computes the same values from the same kernels' unfused forms.
 
 Forward                                                       kernels (liblidarnerf_hip.so)
-  z = near + (far-near) linspace + perturb                    one torch.rand + lnh_lidar_coarse_samples
-  x = (clip(o + d z) + b) / 2b                                lnh_lidar_sample_points
-  feat = hashgrid(x)      [16, N(T+t), 2] fp16, row-mapped    lnh_grid_encode_forward_mapped
-  h16, sigma = sigma_net(feat)  strided into [N,T+t,*]        lnh_density_mlp_forward   (weights: lnh_lidar_pack_weights)
-  new_z, z_all, perm = resample(z, sigma)                     lnh_lidar_resample
-  (same three steps for the t new samples, same buffers)
-  sigma_m, w = merge + weights                                lnh_lidar_merge_weights
-  cdir = W0[:, :kd] enc(d)      per RAY                       model's direction features + lnh_lidar_dir_term
-  rgb = colour_net(h16[perm], cdir) * (w > 1e-4)              lnh_lidar_color_forward
-  ws, depth, image = composite(sigma_m, rgb, z_all)           lnh_lidar_composite_forward
+  wsig16, wcol16 = packed weights; cdir = W0[:, :kd] enc(d)   lnh_lidar_step_prologue (frequency-encoded directions; else
+  z = near + (far-near) linspace + perturb   (one torch.rand)   lnh_lidar_pack_weights, the model's direction features +
+  x = (clip(o + d z) + b) / 2b                                  lnh_lidar_dir_term, lnh_lidar_coarse_sample_points)
+  feat = hashgrid(x)      [16, N(T+t), 2] fp16, row-mapped    lnh_grid_encode_forward_mapped_ex
+  h16, sigma = sigma_net(feat)  strided into [N,T+t,*]        lnh_density_mlp_forward
+  new_z, z_all, perm = resample(z, sigma); x of the new_z     lnh_lidar_resample_points
+  (encode + sigma net for the t new samples, same buffers)
+  sigma_m, w = merge + weights                                lnh_lidar_color_composite_forward (T+t > 2048:
+  rgb = colour_net(h16[perm], cdir) * (w > 1e-4)                lnh_lidar_merge_weights, lnh_lidar_color_forward,
+  ws, depth, image = composite(sigma_m, rgb, z_all)             lnh_lidar_composite_forward)
 Backward runs the mirror image over all N(T+t) points at once; the hash-table gradient uses the bucketed
 scatter-reduce (no HBM atomics) and, data-parallel, goes on the wire in fp16 window by window.
 """
+import os
+
 import numpy as np
 import torch
 from torch.autograd import Function
@@ -58,12 +60,6 @@ def _bucketed_backward_ok(enc):
     return ok
 
 
-def _gridtype_ok(enc):
-    """gridtype 0 (hash) or 2 (tiny-cuda-nn lattice); the latter needs a library that knows it (lnh_version >= 101)."""
-    _hip.require_gridtype(enc.gridtype_id)
-    return True
-
-
 def supported(model, cal_lidar_color, num_steps, upsample_steps):
     """True when `model` has exactly the shapes the fused kernels are specialised for."""
     try:
@@ -76,18 +72,13 @@ def supported(model, cal_lidar_color, num_steps, upsample_steps):
               and sp.n_color_mats == 3 and 1 <= sp.n_dir <= 128 and tuple(sp.wc0.shape) == (64, sp.n_dir + 15)
               and tuple(sp.wc1.shape) == (64, 64) and tuple(sp.wc2.shape) == (2, 64)
               and model.geo_feat_dim == 15 and (num_steps + upsample_steps) % 16 == 0
-              and sp.table.is_cuda and _gridtype_ok(enc) and _bucketed_backward_ok(enc))
-        return bool(ok)
+              and sp.table.is_cuda)
+        if not ok:
+            return False
+        _hip.require_gridtype(enc.gridtype_id)  # (gridtype 2 needs a library that knows it: lnh_version >= 101)
+        return bool(_bucketed_backward_ok(enc))
     except AttributeError:
         return False
-
-
-def _grid_fwd(x01, table16, enc, B):
-    L = enc.num_levels
-    out = torch.empty((L, B, 2), dtype=torch.half, device=x01.device)
-    _hip.call("lnh_grid_encode_forward", x01.data_ptr(), table16.data_ptr(), enc._offsets_host.data_ptr(),
-              out.data_ptr(), B, 3, 2, L, enc.log2_scale, enc.base_resolution, None, enc.gridtype_id, 0, 0, _hip.LNH_F16, tag=B)
-    return out
 
 
 def _grid_bwd_workspace(dev, enc, B):
@@ -132,16 +123,20 @@ def _grid_bwd(g_feat, x01, g_table16, enc, B, ws=None, flags=0):
 # into windows as well: 2.683 / 1362.)  Three windows cost what two cost and cut the table into thirds by rows (39 % / 31 % / 31 %):
 # only the last third's exchange has nothing left to hide behind, instead of 46 % with two.  Which count wins in the end
 # depends on the all-reduce time, which no box of this build could measure (LNH_DP_WINDOWS overrides the cut for that).
-import os as _os
 _DP_LEVEL_WINDOWS = ((0, 8), (8, 12), (12, 16))
-if _os.environ.get("LNH_DP_WINDOWS"):  # developer override for A/B runs: "0,10,16" = two windows
-    _c = [int(v) for v in _os.environ["LNH_DP_WINDOWS"].split(",")]
+if os.environ.get("LNH_DP_WINDOWS"):  # developer override for A/B runs: "0,10,16" = two windows
+    _c = [int(v) for v in os.environ["LNH_DP_WINDOWS"].split(",")]
     # (must be the same on every rank: the shard layout follows the windows)
     if len(_c) < 2 or _c[0] != 0 or _c[-1] != 16 or any(b <= a for a, b in zip(_c[:-1], _c[1:])):
-        raise ValueError(f"LNH_DP_WINDOWS={_os.environ['LNH_DP_WINDOWS']!r}: need increasing level cuts from 0 to 16, "
+        raise ValueError(f"LNH_DP_WINDOWS={os.environ['LNH_DP_WINDOWS']!r}: need increasing level cuts from 0 to 16, "
                          "e.g. '0,10,16'")
     _DP_LEVEL_WINDOWS = tuple(zip(_c[:-1], _c[1:]))
 FORCE_DP_WINDOWS = False  # bench.py --dp-windows: take the windowed backward on one GPU too (the exchange is a no-op)
+
+
+def _level_windows(enc):
+    """The level windows [l0, l1) in which the table gradient of `enc` is reduced, exchanged and sharded."""
+    return _DP_LEVEL_WINDOWS if enc.num_levels == 16 else ((0, enc.num_levels),)
 
 
 def _grid_bwd_windows(g_feat, x01, g_table16, enc, B, ws=None, flags=0):
@@ -149,32 +144,37 @@ def _grid_bwd_windows(g_feat, x01, g_table16, enc, B, ws=None, flags=0):
     but the last reduce pass: the scatter pass stays in ONE piece — cut into level windows it costs 0.33 ms more per 3.4 M
     points, profiles/r03_bench_dpwindows*.json of the first cut), then `..._finish` per window; yields (l0, l1) when the rows
     of that window are final, so that the caller can hand them to a collective while the next window is being reduced."""
-    L = enc.num_levels
     if ws is None:
         ws, _ = _grid_bwd_workspace(g_feat.device, enc, B)
     args = (g_feat, x01, enc._offsets_host, g_table16, enc.log2_scale, enc.base_resolution, enc.gridtype_id, 0, 0, ws)
     grid_backward_bucketed(*args, split=1, flags=flags, timer="lnh_grid_encode_backward_ws_begin", tag=B)
-    for window in (_DP_LEVEL_WINDOWS if L == 16 else ((0, L),)):
+    for window in _level_windows(enc):
         grid_backward_bucketed(*args, window=window, split=2, flags=flags, timer="lnh_grid_encode_backward_ws_finish")
         yield window
 
 
-def _grid_bwd_overlapped(g_feat, x01, g_table16, enc, B, table_param, ws=None, flags=0):
-    """_grid_bwd + parallel.allreduce_half_table, pipelined over level windows.  Returns the handles to wait on."""
+def _allreduce_windows(windows, g_table16, enc, table_param):
+    """parallel.allreduce_half_table on the table rows of each level window, as `windows` hands them out (a generator does
+    its own work in between).  Returns the handles to wait on."""
     off = enc._offsets_host
     handles = []
-    for l0, l1 in _grid_bwd_windows(g_feat, x01, g_table16, enc, B, ws, flags):
+    for l0, l1 in windows:
         h = parallel.allreduce_half_table(g_table16[int(off[l0]):int(off[l1])], table_param)
         if h is not None:
             handles.append(h)
     return handles
 
 
+def _grid_bwd_overlapped(g_feat, x01, g_table16, enc, B, table_param, ws=None, flags=0):
+    """_grid_bwd + parallel.allreduce_half_table, pipelined over level windows.  Returns the handles to wait on."""
+    return _allreduce_windows(_grid_bwd_windows(g_feat, x01, g_table16, enc, B, ws, flags), g_table16, enc, table_param)
+
+
 def _grid_bwd_sharded(g_feat, x01, enc, B, table_param):
     """Data parallel, sharded table optimizer (parallel.py "second cut"): per level window, the finished rows are copied
     into a buffer padded to world * shard rows and REDUCE-SCATTERED (fp16, SUM) — each rank keeps only its rows.
     Returns [(r0, r1, shard tensor [s, 2] fp16, handle, padded buffer)] per window of table rows [r0, r1): this rank's shard
-    holds rows [r0 + rank * s, r0 + (rank + 1) * s) (cut at r1).  Pipelined like the all-reduce: the collective of a window
+    holds the rows parallel.rank_rows(r0, r1, s, rank).  Pipelined like the all-reduce: the collective of a window
     runs behind the reduce pass of the following windows."""
     import torch.distributed as dist
     off = enc._offsets_host
@@ -252,14 +252,118 @@ def _sample_dist(N, value, dev):
     return t
 
 
+# The five matrices of a field, packed for the kernels (element type mdt: torch.half, or torch.bfloat16 for the bf16-operand
+# build of the kernels, config 5 — hash features stay fp16 either way):
+#   wsig16 = [ws0 [64, 32] | ws1 [16, 64]]
+#   wcol16 = [(0 | wc0[:, kd:kd+15]) [64, 16] | wc1 [64, 64] | wc2 padded to 16 rows [16, 64]]
+# The direction columns wc0[:, :kd] act once per RAY (cdir), so a sample's colour input is its own 16-wide sigma-net row.
+# The arena of the small gradients (fp32) is [g_wcol | g_wsig | g_wc0 [64, kd + 15]], the first two laid out like the vectors.
+_N_WSIG = 64 * 32 + 16 * 64
+_N_WCOL = 64 * 16 + 64 * 64 + 16 * 64
+
+
+def _weight_buffers(small, mdt, dev):
+    """(mats, wsig16, wcol16): the fp32 master matrices `small` = (ws0, ws1, wc0, wc1, wc2) as the kernels take them
+    (possibly strided views of flat parameter vectors) and the two packed vectors, still empty."""
+    mats = [m.detach() if m.dtype == torch.float32 and m.stride(-1) == 1 else m.detach().float().contiguous() for m in small]
+    return mats, torch.empty(_N_WSIG, dtype=mdt, device=dev), torch.empty(_N_WCOL, dtype=mdt, device=dev)
+
+
+def _pack_weights(small, kd, mdt, dev):
+    """_weight_buffers, packed: one launch."""
+    mats, wsig16, wcol16 = _weight_buffers(small, mdt, dev)
+    _hip.call("lnh_lidar_pack_weights" + _hip.mlp_suffix(mdt), mats[0].data_ptr(), mats[0].stride(0), mats[1].data_ptr(),
+              mats[1].stride(0), mats[2].data_ptr(), mats[2].stride(0), kd, mats[3].data_ptr(), mats[3].stride(0),
+              mats[4].data_ptr(), mats[4].stride(0), wsig16.data_ptr(), wcol16.data_ptr())
+    return mats, wsig16, wcol16
+
+
+def _dir_term_freq(rays_d, spec, wc0, mdt):
+    """(enc_d16 [N, kd], cdir [N, 64]) of raw directions: the frequency encoder of `spec`, rounded to the MLP element type,
+    and the per-ray direction term of the colour head's first layer (wc0: its entry of `mats`) — one launch."""
+    N, dev = rays_d.shape[0], rays_d.device
+    enc_d16 = torch.empty((N, spec.n_dir), dtype=torch.float32, device=dev)
+    cdir = torch.empty((N, 64), dtype=torch.float32, device=dev)
+    _hip.call("lnh_lidar_dir_term_freq" + _hip.mlp_suffix(mdt), rays_d.data_ptr(), int(spec.dir_freq_degree), wc0.data_ptr(),
+              wc0.stride(0), N, enc_d16.data_ptr(), cdir.data_ptr())
+    return enc_d16, cdir
+
+
+def _small_param_state(small):
+    """(dtypes, the five small matrices as the Parameters they are (network.NeRFNetwork) — or None when the field hands out
+    views of flat parameter vectors (network_tcnn): LidarTrainer takes their gradients straight from the backward's arena
+    then)."""
+    direct = all(isinstance(w, torch.nn.Parameter) and w.dtype == torch.float32 and w.is_contiguous() for w in small)
+    return tuple(w.dtype for w in small), small if direct else None
+
+
+def _small_grad_arena(kd, dev):
+    """One fp32 tensor for all gradients of the small matrices, UNCLEARED (the caller clears it in its one zero_regions
+    launch), and views of it: (arena, g_wcol, g_wsig, g_w0g [64, 16] — the geo-feature columns of wc0 as the colour
+    backward accumulates them —, g_small = the gradients of (ws0, ws1, wc0, wc1, wc2))."""
+    arena = torch.empty(_N_WCOL + _N_WSIG + 64 * (kd + 15), dtype=torch.float32, device=dev)
+    g_wcol, g_wsig = arena[:_N_WCOL], arena[_N_WCOL:_N_WCOL + _N_WSIG]
+    g_small = (g_wsig[:64 * 32].view(64, 32), g_wsig[64 * 32:].view(16, 64), arena[_N_WCOL + _N_WSIG:].view(64, kd + 15),
+               g_wcol[64 * 16:-16 * 64].view(64, 64), g_wcol[-16 * 64:].view(16, 64)[:2])
+    return arena, g_wcol, g_wsig, g_wcol[:64 * 16].view(64, 16), g_small
+
+
+def _hand_over_small(table_param, small_params, arena, g_small, dtypes):
+    """The five entries of a backward's return tuple for the small matrices."""
+    if small_params is not None and getattr(table_param, "_lnh_direct_small_grads", False):
+        # LidarTrainer's fused optimizer: the gradients are handed over as views of the arena (autograd's AccumulateGrad
+        # would copy each view into a tensor of its own: five launches), and the arena goes on the wire as ONE tensor
+        for p_, g_ in zip(small_params, g_small):
+            p_.grad = g_
+        table_param._lnh_small_arena = arena
+        return (None,) * 5
+    return tuple(g_.to(dt_) for g_, dt_ in zip(g_small, dtypes))
+
+
+def _hand_over_table(table_param, g_table16, master_dtype, handles=None):
+    """What a backward returns for the hash table, given its fp16 gradient (data parallel: the SUM over ranks; None with
+    the sharded optimizer, which has its rows in `_lnh_grad16_shards`) and the collectives still in flight on it."""
+    world = parallel.world_size()
+    if getattr(table_param, "_lnh_keep_grad16", False):
+        # the fused table optimizer consumes the fp16 gradient directly: no fp32 copy, no .grad on the table; it divides
+        # by `_lnh_grad16_div` in fp32.  It is the only consumer and waits right before its kernels (train_step.py), so the
+        # last window's bytes travel under the MLP gradients' all-reduce and the loss-scale bookkeeping instead of being
+        # waited for here, inside backward
+        if handles is not None:
+            table_param._lnh_grad16_handles = handles
+        table_param._lnh_grad16, table_param._lnh_grad16_div = g_table16, world
+        return None
+    for handle in handles or ():
+        handle.wait()
+    g_table = g_table16.to(master_dtype)
+    if world > 1:
+        g_table.div_(world)  # sum over ranks -> mean, after the widening
+    return g_table
+
+
+def _ragged_field(xyzs, rays, M, bound, enc, table16, wsig16, wcol16, cdir, mdt, x01, feat, h16, sigma, rgb):
+    """The field on the first M rows of the marcher's samples, into the caller's buffers (at least M rows each): grid
+    coordinates x01, hash features feat [L, M, 2], sigma-net rows h16 [M, 16] and densities sigma [M], colours rgb [M, 2]
+    of the rows a ray of the table `rays` owns (the others keep what the buffer held)."""
+    sfx, L = _hip.mlp_suffix(mdt), enc.num_levels
+    _hip.call("lnh_ragged_points", xyzs.data_ptr(), bound, M, x01.data_ptr())
+    _hip.call("lnh_grid_encode_forward", x01.data_ptr(), table16.data_ptr(), enc._offsets_host.data_ptr(), feat.data_ptr(),
+              M, 3, 2, L, enc.log2_scale, enc.base_resolution, None, enc.gridtype_id, 0, 0, _hip.LNH_F16, tag=M)
+    _hip.call("lnh_density_mlp_forward" + sfx, feat.data_ptr(), wsig16.data_ptr(), M, M, M, 0, 0, h16.data_ptr(),
+              sigma.data_ptr())
+    # colour head, one wave per ray of the marcher's table (round 5; before: a [M, 96] input assembled per sample, the
+    # generic 96 -> 64 -> 64 -> 16 MLP kernel and a sigmoid pass)
+    _hip.call("lnh_ragged_color_forward" + sfx, h16.data_ptr(), rays.data_ptr(), cdir.data_ptr(), wcol16.data_ptr(),
+              rays.shape[0], M, rgb.data_ptr())
+
+
 class FusedLidarRender(Function):
     @staticmethod
     @_no_autocast
     def forward(ctx, rays_o, rays_d, noise, u, embeddings, ws0, ws1, wc0, wc1, wc2, model, density_scale, spec, mdt, near,
                 far, T):
         # noise: [N*T] uniforms of the stratified perturbation, or None (evaluation)
-        # mdt: element type of everything MLP-side (packed weights, sigma-net rows, their gradients): torch.half, or
-        # torch.bfloat16 for the bf16-operand build of the kernels (config 5); hash features stay fp16 either way
+        # mdt: element type of everything MLP-side (packed weights, sigma-net rows, their gradients)
         sfx = _hip.mlp_suffix(mdt)
         enc = spec.grid
         kd = spec.n_dir
@@ -276,35 +380,32 @@ class FusedLidarRender(Function):
         # fp16 copy of the table: maintained by the fused table optimizer when there is one (train_step.LidarTrainer),
         # otherwise cast here (the autocast rule of grid.py:54-57)
         table16 = table16_of(spec.table_param, embeddings, model.training)
-        # fp32 master matrices (possibly strided views of flat parameter vectors) -> the flat fp16 vectors of the
-        # kernels, one launch: wsig16 = [ws0 | ws1]; wcol16 = [(0 | wc0[:, kd:kd+15]) | wc1 | wc2 padded to 16 rows]
-        wsig16 = torch.empty(64 * 32 + 16 * 64, dtype=mdt, device=dev)
-        wcol16 = torch.empty(64 * 16 + 64 * 64 + 16 * 64, dtype=mdt, device=dev)
-        mats = [m.detach() if m.dtype == torch.float32 and m.stride(-1) == 1 else m.detach().float().contiguous()
-                for m in (ws0, ws1, wc0, wc1, wc2)]
+        small = (ws0, ws1, wc0, wc1, wc2)
         # direction features [N, kd] (constant along a ray), rounded to the MLP element type (what the MLP would see), and
         # the per-ray direction term of the colour head's first layer
         enc_d16 = torch.empty((N, kd), dtype=torch.float32, device=dev)
         cdir = torch.empty((N, 64), dtype=torch.float32, device=dev)
         z = torch.empty((N, T), dtype=torch.float32, device=dev)
         x01 = torch.empty((N * Ttot, 3), dtype=torch.float32, device=dev)
-        deg = getattr(spec, "dir_freq_degree", None)
-        prologue = deg is not None and 3 + 6 * deg == kd
-        if prologue:
+        deg = spec.dir_freq_degree
+        if deg is not None and 3 + 6 * deg == kd:
             # weight packing + direction term (frequency encoder folded in) + the coarse pass (stratified depths and their
             # grid coordinates) in ONE launch
+            mats, wsig16, wcol16 = _weight_buffers(small, mdt, dev)
             _hip.call("lnh_lidar_step_prologue" + sfx, mats[0].data_ptr(), mats[0].stride(0), mats[1].data_ptr(),
                       mats[1].stride(0), mats[2].data_ptr(), mats[2].stride(0), int(deg), mats[3].data_ptr(), mats[3].stride(0),
                       mats[4].data_ptr(), mats[4].stride(0), wsig16.data_ptr(), wcol16.data_ptr(),
                       None if noise is None else noise.data_ptr(), rays_o.data_ptr(), rays_d.data_ptr(), aabb.data_ptr(), bound,
                       N, T, Ttot, float(near), float(far), z.data_ptr(), x01.data_ptr(), enc_d16.data_ptr(), cdir.data_ptr())
         else:
-            _hip.call("lnh_lidar_pack_weights" + sfx, mats[0].data_ptr(), mats[0].stride(0), mats[1].data_ptr(),
-                      mats[1].stride(0), mats[2].data_ptr(), mats[2].stride(0), kd, mats[3].data_ptr(), mats[3].stride(0),
-                      mats[4].data_ptr(), mats[4].stride(0), wsig16.data_ptr(), wcol16.data_ptr())
+            mats, wsig16, wcol16 = _pack_weights(small, kd, mdt, dev)
             enc_d = spec.dir_features(rays_d).contiguous()
             _hip.call("lnh_lidar_dir_term" + sfx, enc_d.data_ptr(), mats[2].data_ptr(), mats[2].stride(0), N, kd,
                       enc_d16.data_ptr(), cdir.data_ptr())
+            # coarse pass: the stratified depths and their grid coordinates in one launch
+            _hip.call("lnh_lidar_coarse_sample_points", None if noise is None else noise.data_ptr(), rays_o.data_ptr(),
+                      rays_d.data_ptr(), aabb.data_ptr(), bound, N, T, Ttot, float(near), float(far), z.data_ptr(),
+                      x01.data_ptr())
 
         h16 = torch.empty((N * Ttot, 16), dtype=mdt, device=dev)
         sigma_pt = torch.empty((N, Ttot), dtype=torch.float32, device=dev)
@@ -314,24 +415,15 @@ class FusedLidarRender(Function):
         L = enc.num_levels
         feat = torch.empty((L, B_all, 2), dtype=torch.half, device=dev)
 
-        def density(zz, Tc, off, have_points=False):
+        def density(Tc, off):  # (the prologue / coarse / resample kernel has written the coordinates of these samples)
             B = N * Tc
-            if have_points:  # (the prologue / the resample kernel has written the coordinates of these samples)
-                pass
-            elif zz is None:  # coarse pass: the stratified depths and their grid coordinates in one launch
-                _hip.call("lnh_lidar_coarse_sample_points", None if noise is None else noise.data_ptr(), rays_o.data_ptr(),
-                          rays_d.data_ptr(), aabb.data_ptr(), bound, N, Tc, Ttot, float(near), float(far), z.data_ptr(),
-                          x01.data_ptr())
-            else:
-                _hip.call("lnh_lidar_sample_points", rays_o.data_ptr(), rays_d.data_ptr(), zz.data_ptr(), aabb.data_ptr(),
-                          bound, N, Tc, Ttot, off, x01.data_ptr())
             _hip.call("lnh_grid_encode_forward_mapped_ex", x01.data_ptr(), table16.data_ptr(),
                       enc._offsets_host.data_ptr(), feat.data_ptr(), B, Tc, Ttot, off, B_all, 2, L, enc.log2_scale,
                       enc.base_resolution, enc.gridtype_id, _hip.LNH_F16, tag=B, timer="lnh_grid_encode_forward_mapped")
             _hip.call("lnh_density_mlp_forward" + sfx, feat.data_ptr(), wsig16.data_ptr(), B, Tc, Ttot, off, B_all,
                       h16.data_ptr(), sigma_pt.data_ptr())
 
-        density(None, T, 0, have_points=prologue)
+        density(T, 0)
         new_z = torch.empty((N, t_new), dtype=torch.float32, device=dev)
         z_all = torch.empty((N, Ttot), dtype=torch.float32, device=dev)
         perm = torch.empty((N, Ttot), dtype=torch.int32, device=dev)
@@ -340,7 +432,7 @@ class FusedLidarRender(Function):
         _hip.call("lnh_lidar_resample_points", z.data_ptr(), sigma_pt.data_ptr(), Ttot, sd.data_ptr(), u.data_ptr(), N, T,
                   t_new, float(density_scale), new_z.data_ptr(), z_all.data_ptr(), perm.data_ptr(), rays_o.data_ptr(),
                   rays_d.data_ptr(), aabb.data_ptr(), bound, x01.data_ptr())
-        density(new_z, t_new, T, have_points=True)
+        density(t_new, T)
         if CAPTURE is not None:
             CAPTURE.update(z=z, new_z=new_z, z_all=z_all, perm=perm)
 
@@ -365,14 +457,9 @@ class FusedLidarRender(Function):
                       N, Ttot, 2, float(density_scale), None, ws.data_ptr(), depth.data_ptr(), image.data_ptr())
 
         ctx.save_for_backward(x01, feat, h16, perm, weights, z_all, sigma_m, rgb, sd, cdir, enc_d16, wsig16, wcol16)
-        ctx.model, ctx.dims, ctx.density_scale, ctx.enc = model, (N, T, t_new), density_scale, enc
-        ctx.table_param, ctx.mdt = spec.table_param, mdt
-        ctx.param_dtypes = (embeddings.dtype, ws0.dtype, ws1.dtype, wc0.dtype, wc1.dtype, wc2.dtype)
-        # the five small matrices as the Parameters they are (network.NeRFNetwork) — or None when the field hands out views of
-        # flat parameter vectors (network_tcnn): LidarTrainer takes their gradients straight from this node's arena then
-        small = (ws0, ws1, wc0, wc1, wc2)
-        ctx.small_params = small if all(isinstance(w, torch.nn.Parameter) and w.dtype == torch.float32 and
-                                        w.is_contiguous() for w in small) else None
+        ctx.dims, ctx.density_scale, ctx.enc = (N, T, t_new), density_scale, enc
+        ctx.table_param, ctx.mdt, ctx.table_dtype = spec.table_param, mdt, embeddings.dtype
+        ctx.small_dtypes, ctx.small_params = _small_param_state(small)
         ctx.mark_non_differentiable(weights, z_all)
         # outputs the loss does not use (weights_sum in the LiDAR loss) arrive as None instead of a zero tensor filled
         # for the occasion; the compositing backward takes a null pointer for them
@@ -383,8 +470,8 @@ class FusedLidarRender(Function):
     @_no_autocast
     def backward(ctx, g_ws, g_depth, g_image, _gw, _gz):
         x01, feat, h16, perm, weights, z_all, sigma_m, rgb, sd, cdir, enc_d16, wsig16, wcol16 = ctx.saved_tensors
-        model, (N, T, t_new), ds = ctx.model, ctx.dims, ctx.density_scale
-        enc = ctx.enc
+        (N, T, t_new), ds = ctx.dims, ctx.density_scale
+        enc, table_param = ctx.enc, ctx.table_param
         dev = h16.device
         mdt, sfx = ctx.mdt, _hip.mlp_suffix(ctx.mdt)
         Ttot = T + t_new
@@ -403,76 +490,41 @@ class FusedLidarRender(Function):
         g_h16 = torch.empty((N * Ttot, 16), dtype=mdt, device=dev)
         wws = _hip.wgrad_ws(dev)  # scratch of the fixed-order weight-gradient sums (one per device and stream, kept)
         kd = enc_d16.shape[1]
-        n_col, n_sig, n_c0 = wcol16.numel(), wsig16.numel(), 64 * (kd + 15)
         # every gradient that is ACCUMULATED into (the small matrices' by the fixed-order sums, the table's by the reduce pass) is cleared
         # by one launch: the arena of all small gradients and — unless the sharded backward brings its own — the fp16 table
-        zeros = torch.empty(n_col + n_sig + n_c0, dtype=torch.float32, device=dev)
-        sharded = parallel.dp_active() and getattr(ctx.table_param, "_lnh_shard_optimizer", False)
+        arena, g_wcol, g_wsig, g_w0g, g_small = _small_grad_arena(kd, dev)
+        sharded = parallel.dp_active() and getattr(table_param, "_lnh_shard_optimizer", False)
         g_table16 = None if sharded else torch.empty((int(enc._offsets_host[-1]), 2), dtype=torch.half, device=dev)
         # ... and the cursors at the head of the table backward's workspace (its own clear launch is then skipped)
         bwd_ws, bwd_clear = _grid_bwd_workspace(dev, enc, N * Ttot)
         bwd_flags = 0 if sharded else (_hip.LNH_BWD_TABLE_ZERO | (_hip.LNH_BWD_WS_CLEARED if bwd_clear else 0))
-        _hip.zero_regions((zeros, g_table16, None if sharded or not bwd_clear else bwd_ws[:bwd_clear]))
-        g_wcol, g_wsig = zeros[:n_col], zeros[n_col:n_col + n_sig]
+        _hip.zero_regions((arena, g_table16, None if sharded or not bwd_clear else bwd_ws[:bwd_clear]))
         ray_sum = torch.empty((N, 64), dtype=torch.float32, device=dev)
         _hip.call("lnh_lidar_color_backward_image" + sfx, g_image.data_ptr(), g_sigma.data_ptr(), h16.data_ptr(), perm.data_ptr(),
                   weights.data_ptr(), cdir.data_ptr(), wcol16.data_ptr(), N, Ttot, g_h16.data_ptr(), g_wcol.data_ptr(),
                   ray_sum.data_ptr(), *wws)
-        g_w0g = g_wcol[:64 * 16].view(64, 16)
-        g_wc0 = zeros[n_col + n_sig:].view(64, kd + 15)
         # the whole gradient of the colour head's first matrix in one launch: direction columns = S^T enc(d), geo-feature
         # columns copied out of the packed [64, 16] block the colour backward accumulated
         _hip.call("lnh_lidar_dir_term_backward", ray_sum.data_ptr(), enc_d16.data_ptr(), N, kd, g_w0g.data_ptr(),
-                  g_wc0.data_ptr(), kd + 15, *wws)
-        g_wc1 = g_wcol[64 * 16:64 * 16 + 64 * 64].view(64, 64)
-        g_wc2 = g_wcol[64 * 16 + 64 * 64:].view(16, 64)[:2]
-        dts = ctx.param_dtypes
-        g_small = (g_wsig[:64 * 32].view(64, 32), g_wsig[64 * 32:].view(16, 64), g_wc0, g_wc1, g_wc2)
-        if ctx.small_params is not None and getattr(ctx.table_param, "_lnh_direct_small_grads", False):
-            # LidarTrainer's fused optimizer: the gradients are handed over as views of the arena (autograd's AccumulateGrad
-            # would copy each view into a tensor of its own: five launches), and the arena goes on the wire as ONE tensor
-            for p_, g_ in zip(ctx.small_params, g_small):
-                p_.grad = g_
-            ctx.table_param._lnh_small_arena = zeros
-            g_small = (None,) * 5
-        else:
-            g_small = tuple(g_.to(dt_) for g_, dt_ in zip(g_small, dts[1:]))
+                  g_small[2].data_ptr(), kd + 15, *wws)
+        # (ahead of the sigma net's backward, which still adds to g_wsig: what is handed over of an fp32 matrix is a view)
+        g_small = _hand_over_small(table_param, ctx.small_params, arena, g_small, ctx.small_dtypes)
 
         B_all = N * Ttot
         g_feat = torch.empty((enc.num_levels, B_all, 2), dtype=torch.half, device=dev)
         _hip.call("lnh_density_mlp_backward" + sfx, g_h16.data_ptr(), feat.data_ptr(), wsig16.data_ptr(), B_all, Ttot, Ttot, 0,
                   g_feat.data_ptr(), g_wsig.data_ptr(), *wws)
+        handles = None
         if sharded:
             # data parallel, sharded table optimizer: reduce-scatter per window; the trainer steps this rank's rows
-            ctx.table_param._lnh_grad16_shards = _grid_bwd_sharded(g_feat, x01, enc, B_all, ctx.table_param)
-            ctx.table_param._lnh_grad16_div = parallel.world_size()
-            ctx.table_param._lnh_grad16 = None
-            return (None, None, None, None, None) + g_small + (None,) * 7
-        if parallel.dp_active() or FORCE_DP_WINDOWS:
+            table_param._lnh_grad16_shards = _grid_bwd_sharded(g_feat, x01, enc, B_all, table_param)
+        elif parallel.dp_active() or FORCE_DP_WINDOWS:
             # data parallel: the table gradient goes on the wire as fp16, window by window, behind the kernels of the
             # following windows
-            handles = _grid_bwd_overlapped(g_feat, x01, g_table16, enc, B_all, ctx.table_param, bwd_ws, bwd_flags)
-            if getattr(ctx.table_param, "_lnh_keep_grad16", False):
-                # the fused table optimizer is the only consumer: it waits right before its kernels (train_step.py), so the
-                # last window's bytes travel under the MLP gradients' all-reduce and the loss-scale bookkeeping instead of
-                # being waited for here, inside backward
-                ctx.table_param._lnh_grad16_handles = handles
-            else:
-                for handle in handles:
-                    handle.wait()
+            handles = _grid_bwd_overlapped(g_feat, x01, g_table16, enc, B_all, table_param, bwd_ws, bwd_flags)
         else:
             _grid_bwd(g_feat, x01, g_table16, enc, B_all, bwd_ws, bwd_flags)
-        world = parallel.world_size()
-        if getattr(ctx.table_param, "_lnh_keep_grad16", False):
-            # the fused table optimizer consumes the fp16 gradient directly: no fp32 copy, no .grad on the table
-            # (data parallel: the gradient is the SUM over ranks; the optimizer divides by `_lnh_grad16_div` in fp32)
-            ctx.table_param._lnh_grad16 = g_table16
-            ctx.table_param._lnh_grad16_div = world
-            g_table = None
-        else:
-            g_table = g_table16.to(dts[0])
-            if world > 1:
-                g_table.div_(world)  # sum over ranks -> mean, after the widening
+        g_table = _hand_over_table(table_param, g_table16, ctx.table_dtype, handles)
         return (None, None, None, None, g_table) + g_small + (None,) * 7
 
 
@@ -537,56 +589,35 @@ class FusedLidarRagged(Function):
     @_no_autocast
     def forward(ctx, xyzs, dirs, deltas, rays, rays_o, rays_d, embeddings, ws0, ws1, wc0, wc1, wc2, model, spec, mdt,
                 T_thresh):
-        sfx = _hip.mlp_suffix(mdt)
         enc = spec.grid
         dev = xyzs.device
         M, N, L = xyzs.shape[0], rays.shape[0], enc.num_levels
-        bound, ds = float(model.bound), float(model.density_scale)
+        kd, ds = spec.n_dir, float(model.density_scale)
+        small = (ws0, ws1, wc0, wc1, wc2)
+        ctx.meta = (enc, spec.table_param, mdt, float(T_thresh), kd, ds, embeddings.dtype)
+        ctx.small_dtypes, ctx.small_params = _small_param_state(small)
+        ctx.empty = M == 0
+        ctx.set_materialize_grads(False)
         if M == 0:
             # The marcher found no sample (every ray misses the occupied cells).  The node still exists: its outputs are
             # zeros CONNECTED to the graph, and its backward hands out zero gradients and takes part in the gradient
             # exchange — under data parallel a rank that skipped the table all-reduce would leave the others waiting.
-            ctx.meta = (model, enc, spec.table_param, mdt, float(T_thresh), spec.n_dir, ds,
-                        (embeddings.dtype, ws0.dtype, ws1.dtype, wc0.dtype, wc1.dtype, wc2.dtype))
-            ctx.empty = True
-            ctx.shapes = (ws0.shape, ws1.shape, wc0.shape, wc1.shape, wc2.shape)
-            ctx.set_materialize_grads(False)
+            ctx.shapes = tuple(w.shape for w in small)
             z = torch.zeros(N, dtype=torch.float32, device=dev)
             return z, z.clone(), torch.zeros((N, 2), dtype=torch.float32, device=dev)
-        ctx.empty = False
         table16 = table16_of(spec.table_param, embeddings, model.training)
-        kd, deg = spec.n_dir, int(spec.dir_freq_degree)  # 75, 12
-        mats = [m.detach() if m.dtype == torch.float32 and m.stride(-1) == 1 else m.detach().float().contiguous()
-                for m in (ws0, ws1, wc0, wc1, wc2)]
-        # the dense chain's packing: wcol16 = [(0 | wc0[:, kd:kd+15]) | wc1 | wc2 padded to 16 rows] — the direction columns of
-        # the first matrix act once per RAY (cdir), a sample's colour input is its own 16-wide sigma-net row
-        wsig16 = torch.empty(64 * 32 + 16 * 64, dtype=mdt, device=dev)
-        wcol16 = torch.empty(64 * 16 + 64 * 64 + 16 * 64, dtype=mdt, device=dev)
-        _hip.call("lnh_lidar_pack_weights" + sfx, mats[0].data_ptr(), mats[0].stride(0), mats[1].data_ptr(),
-                  mats[1].stride(0), mats[2].data_ptr(), mats[2].stride(0), kd, mats[3].data_ptr(), mats[3].stride(0),
-                  mats[4].data_ptr(), mats[4].stride(0), wsig16.data_ptr(), wcol16.data_ptr())
-        enc_d16 = torch.empty((N, kd), dtype=torch.float32, device=dev)
-        cdir = torch.empty((N, 64), dtype=torch.float32, device=dev)
-        _hip.call("lnh_lidar_dir_term_freq" + sfx, rays_d.data_ptr(), deg, mats[2].data_ptr(), mats[2].stride(0), N,
-                  enc_d16.data_ptr(), cdir.data_ptr())
+        mats, wsig16, wcol16 = _pack_weights(small, kd, mdt, dev)
+        enc_d16, cdir = _dir_term_freq(rays_d, spec, mats[2], mdt)
         x01 = torch.empty((M, 3), dtype=torch.float32, device=dev)
-        _hip.call("lnh_ragged_points", xyzs.data_ptr(), bound, M, x01.data_ptr())
         feat = torch.empty((L, M, 2), dtype=torch.half, device=dev)
-        _hip.call("lnh_grid_encode_forward", x01.data_ptr(), table16.data_ptr(), enc._offsets_host.data_ptr(),
-                  feat.data_ptr(), M, 3, 2, L, enc.log2_scale, enc.base_resolution, None, enc.gridtype_id, 0, 0, _hip.LNH_F16, tag=M)
         h16 = torch.empty((M, 16), dtype=mdt, device=dev)
         sigma = torch.empty(M, dtype=torch.float32, device=dev)
-        _hip.call("lnh_density_mlp_forward" + sfx, feat.data_ptr(), wsig16.data_ptr(), M, M, M, 0, 0, h16.data_ptr(),
-                  sigma.data_ptr())
-        # colour head, one wave per ray of the marcher's table (round 5; before: a [M, 96] input assembled per sample, the
-        # generic 96 -> 64 -> 64 -> 16 MLP kernel and a sigmoid pass)
-        # (rows no ray owns stay 0.)  run_cuda hands over rows its prologue launch has already cleared
+        # (colour rows no ray owns stay 0.)  run_cuda hands over rows its prologue launch has already cleared
         rgb = getattr(model, "_lnh_rgb_rows", None)
         model._lnh_rgb_rows = None
         if rgb is None or rgb.shape != (M, 2) or rgb.device != dev or rgb.dtype != torch.float32:
             rgb = torch.zeros((M, 2), dtype=torch.float32, device=dev)
-        _hip.call("lnh_ragged_color_forward" + sfx, h16.data_ptr(), rays.data_ptr(), cdir.data_ptr(), wcol16.data_ptr(), N, M,
-                  rgb.data_ptr())
+        _ragged_field(xyzs, rays, M, float(model.bound), enc, table16, wsig16, wcol16, cdir, mdt, x01, feat, h16, sigma, rgb)
         sig_s = sigma * ds if ds != 1.0 else sigma
         ws = torch.empty(N, dtype=torch.float32, device=dev)
         depth = torch.empty(N, dtype=torch.float32, device=dev)
@@ -596,38 +627,21 @@ class FusedLidarRagged(Function):
                   ws.data_ptr(), depth.data_ptr(), image.data_ptr())
         ctx.save_for_backward(x01, feat, h16, sig_s, cdir, enc_d16, rgb, deltas, xyzs, rays_o, rays_d, rays, ws, depth, image,
                               wsig16, wcol16)
-        ctx.meta = (model, enc, spec.table_param, mdt, float(T_thresh), kd, ds,
-                    (embeddings.dtype, ws0.dtype, ws1.dtype, wc0.dtype, wc1.dtype, wc2.dtype))
-        small = (ws0, ws1, wc0, wc1, wc2)
-        ctx.small_params = small if all(isinstance(w, torch.nn.Parameter) and w.dtype == torch.float32 and
-                                        w.is_contiguous() for w in small) else None
-        ctx.set_materialize_grads(False)
         return ws, depth, image
 
     @staticmethod
     @_no_autocast
     def backward(ctx, g_ws, g_depth, g_image):
-        model, enc, table_param, mdt, T_thresh, kd, ds, dts = ctx.meta
+        enc, table_param, mdt, T_thresh, kd, ds, table_dtype = ctx.meta
         if ctx.empty:  # no sample: zero gradients, but the same collectives as every other rank
             dev = table_param.device
             g_table16 = torch.zeros((int(enc._offsets_host[-1]), 2), dtype=torch.half, device=dev)
-            world = parallel.world_size()
             if parallel.dp_active():
-                off = enc._offsets_host
-                handles = []
-                for l0, l1 in (_DP_LEVEL_WINDOWS if enc.num_levels == 16 else ((0, enc.num_levels),)):
-                    h = parallel.allreduce_half_table(g_table16[int(off[l0]):int(off[l1])], table_param)
-                    if h is not None:
-                        handles.append(h)
-                for h in handles:
-                    h.wait()
-            if getattr(table_param, "_lnh_keep_grad16", False):
-                table_param._lnh_grad16, table_param._lnh_grad16_div = g_table16, world
-                g_table = None
-            else:
-                g_table = g_table16.to(dts[0])
-            zw = [torch.zeros(sh, dtype=dt, device=dev) for sh, dt in zip(ctx.shapes, dts[1:])]
-            return (None, None, None, None, None, None, g_table, zw[0], zw[1], zw[2], zw[3], zw[4], None, None, None, None)
+                for handle in _allreduce_windows(_level_windows(enc), g_table16, enc, table_param):
+                    handle.wait()
+            g_table = _hand_over_table(table_param, g_table16, table_dtype)
+            zw = tuple(torch.zeros(sh, dtype=dt, device=dev) for sh, dt in zip(ctx.shapes, ctx.small_dtypes))
+            return (None, None, None, None, None, None, g_table) + zw + (None, None, None, None)
         (x01, feat, h16, sig_s, cdir, enc_d16, rgb, deltas, xyzs, rays_o, rays_d, rays, ws, depth, image, wsig16,
          wcol16) = ctx.saved_tensors
         sfx = _hip.mlp_suffix(mdt)
@@ -639,55 +653,35 @@ class FusedLidarRagged(Function):
         # gradient (rows no ray owns), the per-ray sums, the small matrices' gradients, the fp16 table gradient, the cursors
         # of the table backward — cleared by ONE launch
         gsf = torch.empty(M * 3, dtype=torch.float32, device=dev)
-        n_col, n_sig, n_c0 = wcol16.numel(), wsig16.numel(), 64 * (kd + 15)
-        zeros = torch.empty(n_col + n_sig + n_c0, dtype=torch.float32, device=dev)
+        arena, g_wcol, g_wsig, g_w0g, g_small = _small_grad_arena(kd, dev)
         g_table16 = torch.empty((int(enc._offsets_host[-1]), 2), dtype=torch.half, device=dev)
         g_h16 = torch.empty((M, 16), dtype=mdt, device=dev)
         ray_sum = torch.empty((N, 64), dtype=torch.float32, device=dev)
         bwd_ws, bwd_clear = _grid_bwd_workspace(dev, enc, M)
         bwd_flags = _hip.LNH_BWD_TABLE_ZERO | (_hip.LNH_BWD_WS_CLEARED if bwd_clear else 0)
-        _hip.zero_regions((gsf, zeros, g_table16, g_h16, ray_sum, bwd_ws[:bwd_clear] if bwd_clear else None))
+        _hip.zero_regions((gsf, arena, g_table16, g_h16, ray_sum, bwd_ws[:bwd_clear] if bwd_clear else None))
         gs, gf = gsf[:M], gsf[M:].view(M, 2)
         _hip.call("lnh_lidar_composite_rays_train_backward", g_ws.data_ptr(), g_depth.data_ptr(), g_image.data_ptr(),
                   sig_s.data_ptr(), rgb.data_ptr(), deltas.data_ptr(), xyzs.data_ptr(), rays_o.data_ptr(),
                   rays_d.data_ptr(), rays.data_ptr(), ws.data_ptr(), depth.data_ptr(), image.data_ptr(), M, N, 2,
                   T_thresh, gs.data_ptr(), gf.data_ptr())
-        g_wcol, g_wsig = zeros[:n_col], zeros[n_col:n_col + n_sig]
         wws = _hip.wgrad_ws(dev)
         # colour head backward ray by ray: sigmoid, the three layers, all weight gradients, the sigma-net rows' gradient
         # (col 0 = the density gradient through trunc_exp) and the per-ray sum for the direction columns — one launch
         _hip.call("lnh_ragged_color_backward" + sfx, gf.data_ptr(), gs.data_ptr(), ds, h16.data_ptr(), rays.data_ptr(),
                   cdir.data_ptr(), wcol16.data_ptr(), N, M, g_h16.data_ptr(), g_wcol.data_ptr(), ray_sum.data_ptr(), *wws)
-        g_w0g = g_wcol[:64 * 16].view(64, 16)
-        g_wc0 = zeros[n_col + n_sig:].view(64, kd + 15)
         _hip.call("lnh_lidar_dir_term_backward", ray_sum.data_ptr(), enc_d16.data_ptr(), N, kd, g_w0g.data_ptr(),
-                  g_wc0.data_ptr(), kd + 15, *wws)
-        g_wc1 = g_wcol[64 * 16:64 * 16 + 64 * 64].view(64, 64)
-        g_wc2 = g_wcol[64 * 16 + 64 * 64:].view(16, 64)[:2]
+                  g_small[2].data_ptr(), kd + 15, *wws)
         g_feat = torch.empty((L, M, 2), dtype=torch.half, device=dev)
         _hip.call("lnh_density_mlp_backward" + sfx, g_h16.data_ptr(), feat.data_ptr(), wsig16.data_ptr(), M, M, M, 0,
                   g_feat.data_ptr(), g_wsig.data_ptr(), *wws)
-        world = parallel.world_size()
         if parallel.dp_active():
             for handle in _grid_bwd_overlapped(g_feat, x01, g_table16, enc, M, table_param, bwd_ws, bwd_flags):
                 handle.wait()
         else:
             _grid_bwd(g_feat, x01, g_table16, enc, M, bwd_ws, bwd_flags)
-        if getattr(table_param, "_lnh_keep_grad16", False):
-            table_param._lnh_grad16, table_param._lnh_grad16_div = g_table16, world
-            g_table = None
-        else:
-            g_table = g_table16.to(dts[0])
-            if world > 1:
-                g_table.div_(world)
-        g_small = (g_wsig[:64 * 32].view(64, 32), g_wsig[64 * 32:].view(16, 64), g_wc0, g_wc1, g_wc2)
-        if ctx.small_params is not None and getattr(table_param, "_lnh_direct_small_grads", False):
-            for p_, g_ in zip(ctx.small_params, g_small):  # (see FusedLidarRender.backward)
-                p_.grad = g_
-            table_param._lnh_small_arena = zeros
-            g_small = (None,) * 5
-        else:
-            g_small = tuple(g_.to(dt_) for g_, dt_ in zip(g_small, dts[1:]))
+        g_table = _hand_over_table(table_param, g_table16, table_dtype)
+        g_small = _hand_over_small(table_param, ctx.small_params, arena, g_small, ctx.small_dtypes)
         return (None, None, None, None, None, None, g_table) + g_small + (None, None, None, None)
 
 
@@ -700,7 +694,7 @@ def ragged_supported(model):
     # gridtype 0 only: the tcnn-shaped field renders without cuda_ray (as the reference's -L run does), and this chain is
     # not verified on tiny-cuda-nn's lattice (gridtype 2) — such a model takes the modular occupancy path (the grid
     # encoder's own HIP kernels, which serve every gridtype) instead
-    return supported(model, True, 16, 16) and sp.grid.gridtype_id == 0 and getattr(sp, "dir_freq_degree", None) is not None \
+    return supported(model, True, 16, 16) and sp.grid.gridtype_id == 0 and sp.dir_freq_degree is not None \
         and 3 + 6 * sp.dir_freq_degree == sp.n_dir and sp.n_dir + 15 <= 96
 
 
@@ -716,9 +710,9 @@ def render_lidar_ragged(model, xyzs, dirs, deltas, rays, rays_o, rays_d, T_thres
 class RaggedEvalField:
     """The field half of FusedLidarRagged.forward for the alive-ray evaluation loop (renderer.run_cuda_alive), no autograd:
     what does not change between the rounds of a call — the fp16 table, the packed weights, the per-ray direction term —
-    is made once, the per-sample buffers are allocated once for `rows` samples and reused; a round is lnh_ragged_points ->
-    lnh_grid_encode_forward -> lnh_density_mlp_forward -> lnh_ragged_color_forward on the marcher's table.  The same kernels
-    per sample as the existing evaluation, so a sample's sigma and colour carry the same bits on both paths."""
+    is made once, the per-sample buffers are allocated once for `rows` samples and reused; a round is one _ragged_field on
+    the marcher's table — the very function the training chain calls, so a sample's sigma and colour carry the same bits on
+    both paths."""
 
     def __init__(self, model, rays_d, rows):
         from ..ffmlp.ffmlp import mlp_dtype
@@ -727,25 +721,13 @@ class RaggedEvalField:
     @_no_autocast
     def _setup(self, model, rays_d, rows, mdt):
         sp = model.fused_spec()
-        self.mdt = mdt
-        self.sfx = sfx = _hip.mlp_suffix(mdt)
-        self.enc = enc = sp.grid
+        self.mdt, self.enc = mdt, sp.grid
         self.bound, self.ds = float(model.bound), float(model.density_scale)
-        dev, N, L = rays_d.device, rays_d.shape[0], enc.num_levels
+        dev, L = rays_d.device, sp.grid.num_levels
         self.table16 = table16_of(sp.table_param, sp.table, False)
-        kd, deg = sp.n_dir, int(sp.dir_freq_degree)
-        mats = [m.detach() if m.dtype == torch.float32 and m.stride(-1) == 1 else m.detach().float().contiguous()
-                for m in (sp.ws0, sp.ws1, sp.wc0, sp.wc1, sp.wc2)]
-        self.wsig16 = torch.empty(64 * 32 + 16 * 64, dtype=mdt, device=dev)
-        self.wcol16 = torch.empty(64 * 16 + 64 * 64 + 16 * 64, dtype=mdt, device=dev)
-        _hip.call("lnh_lidar_pack_weights" + sfx, mats[0].data_ptr(), mats[0].stride(0), mats[1].data_ptr(),
-                  mats[1].stride(0), mats[2].data_ptr(), mats[2].stride(0), kd, mats[3].data_ptr(), mats[3].stride(0),
-                  mats[4].data_ptr(), mats[4].stride(0), self.wsig16.data_ptr(), self.wcol16.data_ptr())
-        enc_d16 = torch.empty((N, kd), dtype=torch.float32, device=dev)
-        self.cdir = torch.empty((N, 64), dtype=torch.float32, device=dev)
-        _hip.call("lnh_lidar_dir_term_freq" + sfx, rays_d.data_ptr(), deg, mats[2].data_ptr(), mats[2].stride(0), N,
-                  enc_d16.data_ptr(), self.cdir.data_ptr())
-        self.N, self.rows = N, rows
+        mats, self.wsig16, self.wcol16 = _pack_weights((sp.ws0, sp.ws1, sp.wc0, sp.wc1, sp.wc2), sp.n_dir, mdt, dev)
+        _, self.cdir = _dir_term_freq(rays_d, sp, mats[2], mdt)
+        self.N, self.rows = rays_d.shape[0], rows
         self.x01 = torch.empty(rows * 3, dtype=torch.float32, device=dev)
         self.feat = torch.empty(L * rows * 2, dtype=torch.half, device=dev)
         self.h16 = torch.empty(rows * 16, dtype=mdt, device=dev)
@@ -758,14 +740,7 @@ class RaggedEvalField:
         keep stale values (the compositor reads owned rows only)."""
         if M > self.rows or rays.shape[0] != self.N:
             raise RuntimeError("RaggedEvalField: more samples than the buffers were sized for, or another ray table")
-        enc, sfx, L = self.enc, self.sfx, self.enc.num_levels
-        _hip.call("lnh_ragged_points", xyzs.data_ptr(), self.bound, M, self.x01.data_ptr())
-        _hip.call("lnh_grid_encode_forward", self.x01.data_ptr(), self.table16.data_ptr(), enc._offsets_host.data_ptr(),
-                  self.feat.data_ptr(), M, 3, 2, L, enc.log2_scale, enc.base_resolution, None, enc.gridtype_id, 0, 0,
-                  _hip.LNH_F16, tag=M)
-        _hip.call("lnh_density_mlp_forward" + sfx, self.feat.data_ptr(), self.wsig16.data_ptr(), M, M, M, 0, 0,
-                  self.h16.data_ptr(), self.sigma.data_ptr())
-        _hip.call("lnh_ragged_color_forward" + sfx, self.h16.data_ptr(), rays.data_ptr(), self.cdir.data_ptr(),
-                  self.wcol16.data_ptr(), self.N, M, self.rgb.data_ptr())
+        _ragged_field(xyzs, rays, M, self.bound, self.enc, self.table16, self.wsig16, self.wcol16, self.cdir, self.mdt,
+                      self.x01, self.feat, self.h16, self.sigma, self.rgb)
         sigma = self.sigma[:M]
         return (sigma * self.ds if self.ds != 1.0 else sigma), self.rgb[:M * 2].view(M, 2)

@@ -445,7 +445,7 @@ class LidarTrainer:
             rank = dist.get_rank()
             for i, (r0, r1, mine, handle, _padded) in enumerate(shards):
                 handle.wait()
-                rows = max(0, min(mine.shape[0], r1 - (r0 + rank * mine.shape[0])))
+                rows = parallel.rank_rows(r0, r1, mine.shape[0], rank)[1]
                 check(mine.data_ptr() if rows else None, rows * 2, i == 0)
             # every rank has looked at its own rows only: the skip / back-off decision must be the same everywhere (the stamp
             # of a step is the same number on every rank, so MAX keeps it)
@@ -608,9 +608,7 @@ class LidarTrainer:
         flat16, table16 = shadow.view(-1), shadow.view(-1, 2)
         gathers = []
         for r0, r1, mine, _h, padded in shards:
-            s = mine.shape[0]
-            row0 = r0 + rank * s
-            rows = max(0, min(s, r1 - row0))
+            row0, rows = parallel.rank_rows(r0, r1, mine.shape[0], rank)
             if rows:
                 o = row0 * 2  # element offset of the shard in the [rows, 2] table
                 _hip.call("lnh_adam_table_step_dlr", tp.data_ptr() + 4 * o, self.t_m.data_ptr() + 4 * o,
@@ -635,18 +633,16 @@ class LidarTrainer:
         if not self.sharded:
             return
         import torch.distributed as dist
-        from .fused import _DP_LEVEL_WINDOWS
+        from .fused import _level_windows
         enc = self.model.fused_spec().grid
         off, world, rank = enc._offsets_host, dist.get_world_size(), dist.get_rank()
-        windows = _DP_LEVEL_WINDOWS if enc.num_levels == 16 else ((0, enc.num_levels),)
         for t in (self.table.data, self.t_m, self.t_v):
             rows = t.view(-1, 2)
-            for l0, l1 in windows:
+            for l0, l1 in _level_windows(enc):
                 r0, r1 = int(off[l0]), int(off[l1])
                 s = parallel.shard_rows(r1 - r0, world)
                 mine = torch.zeros((s, 2), dtype=t.dtype, device=t.device)
-                a = r0 + rank * s
-                n = max(0, min(s, r1 - a))
+                a, n = parallel.rank_rows(r0, r1, s, rank)
                 if n:
                     mine[:n] = rows[a:a + n]
                 full = torch.empty((world * s, 2), dtype=t.dtype, device=t.device)

@@ -120,6 +120,13 @@ def shard_rows(n_rows, world, align=4):
     return (per + align - 1) // align * align
 
 
+def rank_rows(r0, r1, s, rank):
+    """(first row, row count) of what `rank` holds of the table rows [r0, r1) dealt out in shards of `s` rows
+    (s = shard_rows(r1 - r0, world)): the shard is cut at r1, and a shard that is padding only has no rows."""
+    row0 = r0 + rank * s
+    return row0, max(0, min(s, r1 - row0))
+
+
 def reduce_scatter_half(padded, out_shard):
     """SUM-reduce `padded` [world * s, 2] fp16 over ranks and leave rows [rank * s, (rank + 1) * s) in `out_shard`
     (async handle).  fp16 on the wire, sum-then-divide like allreduce_half_table."""

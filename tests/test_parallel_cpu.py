@@ -58,6 +58,8 @@ def _worker(rank, world, port, out):
     assert parallel.shard_rows(4920, 2) == 2460 and parallel.shard_rows(4921, 2) == 2464 and parallel.shard_rows(10, 8) == 4
     n_rows = 13                                               # a "window" of 13 rows: shards of 8 rows, 3 rows of padding
     s = parallel.shard_rows(n_rows, world)
+    assert parallel.rank_rows(100, 113, s, 0) == (100, 8) and parallel.rank_rows(100, 113, s, 1) == (108, 5)
+    assert parallel.rank_rows(0, 10, 4, 2) == (8, 2) and parallel.rank_rows(0, 10, 4, 3) == (12, 0)   # cut / padding only
     padded = torch.zeros((world * s, 2), dtype=torch.float16)
     padded[:n_rows] = torch.arange(n_rows * 2, dtype=torch.float16).view(n_rows, 2) * (rank + 1)
     mine = torch.empty((s, 2), dtype=torch.float16)
@@ -130,6 +132,7 @@ def _worker_layout8(rank, world, port, out):
         parallel.reduce_scatter_half(padded, mine).wait()
         a = r0 + rank * s
         n = max(0, min(s, r1 - a))
+        assert parallel.rank_rows(r0, r1, s, rank) == (a, n)
         torch.testing.assert_close(mine[:n].float(), total[a:a + n], rtol=0, atol=0)
         assert float(mine[n:].abs().max()) == 0.0 if n < s else True            # beyond the window: padding
         covered += n
