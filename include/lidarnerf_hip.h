@@ -760,6 +760,25 @@ LNH_API int lnh_train_step(float *state, float *param, float *exp_avg, float *ex
                            uint32_t growth_interval, lnh_stream_t stream);
 LNH_API int lnh_zero_regions(void *const *ptrs, const uint64_t *bytes, uint32_t count, lnh_stream_t stream);
 
+/* ---- exponential moving average of the parameters (nerf/utils.py:619-624, 1257-1258, 1297-1299, 1444-1445: torch_ema's
+ * ExponentialMovingAverage over model.parameters(), update() per epoch, the averaged weights swapped in for evaluation).
+ * Like lnh_train_step ONE launch covers the fp32 table (n values; n = 0: no table, its pointers may be null) and
+ * n_small <= LNH_TRAIN_MAX_SMALL fp32 tensors (host arrays of device pointers and element counts, 4-byte aligned).
+ * lnh_ema_update: for every element, in fp32, three separately rounded operations in torch_ema's order:
+ *   tmp = shadow - param;  tmp = tmp * one_minus_decay;  shadow = shadow - tmp
+ *   — bit-identical to those three torch operations on fp32 tensors (no fused multiply-add).  one_minus_decay in [0, 1] is
+ *   formed by the host (torch_ema: 1 - min(decay, (1 + num_updates) / (10 + num_updates)) in double, then rounded to float).
+ * lnh_ema_swap: exchanges param and shadow in place; for the table it also writes param16[i] = (half)param_new[i] in the
+ *   same pass (param16 null: no fp16 compute copy is kept).  Applied twice it is the identity, bit for bit: it replaces
+ *   torch_ema's store() + copy_to() before an evaluation and restore() after it without a third copy of the parameters.
+ * Table buffers: 16-byte (fp32) / 8-byte (fp16) aligned; param and shadow must not alias.
+ */
+LNH_API int lnh_ema_update(float *shadow, const float *param, uint64_t n, float *const *small_shadow,
+                           const float *const *small_param, const uint32_t *small_numel, uint32_t n_small,
+                           float one_minus_decay, lnh_stream_t stream);
+LNH_API int lnh_ema_swap(float *param, float *shadow, void *param16, uint64_t n, float *const *small_param,
+                         float *const *small_shadow, const uint32_t *small_numel, uint32_t n_small, lnh_stream_t stream);
+
 
 /* ------------------------------------------------------------------ bf16 MLP operands (BASELINE config 5) ---- */
 /*

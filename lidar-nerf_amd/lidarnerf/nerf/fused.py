@@ -199,10 +199,14 @@ def table16_of(param, embeddings=None, training=True):
     torch version counter, so a write to the parameter through torch (load_state_dict, parallel.broadcast_parameters, a
     manual re-initialisation under no_grad) is noticed here and the shadow is re-cast.  Writes through `.data` (torch_ema's
     copy_to / restore) do not move the version counter: evaluation (`training=False`) therefore never trusts the shadow
-    and casts the parameter as it is — 82 MB of traffic per render call, noise next to the render itself.  Without a
+    and casts the parameter as it is — 82 MB of traffic per render call, noise next to the render itself — except inside
+    LidarTrainer.ema_weights(), whose swap kernel writes parameter and shadow together and marks the parameter.  Without a
     shadow the table is cast per call (the autocast rule of grid.py:54-57)."""
     src = param if embeddings is None else embeddings
     shadow = getattr(param, "_lnh_table16", None)
+    if shadow is not None and not training and getattr(param, "_lnh_ema_weights", False):
+        # inside LidarTrainer.ema_weights(): lnh_ema_swap has written the shadow together with the parameter
+        return shadow
     if shadow is not None and getattr(param, "_lnh_shard_optimizer", False):
         # sharded table optimizer: the fp32 master of this rank is current on its own rows only; the all-gathered shadow
         # IS the table (LidarTrainer.gather_table_state() completes the master for checkpoints).  A write to the parameter

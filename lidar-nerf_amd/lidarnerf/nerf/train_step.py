@@ -2,6 +2,7 @@
 of train_one_epoch (1206-1226): zero_grad -> autocast(render + loss) -> scaled backward -> [DP all-reduce] ->
 scaler.step(optimizer) -> scaler.update() -> lr_scheduler.step().  Only the LiDAR branch exists in the reference
 path (opt.enable_lidar is forced True, main_lidarnerf.py:229)."""
+import contextlib
 import dataclasses
 import os
 
@@ -233,7 +234,8 @@ _LADDER_RUNGS_PER_OCTAVE = int(os.environ.get("LNH_GRAPH_LADDER", "8"))
 
 
 class LidarTrainer:
-    """The hot loop only (no logging / checkpoint / EMA: those are host glue outside the path).
+    """The hot loop, the checkpoints in the reference Trainer's layout and — `ema_decay` — the exponential moving average
+    of the parameters the reference evaluates on (no logging: that is host glue outside the path).
 
     fused_table_optimizer (default on for fp16 + a fusable field on the GPU): the 13.7 M-parameter hash table — 99.8 %
     of all parameters — leaves torch.optim.Adam / GradScaler and is stepped by ONE kernel (lnh_adam_table_step) that
@@ -243,7 +245,8 @@ class LidarTrainer:
 
     def __init__(self, model, lr=1e-2, iters=30000, fp16=True, alpha_d=1000.0, alpha_r=1.0, alpha_i=10.0,
                  alpha_grad=100.0, scale=1.0, world_size=1, render_kwargs=None, fused_table_optimizer=True,
-                 mlp_dtype=torch.float16, shard_table_optimizer=False, graph=False, loss_options=None):
+                 mlp_dtype=torch.float16, shard_table_optimizer=False, graph=False, loss_options=None, ema_decay=None,
+                 ema_interval=None):
         # mlp_dtype: the autocast dtype — torch.float16 (the reference's --fp16) or torch.bfloat16 (BASELINE config 5:
         # bf16 MFMA MLPs; the hash table and its gradient stay fp16, so the dynamic loss scale is kept either way)
         # (the backward picks reduce-scatter or all-reduce from the process group, parallel.world_size(): a world_size
@@ -354,6 +357,20 @@ class LidarTrainer:
         self.scheduler = torch.optim.lr_scheduler.LambdaLR(self.optimizer, lambda it: 0.1 ** min(it / iters, 1))
         self.scaler = torch.amp.GradScaler("cuda", enabled=fp16)
         self.params = [p for g in self.optimizer.param_groups for p in g["params"]]
+        # ema_decay (the reference: 0.95, main_lidarnerf.py:431): a ParameterEMA (nerf/ema.py) over model.parameters(), in
+        # that order, as nerf/utils.py:619-624 builds torch_ema's.  None (the default): no buffer, no launch, no checkpoint
+        # key.  ema_update() is the public call — the reference's cadence is once per epoch, the caller's loop decides;
+        # ema_interval=N makes step() call it after every N-th step (after the replay, outside any captured graph).
+        self.ema, self.ema_interval = None, None
+        if ema_interval is not None:
+            if ema_decay is None:
+                raise ValueError("LidarTrainer(ema_interval=) needs ema_decay")
+            if int(ema_interval) != ema_interval or ema_interval < 1:
+                raise ValueError(f"LidarTrainer(ema_interval={ema_interval!r}): a positive number of steps")
+            self.ema_interval = int(ema_interval)
+        if ema_decay is not None:
+            from .ema import ParameterEMA
+            self.ema = ParameterEMA(model.parameters(), float(ema_decay))
 
     @staticmethod
     def _ragged_chain(model):
@@ -650,6 +667,47 @@ class LidarTrainer:
                 rows[r0:r1] = full[:r1 - r0]
         self.table._lnh_master_stale = False
 
+    # ---- exponential moving average of the parameters (ema_decay; the reference's self.ema, nerf/utils.py:619-624)
+    def _require_ema(self, what):
+        if self.ema is None:
+            raise RuntimeError(f"LidarTrainer.{what}: this trainer keeps no parameter average (construct it with ema_decay=)")
+
+    def ema_update(self):
+        """One averaging step (the reference: once per epoch, utils.py:1257-1258).  On the GPU one lnh_ema_update launch on
+        the current stream; never from inside a capture.  Sharded table optimizer: COLLECTIVE (gather_table_state: a rank's
+        fp32 master is current on its own rows only) — call it on every rank.  Non-sharded data parallel needs no
+        communication: every rank holds the same parameters and forms the same average."""
+        self._require_ema("ema_update()")
+        self.gather_table_state()
+        self.ema.update()
+
+    def _ema_swap(self):
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("LidarTrainer: the averaged weights cannot be swapped while a stream is capturing")
+        self.ema.swap()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Context manager: the model carries the averaged weights inside (the reference evaluates on them, utils.py:
+        1297-1299 / 1444-1445) and its own again outside, also after an exception.  Each way is ONE lnh_ema_swap launch on
+        the current stream that exchanges parameters and shadows in place and, with the fused table optimizer, rewrites the
+        persistent fp16 copy of the table in the same pass; inside, fused.table16_of(..., training=False) returns that copy
+        instead of re-casting the table per render call.  Nothing moves a version counter or a pointer: the captured steps
+        (graph=True) stay valid.  Do not step inside.  Sharded table optimizer: entering is COLLECTIVE (gather_table_state)
+        — enter it on every rank."""
+        self._require_ema("ema_weights()")
+        self.gather_table_state()
+        self._ema_swap()
+        tp = self.table
+        if tp is not None:
+            tp._lnh_ema_weights = True
+        try:
+            yield self.ema
+        finally:
+            if tp is not None:
+                del tp._lnh_ema_weights
+            self._ema_swap()
+
     # ---- what lives outside torch.optim / GradScaler when the table is stepped by the fused kernel
     def table_grad(self):
         """fp32, unscaled gradient of the hash table of the LAST step (the fused path keeps it in fp16 and never sets
@@ -667,7 +725,8 @@ class LidarTrainer:
 
     def state_dict(self):
         """Everything a resume needs: torch optimizer / scheduler / scaler state plus — fused table optimizer — the
-        table's Adam moments, its device-side step counter and the dynamic loss scale (99.8 % of the optimizer state).
+        table's Adam moments, its device-side step counter and the dynamic loss scale (99.8 % of the optimizer state) and
+        — a trainer with ema_decay — the parameter average under "ema" (absent otherwise).
         Sharded table optimizer: COLLECTIVE (gather_table_state) — call it on every rank."""
         self.gather_table_state()
         sd = {"optimizer": self.optimizer.state_dict(), "scheduler": self.scheduler.state_dict(),
@@ -678,6 +737,8 @@ class LidarTrainer:
                                  # the small tensors' moments, back to back in the order of self.small
                                  "small_exp_avg": self.small_m, "small_exp_avg_sq": self.small_v,
                                  "small_stepped": [id(p) in self._small_stepped for p in self.small]}
+        if self.ema is not None:
+            sd["ema"] = self.ema.state_dict()
         return sd
 
     def load_state_dict(self, sd):
@@ -699,6 +760,8 @@ class LidarTrainer:
                 self.small_v.copy_(ft["small_exp_avg_sq"])
                 self._small_stepped = {id(p) for p, f in zip(self.small, ft["small_stepped"]) if f}
             self._sync_counters(steps=float(ft["step"]))
+        if self.ema is not None and sd.get("ema") is not None:
+            self.ema.load_state_dict(sd["ema"])
 
     # ---- checkpoints in the reference Trainer's format (lidarnerf/nerf/utils.py:1449-1568)
     def _optimizer_state_ref_layout(self):
@@ -825,7 +888,7 @@ class LidarTrainer:
             sd[key] = [first.get(i, vals[0]) for i in range(n_own)]
         self.scheduler.load_state_dict(sd)
 
-    def save_checkpoint(self, path, full=True, gather=True):
+    def save_checkpoint(self, path, full=True, gather=True, ema_model=False):
         """Same dictionary as Trainer.save_checkpoint (utils.py:1449-1480): epoch, global_step, stats, model and — `full`
         — optimizer / lr_scheduler / scaler in the layout the reference's Trainer.load_checkpoint restores (a reference
         run can resume from it and vice versa: the state dict keys of the model are the reference's, see network.py).
@@ -836,7 +899,13 @@ class LidarTrainer:
             return the path without touching it); a call on rank 0 only would wait for the others forever;
           * the reference's convention, save on local_rank 0 only (utils.py:1069-1074): call gather_table_state() on every
             rank first, then save_checkpoint(path, gather=False) where the reference saves.  Without the gather that
-            raises instead of writing a table with other ranks' stale rows."""
+            raises instead of writing a table with other ranks' stale rows.
+
+        A trainer with ema_decay writes the parameter average under "ema" (`full`; utils.py:1463-1464), in torch_ema's
+        state-dict layout.  ema_model=True: "model" is the state dict under the AVERAGED weights (swapped in for the
+        state_dict() call and back out) — what the reference's best=True checkpoint holds (utils.py:1492-1504)."""
+        if ema_model:
+            self._require_ema("save_checkpoint(ema_model=True)")
         write = True
         if self.sharded:
             import torch.distributed as dist
@@ -858,21 +927,40 @@ class LidarTrainer:
                                    "growth_interval": 2000, "_growth_tracker": int(self.growth_tracker)}
             else:
                 state["scaler"] = self.scaler.state_dict()
+            if self.ema is not None:
+                state["ema"] = self.ema.state_dict()
         if getattr(self.model, "cuda_ray", False):  # a reference loader ignores the extra keys
             state["mean_count"], state["mean_density"] = self.model.mean_count, self.model.mean_density
             state["iter_density"], state["local_step"] = self.model.iter_density, self.model.local_step
-        state["model"] = self.model.state_dict()
+        if ema_model:
+            self._ema_swap()
+            try:
+                # (state_dict() returns views of the parameters: the file must hold the values they have NOW)
+                state["model"] = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
+            finally:
+                self._ema_swap()
+        else:
+            state["model"] = self.model.state_dict()
         torch.save(state, path)
         return path
 
     def load_checkpoint(self, path, model_only=False):
-        """Trainer.load_checkpoint (utils.py:1511-1568): a bare state dict or the dictionary above; strict=False."""
+        """Trainer.load_checkpoint (utils.py:1511-1568): a bare state dict or the dictionary above; strict=False.
+
+        A trainer with ema_decay restores the average from the file's "ema" (the reference's rule, utils.py:1538-1539).
+        When the file has none — a bare state dict, model_only, a checkpoint written without EMA — the shadows are
+        RE-SEEDED from the loaded parameters and num_updates goes back to 0: a deliberate deviation from the reference,
+        which would go on averaging from its random initialisation."""
         ck = torch.load(path, map_location=next(self.model.parameters()).device, weights_only=False)
         # whatever the file holds, the model is about to change under the captured steps (a bare state dict and
         # model_only=True never reach _after_optimizer_load): drop them on every path
         self._drop_graphs()
         if "model" not in ck:
             self.model.load_state_dict(ck)
+            if self.table is not None:
+                self.table._lnh_master_stale = False  # a loaded table is whole
+            if self.ema is not None:
+                self.ema.reseed()
             return [], []
         missing, unexpected = self.model.load_state_dict(ck["model"], strict=False)
         if getattr(self.model, "cuda_ray", False):
@@ -881,6 +969,11 @@ class LidarTrainer:
                     setattr(self.model, key, ck[key])
         if self.table is not None:
             self.table._lnh_master_stale = False  # a loaded table is whole
+        if self.ema is not None:
+            if not model_only and ck.get("ema") is not None:
+                self.ema.load_state_dict(ck["ema"])
+            else:
+                self.ema.reseed()
         if model_only:
             return missing, unexpected
         self.stats, self.epoch, self.global_step = ck["stats"], ck["epoch"], ck["global_step"]
@@ -900,6 +993,12 @@ class LidarTrainer:
         return missing, unexpected
 
     def step(self, rays_o, rays_d, images_lidar, patch=(1, 1)):
+        loss = self._step(rays_o, rays_d, images_lidar, patch)
+        if self.ema_interval and self.global_step % self.ema_interval == 0:
+            self.ema_update()  # (after the replay, outside any captured graph, on the same stream)
+        return loss
+
+    def _step(self, rays_o, rays_d, images_lidar, patch):
         if self.occupancy and self.global_step % self.update_extra_interval == 0:
             with torch.autocast("cuda", dtype=self.amp_dtype, enabled=self.fp16):
                 self.model.update_extra_state()  # refresh the occupancy grid the marcher reads (every 16 steps)
