@@ -779,6 +779,82 @@ LNH_API int lnh_ema_update(float *shadow, const float *param, uint64_t n, float 
 LNH_API int lnh_ema_swap(float *param, float *shadow, void *param16, uint64_t n, float *const *small_param,
                          float *const *small_shadow, const uint32_t *small_numel, uint32_t n_small, lnh_stream_t stream);
 
+/* ---- evaluation of one LiDAR frame (nerf/utils.py:886-1009 Trainer.eval_step / test_step after model.render, and what
+ * evaluate_one_epoch's meters compute from the returned images, 1357-1366 with MAEMeter / RMSEMeter / DepthMeter, 226-362),
+ * on the caller's stream, with no host read between the rendered outputs and the accumulated numbers.  (Added without
+ * moving lnh_version: detect the entry points by symbol.)
+ * Inputs: image_lidar [H*W, 2] (ray-drop, intensity) and depth_lidar [H*W] as the renderer returns them (f32), gt [H, W, 3]
+ * (ray-drop, intensity, depth).  Of `options` only depth_loss / raydrop_loss / intensity_loss (LNH_LOSS_L1 .. LNH_LOSS_BCE;
+ * LNH_LOSS_COS is a patch criterion and is refused), huber_delta, alpha_d / alpha_r / alpha_i and scale are read.
+ * Rules, with the reference's lines:
+ *   - mask = image_lidar[:, 0] > 0.5 (930 / 1002); LNH_EVAL_MODE_EVAL multiplies predicted intensity and depth by it only
+ *     if alpha_r > 0 and some pixel of the mask is set (936-938), LNH_EVAL_MODE_TEST whenever alpha_r > 0 (1005-1007).
+ *   - ground-truth intensity and depth are multiplied by the ground-truth ray-drop before anything is compared (913-914).
+ *   - nerf_mvl: ground-truth ray-drop -1 marks pixels outside the sensor's window (902-911): zeroed in the ground truth,
+ *     removed from the mask in EVAL mode (931-932; test_step has no ground truth and keeps them); the loss is still the mean
+ *     over the whole frame (940-946); the intensity meters and DepthMeter see the valid pixels (948-956, 1357-1366), which
+ *     the reference requires to fill their bounding rectangle — slots CROP_* and VALID let the host check that.
+ *   - loss = alpha_d mean C_depth(pred_depth, gt_depth) + alpha_r mean C_raydrop(pred_raydrop, gt_raydrop) + alpha_i mean
+ *     C_intensity(pred_intensity, gt_intensity) on the masked images (940-946).
+ *   - MAEMeter: mean |gt_i inv_scale - pred_i inv_scale| (290-292); RMSEMeter: sqrt(mean (gt_i - pred_i)^2) (249-250), both
+ *     on the INTENSITY images (1358-1359); DepthMeter (328-360): both depth images / scale, clamped to [1e-3, 80] m, rmse,
+ *     a_k = mean(max(gt/pred, pred/gt) < 1.25^k), SSIM with data_range = max - min of the clamped ground truth.
+ * lnh_lidar_eval_frame: writes the images eval_step / test_step return — pred_intensity, pred_depth [H*W] (masked as above)
+ *   and pred_mask [H*W] (1.0 / 0.0: the thresholded ray-drop, in EVAL mode times the valid window) — and leaves per-workgroup
+ *   partial sums in the workspace.  gt == NULL (LNH_EVAL_MODE_TEST only): the three images alone, H, W >= 1, no workspace.
+ * lnh_lidar_eval_ssim: mean SSIM of pred_depth (lnh_lidar_eval_frame's output) against the ground-truth depth, both / scale
+ *   and clamped, with skimage.metrics.structural_similarity's defaults (uniform 7x7 window, sample covariance, K1 0.01, K2
+ *   0.03, mean over the windows the image covers completely), window moments in fp64; over the bounding rectangle of the
+ *   valid pixels with nerf_mvl; data_range is read from the partials lnh_lidar_eval_frame left.  Leaves its partial sums
+ *   in the workspace.  A rectangle smaller than 7 x 7 gives NaN (and a frame without a valid pixel NaN in every meter
+ *   slot): such a row is added like any other, so the accumulator's means become NaN — slot LNH_EVAL_BAD counts these
+ *   frames, and a caller must not report the means of an accumulator whose LNH_EVAL_BAD is not 0.
+ * lnh_lidar_eval_finalize: adds the partials in index order, forms the frame's row of LNH_EVAL_SLOTS doubles, stores it at
+ *   history[frame * LNH_EVAL_SLOTS] when frame = accumulator[LNH_EVAL_FRAMES] < max_frames (history may be NULL with
+ *   max_frames 0), and adds it to accumulator[LNH_EVAL_SLOTS] (clear that before the first frame): meters are means of
+ *   per-frame values (252-256, 362-364), i.e. accumulator[slot] / accumulator[LNH_EVAL_FRAMES].
+ * Call the three in this order on one stream with the same H, W, mode, nerf_mvl and workspace
+ * (lnh_lidar_eval_workspace_bytes(H, W) bytes, 8-byte aligned, contents irrelevant; 0 for an unsupported shape).
+ * Deterministic (fixed-order sums, no float atomics); no allocation, copy or synchronisation: capturable in a hipGraph.
+ * Errors (before any launch): LNH_ERR_INVALID_ARG for a null pointer, H or W < 7, an unknown mode or criterion, COS, scale
+ * <= 0, a workspace smaller than the query; LNH_ERR_UNSUPPORTED for more than 2^24 pixels.
+ */
+enum { LNH_EVAL_MODE_EVAL = 0, LNH_EVAL_MODE_TEST = 1 };
+enum {
+    LNH_EVAL_LOSS = 0,           /* validation loss of the frame */
+    LNH_EVAL_LOSS_DEPTH = 1,     /* its three unweighted terms (means of the criteria) */
+    LNH_EVAL_LOSS_RAYDROP = 2,
+    LNH_EVAL_LOSS_INTENSITY = 3,
+    LNH_EVAL_MAE = 4,            /* MAEMeter on the intensity images */
+    LNH_EVAL_RMSE = 5,           /* RMSEMeter on the intensity images */
+    LNH_EVAL_DEPTH_RMSE = 6,     /* DepthMeter: rmse [m], a1, a2, a3, ssim */
+    LNH_EVAL_A1 = 7,
+    LNH_EVAL_A2 = 8,
+    LNH_EVAL_A3 = 9,
+    LNH_EVAL_SSIM = 10,
+    LNH_EVAL_MASKED = 11,        /* 1 if the ray-drop mask was applied to intensity and depth */
+    LNH_EVAL_CROP_R0 = 12,       /* bounding rectangle of the valid pixels: first row, first column, height, width */
+    LNH_EVAL_CROP_C0 = 13,
+    LNH_EVAL_CROP_H = 14,
+    LNH_EVAL_CROP_W = 15,
+    LNH_EVAL_VALID = 16,         /* number of valid pixels (== CROP_H * CROP_W for a rectangular window) */
+    LNH_EVAL_DATA_RANGE = 17,    /* max - min of the clamped ground-truth depth [m] */
+    LNH_EVAL_FRAMES = 18,        /* 1 per row: the accumulator's frame count */
+    LNH_EVAL_BAD = 19,           /* 1 if the means cannot use the row: a non-finite number, or valid pixels that do not fill
+                                    their rectangle; the accumulator counts such frames and the host refuses them */
+    LNH_EVAL_SLOTS = 20
+};
+LNH_API uint64_t lnh_lidar_eval_workspace_bytes(uint32_t H, uint32_t W);
+LNH_API int lnh_lidar_eval_frame(const float *image_lidar, const float *depth_lidar, const float *gt, uint32_t H, uint32_t W,
+                                 const lnh_lidar_loss_options *options, float intensity_inv_scale, int32_t mode,
+                                 int32_t nerf_mvl, void *workspace, uint64_t workspace_bytes, float *pred_intensity,
+                                 float *pred_depth, float *pred_mask, lnh_stream_t stream);
+LNH_API int lnh_lidar_eval_ssim(const float *pred_depth, const float *gt, uint32_t H, uint32_t W, float scale,
+                                int32_t nerf_mvl, void *workspace, uint64_t workspace_bytes, lnh_stream_t stream);
+LNH_API int lnh_lidar_eval_finalize(uint32_t H, uint32_t W, const lnh_lidar_loss_options *options, int32_t mode,
+                                    int32_t nerf_mvl, const void *workspace, uint64_t workspace_bytes, double *accumulator,
+                                    double *history, uint32_t max_frames, lnh_stream_t stream);
+
 
 /* ------------------------------------------------------------------ bf16 MLP operands (BASELINE config 5) ---- */
 /*

@@ -4,7 +4,12 @@ extern/chamfer3D (dist_chamfer_3D.py, chamfer3D.cu) + extern/fscore.py on the HI
 
 Same class names, constructor arguments, `update / measure / report / clear` protocol and numbers; inputs are CUDA
 tensors (NumPy arrays are moved to the GPU).  Not here: PSNR/LPIPS image meters of the RGB branch.
+
+FrameEvaluator is the fused form of what Trainer.eval_step / test_step do after the render plus the MAE / RMSE / Depth
+meters (csrc/eval_frame.hip): four launches per frame, no host read until measure().
 """
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -163,3 +168,144 @@ class PointsMeter:
 
     def report(self):
         return f"CD f-score = {self.measure()}"
+
+
+class FrameEvaluator:
+    """The evaluation epilogue of a LiDAR frame on the device (lnh_lidar_eval_frame / _ssim / _finalize, include/
+    lidarnerf_hip.h): the ray-drop masking of the reference's eval_step / test_step (utils.py:886-1009), its validation
+    loss, and the numbers its MAEMeter, RMSEMeter and DepthMeter would report for the frame (utils.py:1357-1366), added to a
+    running accumulator on the device.  Meters average per-frame values, as the reference's do.
+
+        ev = FrameEvaluator(H, W, scale)
+        for frame in frames:
+            pred_intensity, pred_depth, mask = ev.update(out["image_lidar"], out["depth_lidar"], gt)   # no host read
+        numbers = ev.measure()                                                                          # ONE copy to the host
+
+    alphas = (alpha_d, alpha_r, alpha_i); loss_options: a nerf.train_step.LidarLossOptions (its three per-ray criteria;
+    huber's delta is 0.2 * scale); nerf_mvl: ground-truth ray-drop -1 marks pixels outside the sensor's window; max_frames:
+    rows of per-frame history kept (later frames still count in the means).  update() allocates its three output images
+    and nothing else after the first call, and never synchronises: it can be captured in a torch.cuda.graph after one
+    eager call.  SSIM restates skimage's defaults (see structural_similarity above).  No CPU fallback."""
+
+    def __init__(self, H, W, scale, intensity_inv_scale=1.0, alphas=(1000.0, 1.0, 10.0), loss_options=None, nerf_mvl=False,
+                 max_frames=1024):
+        from .nerf.train_step import LidarLossOptions
+        self.H, self.W, self.scale = int(H), int(W), float(scale)
+        if self.H < 1 or self.W < 1:
+            raise ValueError(f"FrameEvaluator: H ({H}) and W ({W}) must be positive")
+        if not self.scale > 0:
+            raise ValueError("FrameEvaluator: scale must be positive")
+        self.intensity_inv_scale, self.nerf_mvl, self.max_frames = float(intensity_inv_scale), bool(nerf_mvl), int(max_frames)
+        if self.max_frames < 0:
+            raise ValueError("FrameEvaluator: max_frames must not be negative")
+        self.alphas = tuple(float(a) for a in alphas)
+        if len(self.alphas) != 3:
+            raise ValueError("FrameEvaluator: alphas = (alpha_d, alpha_r, alpha_i)")
+        self.loss_options = loss_options if loss_options is not None else LidarLossOptions()
+        if not isinstance(self.loss_options, LidarLossOptions):
+            raise TypeError(f"FrameEvaluator(loss_options=): a LidarLossOptions, not {type(self.loss_options).__name__}")
+        self._opt = _hip.loss_options(self.loss_options, 1, 1, self.scale, self.loss_options.huber_delta(self.scale),
+                                      *self.alphas, 0.0)
+        self.state = self._ws = None  # [1 + max_frames, EVAL_SLOTS] f64: row 0 the accumulator, then the history
+
+    def _alloc(self, device):
+        _hip.require_symbols(("lnh_lidar_eval_frame", "lnh_lidar_eval_ssim", "lnh_lidar_eval_finalize",
+                              "lnh_lidar_eval_workspace_bytes"), "metrics.FrameEvaluator")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FrameEvaluator: call update() once eagerly before capturing it (its buffers must exist)")
+        nbytes = int(_hip.lib().lnh_lidar_eval_workspace_bytes(self.H, self.W))
+        self._ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=device)
+        self.state = torch.zeros((1 + self.max_frames, _hip.EVAL_SLOTS), dtype=torch.float64, device=device)
+
+    def clear(self):
+        if self.state is not None:
+            self.state.zero_()
+
+    def update(self, image_lidar, depth_lidar, images_lidar, mode="eval"):
+        """image_lidar [.., H*W, 2], depth_lidar [.., H*W] (the renderer's outputs for ONE frame), images_lidar [.., H, W, 3]
+        ground truth; mode "eval" / "test": whose masking rule.  Returns (pred_intensity, pred_depth, mask), [H, W] f32 each:
+        the masked prediction images and the thresholded ray-drop mask (1.0 / 0.0)."""
+        if mode not in _hip.EVAL_MODES:
+            raise ValueError(f"FrameEvaluator.update: mode {mode!r} is not 'eval' or 'test'")
+        if self.H < 7 or self.W < 7:  # (mask(), test_step's rule without a ground truth, has no such limit)
+            raise ValueError(f"FrameEvaluator.update: H ({self.H}) and W ({self.W}) must be at least 7 (the SSIM window)")
+        for name, t in (("image_lidar", image_lidar), ("depth_lidar", depth_lidar), ("images_lidar", images_lidar)):
+            if not torch.is_tensor(t) or not t.is_cuda:
+                raise RuntimeError(f"FrameEvaluator.update: {name} must be a tensor on the GPU (no CPU fallback)")
+        N = self.H * self.W
+        if image_lidar.numel() != 2 * N or depth_lidar.numel() != N or images_lidar.numel() != 3 * N:
+            raise ValueError(f"FrameEvaluator.update: one {self.H} x {self.W} frame wanted (image_lidar [{N}, 2], depth_lidar "
+                             f"[{N}], images_lidar [{self.H}, {self.W}, 3]), got {tuple(image_lidar.shape)}, "
+                             f"{tuple(depth_lidar.shape)}, {tuple(images_lidar.shape)}")
+        image, depth, gt = (t.detach().float().contiguous() for t in (image_lidar, depth_lidar, images_lidar))
+        if self.state is None:
+            self._alloc(image.device)
+        out = torch.empty((3, self.H, self.W), dtype=torch.float32, device=image.device)
+        opt, code, mvl = C.cast(C.pointer(self._opt), C.c_void_p), _hip.EVAL_MODES[mode], int(self.nerf_mvl)
+        ws, ws_bytes = self._ws.data_ptr(), self._ws.numel() * 8
+        _hip.call("lnh_lidar_eval_frame", image.data_ptr(), depth.data_ptr(), gt.data_ptr(), self.H, self.W, opt,
+                  self.intensity_inv_scale, code, mvl, ws, ws_bytes, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr())
+        _hip.call("lnh_lidar_eval_ssim", out[1].data_ptr(), gt.data_ptr(), self.H, self.W, self.scale, mvl, ws, ws_bytes)
+        _hip.call("lnh_lidar_eval_finalize", self.H, self.W, opt, code, mvl, ws, ws_bytes, self.state.data_ptr(),
+                  self.state[1:].data_ptr() if self.max_frames else None, self.max_frames)
+        return out[0], out[1], out[2]
+
+    def mask(self, image_lidar, depth_lidar):
+        """test_step's masking without a ground truth (utils.py:998-1007) on any number of rows of width W: image_lidar
+        [.., 2], depth_lidar [..] -> (pred_intensity, pred_depth, mask) [rows, W].  Nothing is accumulated."""
+        for name, t in (("image_lidar", image_lidar), ("depth_lidar", depth_lidar)):
+            if not torch.is_tensor(t) or not t.is_cuda:
+                raise RuntimeError(f"FrameEvaluator.mask: {name} must be a tensor on the GPU (no CPU fallback)")
+        n = depth_lidar.numel()
+        if n == 0 or n % self.W or image_lidar.numel() != 2 * n:
+            raise ValueError(f"FrameEvaluator.mask: rows of {self.W} pixels wanted, got {tuple(image_lidar.shape)}, "
+                             f"{tuple(depth_lidar.shape)}")
+        _hip.require_symbols(("lnh_lidar_eval_frame",), "metrics.FrameEvaluator")
+        image, depth = image_lidar.detach().float().contiguous(), depth_lidar.detach().float().contiguous()
+        out = torch.empty((3, n // self.W, self.W), dtype=torch.float32, device=image.device)
+        _hip.call("lnh_lidar_eval_frame", image.data_ptr(), depth.data_ptr(), None, n // self.W, self.W,
+                  C.cast(C.pointer(self._opt), C.c_void_p), self.intensity_inv_scale, _hip.EVAL_MODES["test"], 0, None, 0,
+                  out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr())
+        return out[0], out[1], out[2]
+
+    def measure(self):
+        """One device-to-host copy.  {"frames", "loss", "mae", "rmse", "depth": array (rmse, a1, a2, a3, ssim), "history":
+        {slot name: per-frame array}} — means over the frames of the per-frame values.  Refuses (RuntimeError naming the
+        frame) an evaluation with a frame whose numbers cannot be averaged: NeRF-MVL valid pixels that do not fill their
+        rectangle, or a non-finite number."""
+        if self.state is None:
+            raise RuntimeError("FrameEvaluator.measure: no frame has been evaluated")
+        host = self.state.cpu().numpy()
+        acc, n = host[0], int(host[0][_hip.EVAL_SLOT_NAMES.index("frames")])
+        if n == 0:
+            raise RuntimeError("FrameEvaluator.measure: no frame has been evaluated")
+        rows = host[1:1 + min(n, self.max_frames)]
+        hist = {name: rows[:, k].copy() for k, name in enumerate(_hip.EVAL_SLOT_NAMES) if name != "frames"}
+        n_bad = int(acc[_hip.EVAL_SLOT_NAMES.index("bad")])
+        if n_bad:
+            # a row the means cannot use (the kernel counts them, also beyond the history): valid pixels that do not fill
+            # their rectangle — the reference's reshape to [B, crop_h, crop_w] raises there, utils.py:949-956 — or a
+            # non-finite number (no valid pixel, a window below 7 x 7, a non-finite render)
+            bad = np.nonzero(hist["bad"])[0]
+            where = f"frame {int(bad[0])}" if bad.size else f"a frame beyond the {self.max_frames} kept in the history"
+            why = ""
+            if bad.size:
+                k = int(bad[0])
+                if hist["valid"][k] != hist["crop_h"][k] * hist["crop_w"][k]:
+                    why = (f": the {int(hist['valid'][k])} valid pixels do not fill their {int(hist['crop_h'][k])} x "
+                           f"{int(hist['crop_w'][k])} bounding rectangle")
+                else:
+                    why = ": " + ", ".join(f"{name} = {hist[name][k]}" for name in _hip.EVAL_SLOT_NAMES[:11]
+                                           if not np.isfinite(hist[name][k])) + \
+                          f" ({int(hist['valid'][k])} valid pixels, window {int(hist['crop_h'][k])} x {int(hist['crop_w'][k])})"
+            raise RuntimeError(f"FrameEvaluator.measure: {n_bad} of {n} frames cannot be averaged; {where}{why}")
+        mean = {name: acc[k] / n for k, name in enumerate(_hip.EVAL_SLOT_NAMES)}
+        return {"frames": n, "loss": float(mean["loss"]), "mae": float(mean["mae"]), "rmse": float(mean["rmse"]),
+                "depth": np.array([mean["depth_rmse"], mean["a1"], mean["a2"], mean["a3"], mean["ssim"]]), "history": hist}
+
+    def report(self):
+        """The three lines the reference's meters log (utils.py:262, 304, 372)."""
+        m = self.measure()
+        text = f"MAE = {m['mae']:.6f}\nRMSE = {m['rmse']:.6f}\nDepth_error(rmse, a1, a2, a3, ssim) = {m['depth']}"
+        print(text)
+        return text

@@ -246,7 +246,7 @@ class LidarTrainer:
     def __init__(self, model, lr=1e-2, iters=30000, fp16=True, alpha_d=1000.0, alpha_r=1.0, alpha_i=10.0,
                  alpha_grad=100.0, scale=1.0, world_size=1, render_kwargs=None, fused_table_optimizer=True,
                  mlp_dtype=torch.float16, shard_table_optimizer=False, graph=False, loss_options=None, ema_decay=None,
-                 ema_interval=None):
+                 ema_interval=None, nerf_mvl=False, intensity_inv_scale=1.0):
         # mlp_dtype: the autocast dtype — torch.float16 (the reference's --fp16) or torch.bfloat16 (BASELINE config 5:
         # bf16 MFMA MLPs; the hash table and its gradient stay fp16, so the dynamic loss scale is kept either way)
         # (the backward picks reduce-scatter or all-reduce from the process group, parallel.world_size(): a world_size
@@ -266,6 +266,9 @@ class LidarTrainer:
         if not isinstance(self.loss_options, LidarLossOptions):
             raise TypeError(f"LidarTrainer(loss_options=): a LidarLossOptions, not {type(self.loss_options).__name__}")
         self.render_kwargs = render_kwargs or {}
+        # evaluation only (eval_step / evaluate): the reference's opt.dataloader == "nerf_mvl" (ground-truth ray-drop -1
+        # marks pixels outside the sensor's window) and MAEMeter's intensity_inv_scale (main_lidarnerf.py)
+        self.nerf_mvl, self.intensity_inv_scale = bool(nerf_mvl), float(intensity_inv_scale)
         # Adam(betas .9/.99, eps 1e-15) and lr * 0.1^(it/iters) (main_lidarnerf.py:389-391, 408-410)
         # get_params returns generators: materialise them; one fused kernel for all parameter groups on the GPU
         params = [dict(g, params=list(g["params"])) for g in model.get_params(lr)]
@@ -707,6 +710,47 @@ class LidarTrainer:
             if tp is not None:
                 del tp._lnh_ema_weights
             self._ema_swap()
+
+    # ---- evaluation (nerf/evaluate.py; the reference's eval_step / test_step / evaluate_one_epoch, utils.py:886-1009,
+    # 1282-1447)
+    def eval_step(self, data):
+        """The reference's Trainer.eval_step (utils.py:886-977) on one frame: data["rays_o_lidar"] / ["rays_d_lidar"]
+        [1, H*W, 3], data["images_lidar"] [1, H, W, 3] on the GPU.  Renders with model.render(cal_lidar_color=True,
+        staged=True, perturb=False) under no_grad and the trainer's autocast dtype and render_kwargs, and returns its nine
+        values: pred_intensity [1,H,W,1], pred_depth [1,H,W], pred_depth_crop, pred_raydrop [1,H,W,1], gt_intensity
+        [1,H,W,1], gt_depth [1,H,W], gt_depth_crop, gt_raydrop [1,H,W,1], loss (0-dim, on the device).  The crops are None
+        unless nerf_mvl; with it the intensity images and the crops are [1, crop_h, crop_w(, 1)] — their shape costs this
+        method one host read.  Masking, loss: lnh_lidar_eval_frame (include/lidarnerf_hip.h).  The model's mode and weights
+        are the caller's (the reference calls it from evaluate_one_epoch); evaluate() is the loop."""
+        from . import evaluate
+        return evaluate.eval_step(self, data)
+
+    def test_step(self, data, perturb=False):
+        """The reference's Trainer.test_step (utils.py:980-1009): data["rays_o_lidar"], ["rays_d_lidar"] [B, H*W, 3],
+        ["H_lidar"], ["W_lidar"] -> (pred_raydrop, pred_intensity, pred_depth), [B, H, W] each; intensity and depth are
+        multiplied by (pred_raydrop > 0.5) whenever alpha_r > 0 (no "not all zero" exception, no ground truth)."""
+        from . import evaluate
+        return evaluate.test_step(self, data, perturb)
+
+    def evaluate(self, frames, *, points_intrinsics=None, ema=True, save_dir=None):
+        """The reference's evaluate_one_epoch (utils.py:1282-1447) over `frames`, any iterable of eval_step's `data` dicts
+        (the loaders of lidarnerf.dataset.range_image yield them), all of one size.  model.eval(); with `ema` and a trainer
+        that keeps a parameter average the frames are rendered on the averaged weights (ema_weights(): with the sharded
+        table optimizer entering it is COLLECTIVE — call evaluate() on every rank); every frame goes through the render and
+        metrics.FrameEvaluator.update (no host read per frame); points_intrinsics=(fov_up, fov) also feeds the masked depth
+        of the full frame to metrics.PointsMeter (chamfer distance / F-score; that meter keeps its host read); save_dir
+        writes ep<epoch>_<frame>_lidar.npy point clouds through convert.pano_to_lidar (needs points_intrinsics; no PNG
+        colour maps).  Appends the mean validation loss to stats["valid_loss"] and, as utils.py:1422-1436 does, the first
+        number of the LAST meter to stats["results"]: the chamfer distance with points_intrinsics, the depth RMSE in metres
+        without (the depth meter always runs here, so the reference's "no meter: the loss" case does not arise).  Weights
+        and the model's train / eval mode are restored also after an exception.  Each rank evaluates the frames it is
+        given; nothing is reduced across ranks.  Returns FrameEvaluator.measure()'s dict (+ "points"); its per-frame
+        history holds the first 4096 frames, the means every frame.  A frame whose numbers cannot be averaged (NeRF-MVL
+        valid pixels that do not fill their rectangle — the reference raises inside eval_step — or a non-finite number) is
+        counted on the device whatever its index and refused by measure() at the END of the loop: nothing is appended to
+        stats then, but that frame's PointsMeter update and .npy file have already happened."""
+        from . import evaluate
+        return evaluate.evaluate(self, frames, points_intrinsics=points_intrinsics, ema=ema, save_dir=save_dir)
 
     # ---- what lives outside torch.optim / GradScaler when the table is stepped by the fused kernel
     def table_grad(self):
