@@ -855,6 +855,57 @@ LNH_API int lnh_lidar_eval_finalize(uint32_t H, uint32_t W, const lnh_lidar_loss
                                     int32_t nerf_mvl, const void *workspace, uint64_t workspace_bytes, double *accumulator,
                                     double *history, uint32_t max_frames, lnh_stream_t stream);
 
+/* ---- points meter of one evaluation frame (nerf/utils.py:375-427 PointsMeter: both range images back-projected to point
+ * clouds, extern/chamfer3D's nearest-neighbour distances between them, extern/fscore.py), from two depth images to a row of
+ * numbers on the device, on the caller's stream, with no host read.  (Added without moving lnh_version: detect by symbol.)
+ * Buffers of the caller, capacity = H * W: cloud_pred / cloud_gt [capacity, 4] f32 (x, y, z, 0; 16-byte aligned), counts
+ * uint32[2] (points of cloud_pred, cloud_gt), dist_* [capacity] f32, idx_* [capacity] int32; one workspace of
+ * lnh_eval_points_workspace_bytes(H, W) bytes (16-byte aligned, contents irrelevant; 0 for an unsupported shape).
+ * lnh_eval_points_project: pred_depth [H*W] (the masked depth lnh_lidar_eval_frame writes) and gt [H, W, 3] (ray-drop,
+ *   intensity, depth; with nerf_mvl a ray-drop of -1 counts as 0) -> the metric depth images pred * (1 / scale) and
+ *   gt_depth * gt_raydrop * (1 / scale) (torch's tensor / host scalar: a product with the float32 reciprocal), every pixel
+ *   back-projected with lnh_pano_to_lidar's arithmetic, the pixels with depth != 0 compacted in row-major pixel order into
+ *   the two clouds, and the two counts.  Rows >= count are left as they were.  Equal, bit for bit and row for row, to
+ *   convert.pano_to_lidar(depth / scale, (fov_up, fov)).
+ * lnh_eval_points_nn: for every point of each cloud the SQUARED distance to, and the index of, its nearest point in the
+ *   other cloud (first index on ties), both directions in one call, counts read from device memory: dist_pred / idx_pred
+ *   [counts[0]] against cloud_gt, dist_gt / idx_gt [counts[1]] against cloud_pred — bit-identical to two lnh_chamfer_nn
+ *   calls.  Rows >= count of the clouds are never read.  An empty target cloud gives +inf / 0.
+ * lnh_eval_points_finalize: sums both distance arrays in a fixed order in fp64, counts dist < threshold on each side, forms
+ *   the row of LNH_PTS_SLOTS doubles, stores it at history[frame * LNH_PTS_SLOTS] when frame = accumulator[LNH_PTS_FRAMES] <
+ *   max_frames (history may be NULL with max_frames 0) and adds it to accumulator[LNH_PTS_SLOTS] (clear that before the
+ *   first frame): the meter is the mean of per-frame values, accumulator[slot] / accumulator[LNH_PTS_FRAMES].  A frame with
+ *   an empty cloud on either side has no chamfer distance: its row holds NaN, the distance arrays are not read, and
+ *   LNH_PTS_BAD counts it — a caller must not report the means of an accumulator whose LNH_PTS_BAD is not 0.
+ * Call the three in this order on one stream.  Deterministic (integer minimum over the partial searches, fixed-order sums, no
+ * float atomics); no allocation, copy or synchronisation: capturable in a hipGraph.
+ * Errors (before any launch): LNH_ERR_INVALID_ARG for a null or misaligned pointer, H * W = 0, scale or threshold <= 0, a
+ * workspace smaller than the query; LNH_ERR_UNSUPPORTED for more than 2^24 pixels.
+ */
+enum {
+    LNH_PTS_CHAMFER = 0,     /* mean(dist_pred) + mean(dist_gt) */
+    LNH_PTS_FSCORE = 1,      /* 2 p r / (p + r), 0 where that is NaN (extern/fscore.py) */
+    LNH_PTS_PRECISION = 2,   /* p: share of dist_pred < threshold */
+    LNH_PTS_RECALL = 3,      /* r: share of dist_gt < threshold */
+    LNH_PTS_MEAN_PRED = 4,   /* the two means */
+    LNH_PTS_MEAN_GT = 5,
+    LNH_PTS_COUNT_PRED = 6,  /* the two point counts */
+    LNH_PTS_COUNT_GT = 7,
+    LNH_PTS_FRAMES = 8,      /* 1 per row: the accumulator's frame count */
+    LNH_PTS_BAD = 9,         /* 1 if the means cannot use the row: an empty cloud or a non-finite chamfer distance */
+    LNH_PTS_SLOTS = 10
+};
+LNH_API uint64_t lnh_eval_points_workspace_bytes(uint32_t H, uint32_t W);
+LNH_API int lnh_eval_points_project(const float *pred_depth, const float *gt, uint32_t H, uint32_t W, float fov_up, float fov,
+                                    float scale, int32_t nerf_mvl, void *workspace, uint64_t workspace_bytes,
+                                    float *cloud_pred, float *cloud_gt, uint32_t *counts, lnh_stream_t stream);
+LNH_API int lnh_eval_points_nn(const float *cloud_pred, const float *cloud_gt, const uint32_t *counts, uint32_t capacity,
+                               void *workspace, uint64_t workspace_bytes, float *dist_pred, int32_t *idx_pred,
+                               float *dist_gt, int32_t *idx_gt, lnh_stream_t stream);
+LNH_API int lnh_eval_points_finalize(const float *dist_pred, const float *dist_gt, const uint32_t *counts, uint32_t capacity,
+                                     float threshold, double *accumulator, double *history, uint32_t max_frames,
+                                     lnh_stream_t stream);
+
 
 /* ------------------------------------------------------------------ bf16 MLP operands (BASELINE config 5) ---- */
 /*

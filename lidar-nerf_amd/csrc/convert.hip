@@ -10,6 +10,7 @@
 // weak-scalar promotion rounds them); atan2 is evaluated in double and rounded to float, which reproduces a
 // correctly-rounded atan2f.
 #include "common.h"
+#include "pano_geom.h"
 
 namespace {
 
@@ -61,14 +62,12 @@ k_pano_to_lidar(const float *__restrict__ pano, const float *__restrict__ intens
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= H * W) return;
     const uint32_t j = p / W, i = p % W;
-    // convert.py:207-217: float32 index grids; W/2, W, H are Python scalars (weak), 2*np.pi and 180 likewise
-    const float beta = -((float)i - (float)(W / 2.0)) / (float)W * 2.0f * (float)kPi;
-    const float alpha = (fov_up - (float)j / (float)H * fov) / 180.0f * (float)kPi;
-    const float ca = cosf(alpha), sa = sinf(alpha), cb = cosf(beta), sb = sinf(beta);
     const float d = pano[p];
-    pts[(size_t)p * 4] = ca * cb * d;
-    pts[(size_t)p * 4 + 1] = ca * sb * d;
-    pts[(size_t)p * 4 + 2] = sa * d;
+    float x, y, z;
+    pano_point(j, i, H, W, fov_up, fov, d, x, y, z);  // (pano_geom.h: shared with the fused points meter)
+    pts[(size_t)p * 4] = x;
+    pts[(size_t)p * 4 + 1] = y;
+    pts[(size_t)p * 4 + 2] = z;
     pts[(size_t)p * 4 + 3] = intens ? intens[p] : 0.0f;
     valid[p] = d != 0.0f;
 }

@@ -103,11 +103,16 @@ _SIGS = {
     "lnh_lidar_eval_frame": [P, P, P, U32, U32, P, F32, I32, I32, P, C.c_uint64, P, P, P],
     "lnh_lidar_eval_ssim": [P, P, U32, U32, F32, I32, P, C.c_uint64],
     "lnh_lidar_eval_finalize": [U32, U32, P, I32, I32, P, C.c_uint64, P, P, U32],
+    "lnh_eval_points_project": [P, P, U32, U32, F32, F32, F32, I32, P, C.c_uint64, P, P, P],
+    "lnh_eval_points_nn": [P, P, P, U32, P, C.c_uint64, P, P, P, P],
+    "lnh_eval_points_finalize": [P, P, P, U32, F32, P, P, U32],
 }
 # entry points added without moving lnh_version(): a library built before them still loads, and the feature is detected
 # by symbol (require_symbols)
 _OPTIONAL = {"lnh_lidar_eval_frame": "frame evaluation", "lnh_lidar_eval_ssim": "frame evaluation",
-             "lnh_lidar_eval_finalize": "frame evaluation", "lnh_lidar_eval_workspace_bytes": "frame evaluation"}
+             "lnh_lidar_eval_finalize": "frame evaluation", "lnh_lidar_eval_workspace_bytes": "frame evaluation",
+             "lnh_eval_points_project": "points evaluation", "lnh_eval_points_nn": "points evaluation",
+             "lnh_eval_points_finalize": "points evaluation", "lnh_eval_points_workspace_bytes": "points evaluation"}
 for _n in ("lnh_mlp_forward", "lnh_mlp_backward", "lnh_mlp_backward_data", "lnh_mlp_wgrad", "lnh_density_mlp_forward", "lnh_density_mlp_backward",
            "lnh_lidar_dir_term", "lnh_lidar_pack_weights", "lnh_lidar_step_prologue", "lnh_lidar_color_forward", "lnh_lidar_color_backward",
            "lnh_lidar_color_composite_forward", "lnh_lidar_color_backward_image", "lnh_lidar_dir_term_freq",
@@ -118,7 +123,8 @@ EXPORTS = sorted(list(_SIGS) + ["lnh_version", "lnh_last_error", "lnh_arch", "ln
                                  "lnh_grid_backward_workspace_size", "lnh_grid_backward_workspace_size_min",
                                  "lnh_grid_backward_plan_info", "lnh_grid_backward_workspace_clear_bytes",
                                  "lnh_grid_backward_set_slice_entries", "lnh_wgrad_workspace_bytes",
-                                 "lnh_lidar_loss_ex_workspace_bytes", "lnh_lidar_eval_workspace_bytes"])
+                                 "lnh_lidar_loss_ex_workspace_bytes", "lnh_lidar_eval_workspace_bytes",
+                                 "lnh_eval_points_workspace_bytes"])
 
 LNH_F32, LNH_F16 = 0, 1
 LNH_BWD_WS_CLEARED, LNH_BWD_TABLE_ZERO = 1, 2
@@ -160,6 +166,9 @@ def lib():
         if hasattr(L, "lnh_lidar_eval_workspace_bytes"):
             L.lnh_lidar_eval_workspace_bytes.argtypes = [U32, U32]
             L.lnh_lidar_eval_workspace_bytes.restype = C.c_uint64
+        if hasattr(L, "lnh_eval_points_workspace_bytes"):
+            L.lnh_eval_points_workspace_bytes.argtypes = [U32, U32]
+            L.lnh_eval_points_workspace_bytes.restype = C.c_uint64
         L.lnh_last_error.restype = C.c_char_p
         L.lnh_arch.restype = C.c_char_p
         L.lnh_build_variant.restype = C.c_char_p
@@ -220,6 +229,10 @@ EVAL_MODES = {"eval": 0, "test": 1}
 EVAL_SLOT_NAMES = ("loss", "loss_depth", "loss_raydrop", "loss_intensity", "mae", "rmse", "depth_rmse", "a1", "a2", "a3",
                    "ssim", "masked", "crop_r0", "crop_c0", "crop_h", "crop_w", "valid", "data_range", "frames", "bad")
 EVAL_SLOTS = len(EVAL_SLOT_NAMES)
+# lnh_eval_points_* (include/lidarnerf_hip.h, LNH_PTS_*): row layout of the fused points meter
+PTS_SLOT_NAMES = ("chamfer", "fscore", "precision", "recall", "mean_pred", "mean_gt", "count_pred", "count_gt", "frames",
+                  "bad")
+PTS_SLOTS = len(PTS_SLOT_NAMES)
 
 
 # lnh_lidar_loss_options (include/lidarnerf_hip.h): criterion codes, flags, the struct

@@ -309,3 +309,116 @@ class FrameEvaluator:
         text = f"MAE = {m['mae']:.6f}\nRMSE = {m['rmse']:.6f}\nDepth_error(rmse, a1, a2, a3, ssim) = {m['depth']}"
         print(text)
         return text
+
+
+class FramePointsEvaluator:
+    """The points meter of a LiDAR frame on the device (lnh_eval_points_project / _nn / _finalize, include/lidarnerf_hip.h,
+    csrc/eval_points.hip): what PointsMeter computes — both depth images back-projected to point clouds, the chamfer
+    distance and the F-score between them — from the masked predicted depth FrameEvaluator.update returns and the ground-
+    truth frame to a row of numbers in an accumulator on the device.
+
+        pts = FramePointsEvaluator(H, W, scale, (fov_up, fov))
+        for frame in frames:
+            pts.update(pred_depth, images_lidar)          # no host read
+        chamfer, fscore = pts.measure()                    # ONE copy to the host
+
+    threshold: the F-score's, on SQUARED distances (PointsMeter's 0.05); nerf_mvl: ground-truth ray-drop -1 counts as 0;
+    max_frames: rows of per-frame history kept (later frames still count in the means).  update() allocates on its first
+    call only and never synchronises: it can be captured in a torch.cuda.graph after one eager call.  The clouds equal
+    convert.pano_to_lidar(depth / scale, intrinsics) bit for bit, the distances lnh_chamfer_nn's; per-frame means are taken
+    in fp64 (PointsMeter: fp32).  No CPU fallback."""
+
+    def __init__(self, H, W, scale, intrinsics, threshold=0.05, nerf_mvl=False, max_frames=1024):
+        self.H, self.W, self.scale = int(H), int(W), float(scale)
+        if self.H < 1 or self.W < 1:
+            raise ValueError(f"FramePointsEvaluator: H ({H}) and W ({W}) must be positive")
+        if not self.scale > 0:
+            raise ValueError("FramePointsEvaluator: scale must be positive")
+        self.intrinsics = (float(intrinsics[0]), float(intrinsics[1]))
+        self.threshold, self.nerf_mvl, self.max_frames = float(threshold), bool(nerf_mvl), int(max_frames)
+        if not self.threshold > 0:
+            raise ValueError("FramePointsEvaluator: threshold must be positive")
+        if self.max_frames < 0:
+            raise ValueError("FramePointsEvaluator: max_frames must not be negative")
+        self.state = self._ws = None  # [1 + max_frames, PTS_SLOTS] f64: row 0 the accumulator, then the history
+
+    def _alloc(self, device):
+        _hip.require_symbols(("lnh_eval_points_project", "lnh_eval_points_nn", "lnh_eval_points_finalize",
+                              "lnh_eval_points_workspace_bytes"), "metrics.FramePointsEvaluator")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FramePointsEvaluator: call update() once eagerly before capturing it (its buffers must exist)")
+        nbytes = int(_hip.lib().lnh_eval_points_workspace_bytes(self.H, self.W))
+        if nbytes == 0:
+            raise ValueError(f"FramePointsEvaluator: a frame of {self.H} x {self.W} pixels is not supported (at most 2^24)")
+        cap = self.H * self.W
+        self._ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=device)
+        self.clouds = torch.zeros((2, cap, 4), dtype=torch.float32, device=device)  # predicted, ground truth: x, y, z, 0
+        self.counts = torch.zeros(4, dtype=torch.int32, device=device)
+        self.dist = torch.zeros((2, cap), dtype=torch.float32, device=device)
+        self.idx = torch.zeros((2, cap), dtype=torch.int32, device=device)
+        self.state = torch.zeros((1 + self.max_frames, _hip.PTS_SLOTS), dtype=torch.float64, device=device)
+
+    def clear(self):
+        if self.state is not None:
+            self.state.zero_()
+
+    def update(self, pred_depth, images_lidar):
+        """pred_depth [.., H, W]: the masked predicted depth of ONE frame (FrameEvaluator.update's second value);
+        images_lidar [.., H, W, 3]: the ground truth (ray-drop, intensity, depth).  Returns nothing."""
+        for name, t in (("pred_depth", pred_depth), ("images_lidar", images_lidar)):
+            if not torch.is_tensor(t) or not t.is_cuda:
+                raise RuntimeError(f"FramePointsEvaluator.update: {name} must be a tensor on the GPU (no CPU fallback)")
+        N = self.H * self.W
+        if pred_depth.numel() != N or images_lidar.numel() != 3 * N:
+            raise ValueError(f"FramePointsEvaluator.update: one {self.H} x {self.W} frame wanted (pred_depth [{self.H}, {self.W}], "
+                             f"images_lidar [{self.H}, {self.W}, 3]), got {tuple(pred_depth.shape)}, {tuple(images_lidar.shape)}")
+        depth, gt = pred_depth.detach().float().contiguous(), images_lidar.detach().float().contiguous()
+        if self.state is None:
+            self._alloc(depth.device)
+        ws, ws_bytes = self._ws.data_ptr(), self._ws.numel() * 8
+        _hip.call("lnh_eval_points_project", depth.data_ptr(), gt.data_ptr(), self.H, self.W, self.intrinsics[0],
+                  self.intrinsics[1], self.scale, int(self.nerf_mvl), ws, ws_bytes, self.clouds[0].data_ptr(),
+                  self.clouds[1].data_ptr(), self.counts.data_ptr())
+        _hip.call("lnh_eval_points_nn", self.clouds[0].data_ptr(), self.clouds[1].data_ptr(), self.counts.data_ptr(), N, ws,
+                  ws_bytes, self.dist[0].data_ptr(), self.idx[0].data_ptr(), self.dist[1].data_ptr(), self.idx[1].data_ptr())
+        _hip.call("lnh_eval_points_finalize", self.dist[0].data_ptr(), self.dist[1].data_ptr(), self.counts.data_ptr(), N,
+                  self.threshold, self.state.data_ptr(), self.state[1:].data_ptr() if self.max_frames else None,
+                  self.max_frames)
+
+    def cloud(self):
+        """The predicted cloud of the last frame, [count, 3] on the device (a view of the evaluator's buffer: the next
+        update() overwrites it).  The one method that reads the count back."""
+        if self.state is None:
+            raise RuntimeError("FramePointsEvaluator.cloud: no frame has been evaluated")
+        return self.clouds[0, :int(self.counts[0]), :3]
+
+    def rows(self):
+        """One device-to-host copy: (accumulator row, history rows of the frames kept), fp64, slots _hip.PTS_SLOT_NAMES."""
+        if self.state is None:
+            raise RuntimeError("FramePointsEvaluator.measure: no frame has been evaluated")
+        host = self.state.cpu().numpy()
+        n = int(host[0][_hip.PTS_SLOT_NAMES.index("frames")])
+        return host[0], host[1:1 + min(n, self.max_frames)]
+
+    def measure(self):
+        """np.array([chamfer distance, F-score]): means over the frames of the per-frame values, as PointsMeter.measure().
+        Refuses (RuntimeError naming the frame) an evaluation with a frame that has no chamfer distance: an empty cloud on
+        either side, or a non-finite distance."""
+        acc, rows = self.rows()
+        slot = _hip.PTS_SLOT_NAMES.index
+        n = int(acc[slot("frames")])
+        if n == 0:
+            raise RuntimeError("FramePointsEvaluator.measure: no frame has been evaluated")
+        n_bad = int(acc[slot("bad")])
+        if n_bad:
+            bad = np.nonzero(rows[:, slot("bad")])[0]
+            where = f"a frame beyond the {self.max_frames} kept in the history"
+            if bad.size:
+                k = int(bad[0])
+                where = (f"frame {k}: {int(rows[k, slot('count_pred')])} predicted and {int(rows[k, slot('count_gt')])} "
+                         f"ground-truth points, chamfer = {rows[k, slot('chamfer')]}")
+            raise RuntimeError(f"FramePointsEvaluator.measure: {n_bad} of {n} frames have no chamfer distance; {where}")
+        return np.array([acc[slot("chamfer")] / n, acc[slot("fscore")] / n])
+
+    def report(self):
+        return f"CD f-score = {self.measure()}"

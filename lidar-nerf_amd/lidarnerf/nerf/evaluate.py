@@ -93,14 +93,14 @@ def test_step(trainer, data, perturb=False):
     return image[..., 0], pred_intensity.reshape(B, H, W), pred_depth.reshape(B, H, W)
 
 
-def evaluate(trainer, frames, *, points_intrinsics=None, ema=True, save_dir=None):
-    from ..metrics import PointsMeter
+def evaluate(trainer, frames, *, points_intrinsics=None, ema=True, save_dir=None, fused_points=False):
+    from ..metrics import FramePointsEvaluator, PointsMeter
     from ..convert import pano_to_lidar
     model = trainer.model
     was_training = model.training
     use_ema = bool(ema) and trainer.ema is not None
     ev, points, n = None, None, 0
-    if points_intrinsics is not None:
+    if points_intrinsics is not None and not fused_points:
         points = PointsMeter(trainer.scale, points_intrinsics)
     if save_dir is not None:
         if points_intrinsics is None:
@@ -119,13 +119,19 @@ def evaluate(trainer, frames, *, points_intrinsics=None, ema=True, save_dir=None
                 out = _render(trainer, rays_o, rays_d, False)
                 _, pred_depth, _ = ev.update(out["image_lidar"], out["depth_lidar"], images, mode="eval")
                 n += 1
-                if points is not None:  # (the full frame, also with nerf_mvl: utils.py:1361-1366)
+                if fused_points and points_intrinsics is not None:  # (the same meter with no host read per frame)
+                    if points is None:
+                        points = FramePointsEvaluator(H, W, trainer.scale, points_intrinsics, nerf_mvl=trainer.nerf_mvl,
+                                                      max_frames=HISTORY_FRAMES)
+                    points.update(pred_depth, images)
+                elif points is not None:  # (the full frame, also with nerf_mvl: utils.py:1361-1366)
                     gr = images[..., 0]
                     if trainer.nerf_mvl:
                         gr = gr * torch.where(gr == -1, 0, 1)
                     points.update(pred_depth[None], images[..., 2] * gr)
                 if save_dir is not None:
-                    cloud = pano_to_lidar(pred_depth / trainer.scale, points_intrinsics)
+                    # (the fused meter has just built this cloud; reading its row count is the one host read it costs)
+                    cloud = points.cloud() if fused_points else pano_to_lidar(pred_depth / trainer.scale, points_intrinsics)
                     np.save(os.path.join(save_dir, f"ep{trainer.epoch:04d}_{n:04d}_lidar.npy"), cloud.cpu().numpy())
     finally:
         model.train(was_training)

@@ -246,7 +246,7 @@ class LidarTrainer:
     def __init__(self, model, lr=1e-2, iters=30000, fp16=True, alpha_d=1000.0, alpha_r=1.0, alpha_i=10.0,
                  alpha_grad=100.0, scale=1.0, world_size=1, render_kwargs=None, fused_table_optimizer=True,
                  mlp_dtype=torch.float16, shard_table_optimizer=False, graph=False, loss_options=None, ema_decay=None,
-                 ema_interval=None, nerf_mvl=False, intensity_inv_scale=1.0):
+                 ema_interval=None, nerf_mvl=False, intensity_inv_scale=1.0, fused_points=False):
         # mlp_dtype: the autocast dtype — torch.float16 (the reference's --fp16) or torch.bfloat16 (BASELINE config 5:
         # bf16 MFMA MLPs; the hash table and its gradient stay fp16, so the dynamic loss scale is kept either way)
         # (the backward picks reduce-scatter or all-reduce from the process group, parallel.world_size(): a world_size
@@ -269,6 +269,9 @@ class LidarTrainer:
         # evaluation only (eval_step / evaluate): the reference's opt.dataloader == "nerf_mvl" (ground-truth ray-drop -1
         # marks pixels outside the sensor's window) and MAEMeter's intensity_inv_scale (main_lidarnerf.py)
         self.nerf_mvl, self.intensity_inv_scale = bool(nerf_mvl), float(intensity_inv_scale)
+        # evaluate(points_intrinsics=): the points meter on the device (metrics.FramePointsEvaluator) instead of
+        # metrics.PointsMeter.  An attribute, assignable between evaluations; off keeps every number of PointsMeter bit for bit
+        self.fused_points = bool(fused_points)
         # Adam(betas .9/.99, eps 1e-15) and lr * 0.1^(it/iters) (main_lidarnerf.py:389-391, 408-410)
         # get_params returns generators: materialise them; one fused kernel for all parameter groups on the GPU
         params = [dict(g, params=list(g["params"])) for g in model.get_params(lr)]
@@ -738,7 +741,10 @@ class LidarTrainer:
         that keeps a parameter average the frames are rendered on the averaged weights (ema_weights(): with the sharded
         table optimizer entering it is COLLECTIVE — call evaluate() on every rank); every frame goes through the render and
         metrics.FrameEvaluator.update (no host read per frame); points_intrinsics=(fov_up, fov) also feeds the masked depth
-        of the full frame to metrics.PointsMeter (chamfer distance / F-score; that meter keeps its host read); save_dir
+        of the full frame to metrics.PointsMeter (chamfer distance / F-score; that meter keeps its host read), or on a
+        trainer with fused_points=True (constructor argument and attribute; nerf.evaluate.evaluate takes it as a keyword) to
+        metrics.FramePointsEvaluator (the same numbers with per-frame means in fp64, no host read per
+        frame; a frame with an empty cloud is refused by its measure() at the end of the loop); save_dir
         writes ep<epoch>_<frame>_lidar.npy point clouds through convert.pano_to_lidar (needs points_intrinsics; no PNG
         colour maps).  Appends the mean validation loss to stats["valid_loss"] and, as utils.py:1422-1436 does, the first
         number of the LAST meter to stats["results"]: the chamfer distance with points_intrinsics, the depth RMSE in metres
@@ -750,7 +756,8 @@ class LidarTrainer:
         counted on the device whatever its index and refused by measure() at the END of the loop: nothing is appended to
         stats then, but that frame's PointsMeter update and .npy file have already happened."""
         from . import evaluate
-        return evaluate.evaluate(self, frames, points_intrinsics=points_intrinsics, ema=ema, save_dir=save_dir)
+        return evaluate.evaluate(self, frames, points_intrinsics=points_intrinsics, ema=ema, save_dir=save_dir,
+                                 fused_points=self.fused_points)
 
     # ---- what lives outside torch.optim / GradScaler when the table is stepped by the fused kernel
     def table_grad(self):
