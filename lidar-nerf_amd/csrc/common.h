@@ -83,6 +83,21 @@ __device__ __forceinline__ float wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
+    return v;
+}
+// sum over the workgroup (kT threads) in a fixed order; every thread receives it.  `sh`: kT / 64 doubles of LDS.
+template <uint32_t kT>
+__device__ __forceinline__ double block_sum(double v, double *sh) {
+    static_assert(kT == 256, "block_sum adds exactly four wave sums: a workgroup of 256 threads");
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
 // inclusive scan (sum) across the 64 lanes of a wave
 __device__ __forceinline__ float wave_scan_add(float v, int lane) {
 #pragma unroll

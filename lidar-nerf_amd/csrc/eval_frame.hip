@@ -70,21 +70,6 @@ __host__ __device__ __forceinline__ bool mask_applies(float alpha_r, int32_t mod
 // numpy's in-place clamp of DepthMeter (utils.py:344-347): a NaN stays a NaN
 __device__ __forceinline__ float clamp_depth(float x) { return x < 1e-3f ? 1e-3f : (x > 80.0f ? 80.0f : x); }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-    return v;
-}
-
-// sum over the workgroup in a fixed order; every thread receives it.  `sh`: kT / 64 doubles of LDS.
-__device__ __forceinline__ double block_sum(double v, double *sh) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
 // combines thread-private AnyPart values of the workgroup (integer operations: any order gives the same bits)
 __device__ __forceinline__ AnyPart block_any(const AnyPart &t, AnyPart *sh) {
     __syncthreads();
@@ -202,7 +187,7 @@ k_eval_frame(EvalArgs a, const AnyPart *__restrict__ any_parts, FramePart *__res
     }
     double tot_s[6];
 #pragma unroll
-    for (int q = 0; q < 6; q++) tot_s[q] = block_sum(s[q], sh);
+    for (int q = 0; q < 6; q++) tot_s[q] = block_sum<kT>(s[q], sh);
 #pragma unroll
     for (int sft = 32; sft > 0; sft >>= 1) {
         gmin = fminf(gmin, __shfl_xor(gmin, sft, 64));
@@ -319,7 +304,7 @@ k_eval_ssim(const float *__restrict__ pred_depth, const float *__restrict__ gt, 
         const double vx = cov_norm * (uxx - ux * ux), vy = cov_norm * (uyy - uy * uy), vxy = cov_norm * (uxy - ux * uy);
         acc += ((2.0 * ux * uy + c1) * (2.0 * vxy + c2)) / ((ux * ux + uy * uy + c1) * (vx + vy + c2));
     }
-    const double total = block_sum(acc, sh);
+    const double total = block_sum<kT>(acc, sh);
     if (threadIdx.x == 0) ssim_parts[part] = total;
 }
 
@@ -338,12 +323,12 @@ k_eval_finalize(uint32_t N, uint32_t B, uint32_t SB, float a_d, float a_r, float
     for (int q = 0; q < 9; q++) {
         double v = 0.0;
         for (uint32_t i = threadIdx.x; i < B; i += kT) v += q < 6 ? frame_parts[i].s[q] : (double)frame_parts[i].a[q - 6];
-        s[q] = block_sum(v, sh);
+        s[q] = block_sum<kT>(v, sh);
     }
     {
         double v = 0.0;
         for (uint32_t i = threadIdx.x; i < SB; i += kT) v += ssim_parts[i];
-        s[9] = block_sum(v, sh);
+        s[9] = block_sum<kT>(v, sh);
     }
     if (threadIdx.x != 0) return;
     const uint32_t h = tot.nvalid ? tot.rmax - tot.rmin + 1 : 0u, w = tot.nvalid ? tot.cmax - tot.cmin + 1 : 0u;

@@ -197,20 +197,6 @@ k_pts_resolve(const uint32_t *__restrict__ counts, uint32_t cap, uint32_t S, con
     (dir ? idx1 : idx0)[q] = (int32_t)(uint32_t)key;
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-    return v;
-}
-// sum over the workgroup in a fixed order; every thread receives it.  `sh`: kT / 64 doubles of LDS.
-__device__ __forceinline__ double block_sum_f64(double v, double *sh) {
-    v = wave_sum_f64(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
 __global__ void __launch_bounds__(kT)
 k_pts_finalize(const float *__restrict__ dist0, const float *__restrict__ dist1, const uint32_t *__restrict__ counts,
                uint32_t cap, float threshold, double *__restrict__ acc, double *__restrict__ history, uint32_t max_frames) {
@@ -227,8 +213,8 @@ k_pts_finalize(const float *__restrict__ dist0, const float *__restrict__ dist1,
                 s += (double)v;
                 b += v < threshold ? 1.0 : 0.0;
             }
-        sum[c] = block_sum_f64(s, sh);
-        below[c] = block_sum_f64(b, sh);
+        sum[c] = block_sum<kT>(s, sh);
+        below[c] = block_sum<kT>(b, sh);
     }
     if (threadIdx.x != 0) return;
     double row[LNH_PTS_SLOTS];

@@ -249,7 +249,7 @@ class LidarLossOptionsC(C.Structure):
 
 
 def loss_options(o, px, py, scale, huber_delta, alpha_d, alpha_r, alpha_i, alpha_grad):
-    """The C struct of a nerf.train_step.LidarLossOptions for one call."""
+    """The C struct of a nerf.loss.LidarLossOptions for one call."""
     flags = ((LOSS_SOBEL if o.sobel_grad else 0) | (LOSS_GRAD if o.grad_loss else 0) |
              (LOSS_GRAD_NORM_SMOOTH if o.grad_norm_smooth else 0) | (LOSS_SPATIAL if o.spatial_smooth else 0) |
              (LOSS_TV if o.tv_loss else 0))

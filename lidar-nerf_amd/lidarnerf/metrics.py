@@ -181,7 +181,7 @@ class FrameEvaluator:
             pred_intensity, pred_depth, mask = ev.update(out["image_lidar"], out["depth_lidar"], gt)   # no host read
         numbers = ev.measure()                                                                          # ONE copy to the host
 
-    alphas = (alpha_d, alpha_r, alpha_i); loss_options: a nerf.train_step.LidarLossOptions (its three per-ray criteria;
+    alphas = (alpha_d, alpha_r, alpha_i); loss_options: a nerf.loss.LidarLossOptions (its three per-ray criteria;
     huber's delta is 0.2 * scale); nerf_mvl: ground-truth ray-drop -1 marks pixels outside the sensor's window; max_frames:
     rows of per-frame history kept (later frames still count in the means).  update() allocates its three output images
     and nothing else after the first call, and never synchronises: it can be captured in a torch.cuda.graph after one
@@ -189,7 +189,7 @@ class FrameEvaluator:
 
     def __init__(self, H, W, scale, intensity_inv_scale=1.0, alphas=(1000.0, 1.0, 10.0), loss_options=None, nerf_mvl=False,
                  max_frames=1024):
-        from .nerf.train_step import LidarLossOptions
+        from .nerf.loss import LidarLossOptions
         self.H, self.W, self.scale = int(H), int(W), float(scale)
         if self.H < 1 or self.W < 1:
             raise ValueError(f"FrameEvaluator: H ({H}) and W ({W}) must be positive")

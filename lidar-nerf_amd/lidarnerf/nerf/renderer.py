@@ -273,7 +273,7 @@ class NeRFRenderer(nn.Module):
         dev = rays_o.device
         static = getattr(self, "_static_march", None)
         if self.training and static is not None:
-            # LidarTrainer's captured step (train_step.py, graph=True): a fixed counter buffer and a fixed sample capacity —
+            # LidarTrainer's captured step (captured_step.py, graph=True): a fixed counter buffer and a fixed sample capacity —
             # this Python runs at capture only; the trainer copies the counter into the ring and advances local_step per replay
             counter, mean_count = static
         elif self.training:

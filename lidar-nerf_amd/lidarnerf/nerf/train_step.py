@@ -3,234 +3,13 @@ of train_one_epoch (1206-1226): zero_grad -> autocast(render + loss) -> scaled b
 scaler.step(optimizer) -> scaler.update() -> lr_scheduler.step().  Only the LiDAR branch exists in the reference
 path (opt.enable_lidar is forced True, main_lidarnerf.py:229)."""
 import contextlib
-import dataclasses
-import os
 
 import torch
 
-from .. import parallel
-
-
-_CRITERIA = ("l1", "mse", "huber", "bce")
-_GRAD_CRITERIA = _CRITERIA + ("cos",)
-
-
-@dataclasses.dataclass(frozen=True)
-class LidarLossOptions:
-    """The loss options of the reference CLI (main_lidarnerf.py:46-60, 92-103; criteria built at 330-342), under its names.
-    The defaults are the loss the fast trainer has always trained: L1 depth, MSE ray-drop and intensity, and on patch
-    epochs the non-Sobel L1 structural-gradient term.  alpha_d / alpha_r / alpha_i / alpha_grad and scale stay arguments of
-    the callers (LidarTrainer's alpha_* and scale).  `huber` is HuberLoss(delta=0.2*scale), `bce` BCEWithLogitsLoss on
-    the prediction as given, `cos` (depth_grad_loss only) 1 - CosineSimilarity per patch."""
-    depth_loss: str = "l1"
-    raydrop_loss: str = "mse"
-    intensity_loss: str = "mse"
-    depth_grad_loss: str = "l1"
-    grad_loss: bool = True
-    sobel_grad: bool = False
-    grad_norm_smooth: bool = False
-    spatial_smooth: bool = False
-    tv_loss: bool = False
-    alpha_grad_norm: float = 1.0
-    alpha_spatial: float = 0.1
-    alpha_tv: float = 1.0
-
-    def __post_init__(self):
-        for name in ("depth_loss", "raydrop_loss", "intensity_loss", "depth_grad_loss"):
-            allowed = _GRAD_CRITERIA if name == "depth_grad_loss" else _CRITERIA
-            v = getattr(self, name)
-            if v not in allowed:
-                raise ValueError(f"LidarLossOptions: {name}={v!r} is not one of {', '.join(allowed)}")
-        for name in ("grad_loss", "sobel_grad", "grad_norm_smooth", "spatial_smooth", "tv_loss"):
-            object.__setattr__(self, name, bool(getattr(self, name)))
-        for name in ("alpha_grad_norm", "alpha_spatial", "alpha_tv"):
-            object.__setattr__(self, name, float(getattr(self, name)))
-
-    @classmethod
-    def from_opt(cls, opt):
-        """From a reference argparse namespace (main_lidarnerf.py); an attribute it lacks keeps this class's default."""
-        return cls(**{f.name: getattr(opt, f.name, f.default) for f in dataclasses.fields(cls)})
-
-    @property
-    def is_default(self):
-        return self == _DEFAULT_OPTIONS
-
-    def huber_delta(self, scale):
-        return 0.2 * float(scale)  # main_lidarnerf.py:336
-
-
-_DEFAULT_OPTIONS = LidarLossOptions()
-
-
-def _criterion(name, scale):
-    """main_lidarnerf.py:330-342's loss_dict entry (reduction 'none')."""
-    if name == "mse":
-        return torch.nn.MSELoss(reduction="none")
-    if name == "l1":
-        return torch.nn.L1Loss(reduction="none")
-    if name == "bce":
-        return torch.nn.BCEWithLogitsLoss(reduction="none")
-    if name == "huber":
-        if scale is None:
-            raise ValueError("the huber criterion needs the scene scale (delta = 0.2 * scale)")
-        return torch.nn.HuberLoss(reduction="none", delta=0.2 * float(scale))
-    return torch.nn.CosineSimilarity()
-
-
-def lidar_loss(outputs, images_lidar, alpha_d=1000.0, alpha_r=1.0, alpha_i=10.0, *, options=None, scale=None):
-    """utils.py:712-746; by default with the default criteria (L1 depth, MSE ray-drop, MSE intensity;
-    main_lidarnerf.py:330-342), `options` (LidarLossOptions) selects others (`scale`: the huber delta's).
-    images_lidar [B,N,3] = (raydrop, intensity, depth).  Returns (loss, pred_depth, gt_depth)."""
-    gt_raydrop = images_lidar[..., 0]
-    gt_intensity = images_lidar[..., 1] * gt_raydrop
-    gt_depth = images_lidar[..., 2] * gt_raydrop
-    pred_raydrop = outputs["image_lidar"][..., 0]
-    pred_intensity = outputs["image_lidar"][..., 1] * gt_raydrop
-    pred_depth = outputs["depth_lidar"] * gt_raydrop
-    if options is None or options.is_default:
-        per_ray = (alpha_d * (pred_depth - gt_depth).abs() + alpha_r * (pred_raydrop - gt_raydrop) ** 2
-                   + alpha_i * (pred_intensity - gt_intensity) ** 2)
-    else:
-        per_ray = (alpha_d * _criterion(options.depth_loss, scale)(pred_depth, gt_depth)
-                   + alpha_r * _criterion(options.raydrop_loss, scale)(pred_raydrop, gt_raydrop)
-                   + alpha_i * _criterion(options.intensity_loss, scale)(pred_intensity, gt_intensity))
-    return per_ray.mean(), pred_depth, gt_depth
-
-
-class _FusedLidarLoss(torch.autograd.Function):
-    """lidar_loss as ONE kernel that also emits d loss / d (depth, image); backward only scales by the upstream scalar."""
-
-    @staticmethod
-    def forward(ctx, depth, image, gt, ad, ar, ai, patch=None, grad_scale=None, options=None, scale=None):
-        # patch = (px, py, scale, alpha_grad): the reference's patch epochs, structural-gradient term included
-        # grad_scale (device scalar): the kernel multiplies the gradients it emits by it — the caller then starts
-        # backward() from a gradient of ONE (LidarTrainer: the loss scale, without an element-wise launch in backward)
-        import ctypes as C
-
-        from .. import _hip
-        n = depth.numel()
-        depth, image, gt = depth.reshape(n).float().contiguous(), image.reshape(n, 2).float().contiguous(), \
-            gt.reshape(n, 3).float().contiguous()
-        loss = torch.empty((), dtype=torch.float32, device=depth.device)
-        grads = torch.empty(3 * n, dtype=torch.float32, device=depth.device)  # [d/d depth (n) | d/d image (n, 2)]
-        gs = None if grad_scale is None else grad_scale.data_ptr()
-        if options is not None and not options.is_default:
-            # lnh_lidar_loss_ex: every other option set (the default one keeps the two kernels below)
-            _hip.require_version(102, "LidarLossOptions other than the defaults (lnh_lidar_loss_ex)")
-            px, py, pscale, ag = patch if patch is not None else (1, 1, scale, 0.0)
-            hscale = scale if scale is not None else pscale
-            if hscale is None and "huber" in (options.depth_loss, options.raydrop_loss, options.intensity_loss,
-                                              options.depth_grad_loss):
-                raise ValueError("the huber criterion needs the scene scale (delta = 0.2 * scale)")
-            opts = _hip.loss_options(options, px, py, 1.0 if pscale is None else pscale,
-                                     0.0 if hscale is None else options.huber_delta(hscale), ad, ar, ai, ag)
-            ws = torch.empty(int(_hip.lib().lnh_lidar_loss_ex_workspace_bytes(n)), dtype=torch.uint8, device=depth.device)
-            _hip.call("lnh_lidar_loss_ex", depth.data_ptr(), image.data_ptr(), gt.data_ptr(), n, C.byref(opts), gs,
-                      ws.data_ptr(), ws.numel(), loss.data_ptr(), grads.data_ptr(), grads.data_ptr() + 4 * n)
-        elif patch is None:
-            _hip.call("lnh_lidar_loss", depth.data_ptr(), image.data_ptr(), gt.data_ptr(), n, float(ad), float(ar), float(ai),
-                      gs, loss.data_ptr(), grads.data_ptr(), grads.data_ptr() + 4 * n)
-        else:
-            px, py, scale, ag = patch
-            _hip.call("lnh_lidar_loss_patch", depth.data_ptr(), image.data_ptr(), gt.data_ptr(), n, int(px), int(py),
-                      float(scale), float(ad), float(ar), float(ai), float(ag), gs, loss.data_ptr(), grads.data_ptr(),
-                      grads.data_ptr() + 4 * n)
-        ctx.save_for_backward(grads)
-        ctx.n, ctx.prescaled = n, grad_scale is not None
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        (grads,) = ctx.saved_tensors
-        # (pre-scaled gradients: the contract of grad_scale is that backward() starts from ONE)
-        scaled = grads if ctx.prescaled else grads * g  # one launch for both
-        return scaled[:ctx.n], scaled[ctx.n:].view(ctx.n, 2), None, None, None, None, None, None, None, None
-
-
-class _ScaleGrad(torch.autograd.Function):
-    """Identity whose gradient is multiplied by a device scalar (the loss scale, for the loss paths without a kernel)."""
-
-    @staticmethod
-    def forward(ctx, x, scale):
-        ctx.save_for_backward(scale)
-        return x.view_as(x)
-
-    @staticmethod
-    def backward(ctx, g):
-        return g * ctx.saved_tensors[0], None
-
-
-def fused_lidar_loss(outputs, images_lidar, alpha_d=1000.0, alpha_r=1.0, alpha_i=10.0, patch=None, grad_scale=None,
-                     options=None, scale=None):
-    """lidar_loss (+ patch_gradient_loss when patch = (px, py, scale, alpha_grad)) through the single-launch kernel (GPU
-    tensors only); same value and gradients.  grad_scale (device scalar): the gradients come out multiplied by it and
-    backward() must then be started from a gradient of one.  options (LidarLossOptions): any other loss option set of the
-    reference CLI (lnh_lidar_loss_ex; `scale`, the huber delta's, defaults to the patch's)."""
-    depth, image = outputs["depth_lidar"], outputs["image_lidar"]
-    loss = _FusedLidarLoss.apply(depth.reshape(-1), image.reshape(-1, 2), images_lidar, alpha_d, alpha_r, alpha_i, patch,
-                                 grad_scale, options, scale)
-    return loss
-
-
-_SOBEL_X = ((-1.0, 0.0, 1.0), (-2.0, 0.0, 2.0), (-1.0, 0.0, 1.0))
-_SOBEL_Y = ((-1.0, -2.0, -1.0), (0.0, 0.0, 0.0), (1.0, 2.0, 1.0))
-
-
-def patch_gradient_loss(pred_depth, gt_depth, gt_raydrop, px, py, scale, alpha_grad=100.0, *, options=None):
-    """utils.py:760-876 (grad_loss, non-sobel): |dx| of the prediction vs the SIGNED dx of the ground truth, masked to
-    |gt dx| < 0.01 m and returned rays; only the x term enters the loss (the y terms are computed but unused).
-    `options` (LidarLossOptions): the reference's other patch terms — Sobel gradients, the smoothness terms, another
-    depth_grad_loss criterion, grad_loss off — term for term as utils.py:760-876 writes them."""
-    if options is None or options.is_default:
-        pred = pred_depth.reshape(-1, 1, px, py) / scale
-        gt = gt_depth.reshape(-1, 1, px, py) / scale
-        rd = gt_raydrop.reshape(-1, 1, px, py)
-        pred_gx = (pred[..., :-1] - pred[..., 1:]).abs()
-        gt_gx = gt[..., :-1] - gt[..., 1:]
-        mask = rd[..., :-1] * (gt_gx.abs() < 0.01)
-        return alpha_grad * (pred_gx * mask - gt_gx * mask).abs().mean()
-    o = options
-    F = torch.nn.functional
-
-    def sobel(x, k):
-        return F.conv2d(x, torch.tensor(k, dtype=x.dtype, device=x.device)[None, None], padding=1)
-
-    pred = pred_depth.reshape(-1, px, py, 1).permute(0, 3, 1, 2).contiguous() / scale
-    if o.sobel_grad:
-        pred_gx, pred_gy = sobel(pred, _SOBEL_X), sobel(pred, _SOBEL_Y)
-    else:
-        pred_gy = (pred[:, :, :-1, :] - pred[:, :, 1:, :]).abs()
-        pred_gx = (pred[:, :, :, :-1] - pred[:, :, :, 1:]).abs()
-    dy, dx = pred_gy.abs(), pred_gx.abs()
-    loss = pred.new_zeros(())
-    if o.grad_norm_smooth:
-        loss = loss + o.alpha_grad_norm * (torch.exp(-dx).mean() + torch.exp(-dy).mean())
-    if o.spatial_smooth:
-        loss = loss + o.alpha_spatial * ((dx ** 2).mean() + (dy ** 2).mean())
-    if o.tv_loss:
-        loss = loss + o.alpha_tv * (dx.mean() + dy.mean())
-    if o.grad_loss:
-        gt = gt_depth.reshape(-1, px, py, 1).permute(0, 3, 1, 2).contiguous() / scale
-        rd = gt_raydrop.reshape(-1, px, py, 1).permute(0, 3, 1, 2).contiguous()
-        gt_gx = sobel(gt, _SOBEL_X) if o.sobel_grad else gt[:, :, :, :-1] - gt[:, :, :, 1:]
-        mask = (rd if o.sobel_grad else rd[:, :, :, :-1]) * torch.where(gt_gx.abs() < 0.01, 1, 0)
-        crit = _criterion(o.depth_grad_loss, scale)
-        if o.depth_grad_loss == "cos":
-            patches = pred_gx.shape[0]
-            grad = 1 - crit((pred_gx * mask).reshape(patches, -1), (gt_gx * mask).reshape(patches, -1))
-        else:
-            grad = crit(pred_gx * mask, gt_gx * mask)
-        loss = loss + alpha_grad * grad.mean()
-    return loss
-
-
-def _hip_consts():
-    from .. import _hip
-    return _hip
-
-
-# rungs per octave of the captured step's sample-capacity ladder (LidarTrainer._graph_capacity)
-_LADDER_RUNGS_PER_OCTAVE = int(os.environ.get("LNH_GRAPH_LADDER", "8"))
+from .. import _hip, parallel
+from . import captured_step, checkpoint
+from .loss import (_CRITERIA, _DEFAULT_OPTIONS, _GRAD_CRITERIA, _SOBEL_X, _SOBEL_Y, LidarLossOptions, _criterion,  # noqa: F401
+                   _FusedLidarLoss, _ScaleGrad, fused_lidar_loss, lidar_loss, patch_gradient_loss)  # (callers import them from here)
 
 
 class LidarTrainer:
@@ -293,19 +72,18 @@ class LidarTrainer:
             # the fused optimizer steps EVERY parameter: the table from its fp16 gradient and the other tensors (the MLP
             # weights: a handful of small fp32 matrices) in the same launch
             if tp is not None and tp.dtype == torch.float32 and tp.is_contiguous() and tp.numel() % 4 == 0 and \
-                    len(others) <= _hip_consts().TRAIN_MAX_SMALL and \
+                    len(others) <= _hip.TRAIN_MAX_SMALL and \
                     all(p.dtype == torch.float32 and p.is_contiguous() and p.is_cuda for p in others):
-                H = _hip_consts()
                 self.table = tp
                 params = [dict(g, params=[p for p in g["params"] if p is not tp]) for g in params]
                 self.t_m, self.t_v = torch.zeros_like(tp), torch.zeros_like(tp)
                 # every scalar of the optimizer in ONE device buffer (include/lidarnerf_hip.h LNH_TS_*): a captured step
                 # needs no host value.  loss_scale / growth_tracker / t_steps are views of it (the names rounds 2-4 used).
-                self.opt_state = torch.zeros(H.TRAIN_STATE_FLOATS, dtype=torch.float32, device=tp.device)
-                self.opt_state[H.TS_SCALE] = 65536.0
-                self.loss_scale = self.opt_state[H.TS_SCALE:H.TS_SCALE + 1].view(())
-                self.growth_tracker = self.opt_state[H.TS_GROWTH:H.TS_GROWTH + 1].view(())
-                self.t_steps, self.t_flip = [self.opt_state[H.TS_T_NEXT:H.TS_T_NEXT + 1].view(())] * 2, 0
+                self.opt_state = torch.zeros(_hip.TRAIN_STATE_FLOATS, dtype=torch.float32, device=tp.device)
+                self.opt_state[_hip.TS_SCALE] = 65536.0
+                self.loss_scale = self.opt_state[_hip.TS_SCALE:_hip.TS_SCALE + 1].view(())
+                self.growth_tracker = self.opt_state[_hip.TS_GROWTH:_hip.TS_GROWTH + 1].view(())
+                self.t_steps, self.t_flip = [self.opt_state[_hip.TS_T_NEXT:_hip.TS_T_NEXT + 1].view(())] * 2, 0
                 self._one = torch.ones((), dtype=torch.float32, device=tp.device)
                 self._lr0, self._iters = float(lr), float(iters)
                 self.small = others
@@ -328,24 +106,12 @@ class LidarTrainer:
         params = [g for g in params if len(g["params"])]
         # the reference's groups differ in nothing but their parameter lists (network.py get_params: every group at `lr`):
         # step them as ONE group — torch launches its fused Adam once per group — and keep the reference's grouping for
-        # the checkpoint layout only (_optimizer_state_ref_layout)
+        # the checkpoint layout only (nerf/checkpoint.py)
         if len(params) > 1 and all({k: v for k, v in g.items() if k != "params"} ==
                                    {k: v for k, v in params[0].items() if k != "params"} for g in params):
             params = [dict(params[0], params=[p for g in params for p in g["params"]])]
-        # graph=True (fused chain + fused table optimizer): the whole step — (march,) render chain, loss, backward, (the
-        # gradient exchange,) both optimizers, loss-scale update — is captured in a hipGraph per (batch shape, sample
-        # capacity) and replayed (_step_graphed).  Built for occupancy-grid sampling; the dense step (no data-dependent sizes
-        # at all) captures the same way and then costs the host 0.05 ms instead of ~0.8 — it is GPU-bound either way on the
-        # fast hosts of this build, a slower host is not (3.42 against 2.21 ms).  The step is ~45 launches over
-        # ~0.4 M samples: eager, the host cannot issue them as fast as the GPU retires them (profiles/r04_bench_nerfmvl.json:
-        # 1.0 ms of host time per 0.7 ms of kernels).  What a capture freezes — kernel arguments — must not change between
-        # replays, so the learning rate becomes a device scalar (torch's capturable Adam, lnh_adam_table_step_dlr) and the
-        # marcher's sample capacity comes from a ladder of sizes (_graph_capacity; the reference sizes it to the running
-        # mean rounded to 128, raymarching.py:223-229: a larger buffer drops fewer rays on overflow, nothing else changes).
-        # Data parallel (round 5): under RCCL (backend "nccl") the collectives of the step — the windowed fp16 all-reduce
-        # or reduce-scatter / all-gather of the table, the MLP gradients, the found-inf MAX — are captured with it, each on
-        # RCCL's own stream inside the graph, so N ranks replay N identical graphs and none of them is host-bound (eight
-        # processes share the 16-CPU quota of a box).  gloo cannot be captured (its collectives synchronise with the host).
+        # graph=True: the whole step is captured in a hipGraph per (batch shape, sample capacity) and replayed — what that
+        # takes and what it freezes: the docstring of nerf/captured_step.py
         self.graph = bool(graph and self.table is not None and on_gpu and (not self.dp or parallel.backend() == "nccl"))
         if graph and not self.graph:
             raise RuntimeError("LidarTrainer(graph=True): the captured step needs the fused chain with the fused table "
@@ -423,9 +189,7 @@ class LidarTrainer:
         """One iteration with the fused optimizer: render + loss + backward, (the gradient exchange,) and the optimizer as two
         launches — lnh_train_check (finite check of every gradient, 1 / scale, the learning rate of this step) and
         lnh_train_step (Adam on the table and on the small tensors, GradScaler's skip / scale update, the step counters)."""
-        from .. import _hip
         from .fused import table16_of
-        H = _hip
         tp, st = self.table, self.opt_state
         loss = self._forward_backward(rays_o, rays_d, images_lidar, patch)
         # --- data parallel: the small gradients.  The fused chain leaves all of them in ONE arena (views): that tensor goes
@@ -453,10 +217,10 @@ class LidarTrainer:
                     raise RuntimeError("fused optimizer: gradients of the small parameters must be contiguous fp32")
                 self._small_stepped.add(id(p))
         n_small = len(self.small)
-        gp = H.ptr_array([None if g is None else g.data_ptr() for g in grads])
-        pp = H.ptr_array([p.data_ptr() for p in self.small])
-        nn_ = H.u32_array([p.numel() for p in self.small])
-        cast = lambda arr: H.C.cast(arr, H.C.c_void_p)
+        gp = _hip.ptr_array([None if g is None else g.data_ptr() for g in grads])
+        pp = _hip.ptr_array([p.data_ptr() for p in self.small])
+        nn_ = _hip.u32_array([p.numel() for p in self.small])
+        cast = lambda arr: _hip.C.cast(arr, _hip.C.c_void_p)
         if small_handle is not None:
             small_handle.wait()
         check = lambda ptr, n, first: _hip.call("lnh_train_check", st.data_ptr(), ptr, n, cast(gp), cast(nn_),
@@ -472,7 +236,7 @@ class LidarTrainer:
                 check(mine.data_ptr() if rows else None, rows * 2, i == 0)
             # every rank has looked at its own rows only: the skip / back-off decision must be the same everywhere (the stamp
             # of a step is the same number on every rank, so MAX keeps it)
-            dist.all_reduce(st[H.TS_FOUND:H.TS_FOUND + 1], op=dist.ReduceOp.MAX)
+            dist.all_reduce(st[_hip.TS_FOUND:_hip.TS_FOUND + 1], op=dist.ReduceOp.MAX)
             shadow = table16_of(tp)  # (re-cast first if somebody wrote the parameter since the last step)
             _hip.call("lnh_train_step", st.data_ptr(), None, None, None, None, None, 0, *step_args)
             self._step_table_shards(shards, shadow)
@@ -490,141 +254,28 @@ class LidarTrainer:
 
     def steps_taken(self):
         """Number of optimizer steps applied so far (skipped steps — inf / nan gradients — do not count).  Synchronises."""
-        return int(self.opt_state[_hip_consts().TS_T_NEXT]) if self.table is not None else None
+        return int(self.opt_state[_hip.TS_T_NEXT]) if self.table is not None else None
 
     def _sync_counters(self, steps=None):
         """After a load: the device-side counters follow the host's (scheduler position; optionally the Adam step count)."""
-        H = _hip_consts()
         it = float(self.scheduler.last_epoch)
-        self.opt_state[H.TS_IT], self.opt_state[H.TS_IT_NEXT] = it, it
+        self.opt_state[_hip.TS_IT], self.opt_state[_hip.TS_IT_NEXT] = it, it
         # the inf / nan stamp is `it + 1` of the step that saw it and relies on `it` only ever growing: after a rewind a stale
         # stamp would match again when training reaches that iteration (a finite step skipped, the loss scale halved)
-        self.opt_state[H.TS_FOUND], self.opt_state[H.TS_SKIPPED] = 0.0, 0.0
+        self.opt_state[_hip.TS_FOUND], self.opt_state[_hip.TS_SKIPPED] = 0.0, 0.0
         if steps is not None:
-            self.opt_state[H.TS_T], self.opt_state[H.TS_T_NEXT] = float(steps), float(steps)
+            self.opt_state[_hip.TS_T], self.opt_state[_hip.TS_T_NEXT] = float(steps), float(steps)
 
-    # ---- the captured step (graph=True)
+    # ---- the captured step (graph=True; nerf/captured_step.py)
     def _graph_capacity(self):
-        """Sample capacity of the marcher for a captured step: the running mean of the recent marches (renderer.py
-        update_extra_state) rounded UP to the next of a geometric ladder of capacities (ratio 2^(1/8), multiples of 1024;
-        LNH_GRAPH_LADDER = rungs per octave): while the occupancy grid is still settling the mean swings by tens of percent
-        from one grid update to the next (measured on the NeRF-MVL-shaped bench: 107 K .. 393 K over 300 steps), and every
-        distinct capacity is one capture (0.7 .. 0.9 ms since the trainer captures without emptying the allocator's cache) —
-        the ladder has ~15 rungs over that range, each captured once and kept.  On average 4 % of the buffer is padding (zero
-        samples the chain runs over; 9 % with the 2^(1/4) ladder of round 4, when a capture cost 70 ms: 0.500 against
-        0.516 ms per step at 66 .. 69 samples per ray).  0 while there is no mean yet (the first 16 steps march into N x 1024
-        buffers and read the count back)."""
-        mc = int(self.model.mean_count)
-        if mc <= 0:
-            return 0
-        import math
-        per = _LADDER_RUNGS_PER_OCTAVE
-        rung = math.ceil(per * math.log2(max(mc, 1024) / 1024.0) - 1e-9)
-        return int(math.ceil(1024 * 2 ** (rung / per) / 1024.0)) * 1024
-
-    def _step_graphed(self, rays_o, rays_d, images_lidar, patch):
-        model = self.model
-        # (the dense step has no sample buffers to size: one graph per batch shape)
-        cap = self._graph_capacity() if self.occupancy else -1
-        if cap == 0 or not self._graph_warm:
-            # eager: no sample mean yet / the very first step (it takes every lazy initialisation — workspaces, kernel
-            # attributes, optimizer state — out of the captures that follow).
-            # (detached: a caller holding the loss would keep this step's autograd graph — and its AccumulateGrad nodes,
-            #  bound to the eager stream — alive into the capture that follows)
-            self._graph_warm.add("eager")
-            model._static_march = None
-            return self._step_fused_table(rays_o, rays_d, images_lidar, patch).detach()
-        # what a capture bakes in as kernel arguments is part of the key: the loss weights, the scene scale, the render
-        # arguments (a change of any of them captures a new step instead of silently replaying the old values)
-        key = (tuple(rays_o.shape), tuple(images_lidar.shape), tuple(patch), tuple(self.alpha), float(self.scale),
-               tuple(sorted((k, repr(v)) for k, v in self.render_kwargs.items())), self.loss_options, cap)
-        tp = self.table
-        if getattr(tp, "_lnh_table16_version", None) != tp._version:
-            # somebody wrote the fp32 table through torch since the last step (model.load_state_dict, a manual
-            # re-initialisation): a replay never runs table16_of, so the fp16 compute copy is re-cast here — the captured
-            # kernels read it in place
-            from .fused import table16_of
-            table16_of(tp)
-        ent = self._graphs.get(key)
-        if ent is None:
-            dev = self.table.device
-            if self._graph_pool is None:
-                # one memory pool for all captured steps: they never run concurrently and none reads what another left
-                # behind, so a later capture may reuse what an earlier one freed (and no capture after the largest pays
-                # for fresh device allocations)
-                self._graph_pool = torch.cuda.graph_pool_handle()
-            ent = {"rays_o": torch.empty_like(rays_o), "rays_d": torch.empty_like(rays_d),
-                   "gt": torch.empty_like(images_lidar), "counter": torch.zeros(2, dtype=torch.int32, device=dev),
-                   "graph": torch.cuda.CUDAGraph()}
-            for k, src in (("rays_o", rays_o), ("rays_d", rays_d), ("gt", images_lidar)):
-                ent[k].copy_(src)
-            if self.occupancy:
-                model._static_march = (ent["counter"], cap - 128)  # (march_rays_train adds its 128-alignment on top)
-            try:
-                # capture_begin / capture_end by hand: torch.cuda.graph's context manager empties the allocator's cache
-                # first (every cached block back to the driver: the workspaces of this step and of the evaluation pass
-                # are re-allocated afterwards), which made a capture cost 70-80 ms — 140 steps of the occupancy-grid
-                # workload, whose sample capacity moves to a new rung (a new capture) whenever the grid has changed enough
-                torch.cuda.synchronize()
-                import time
-                if self.dp:
-                    # Data parallel: ProcessGroupNCCL's watchdog thread keeps every EAGER collective in a list until one of
-                    # its sweeps (every 100 ms) finds the work's end event complete.  RCCL's stream joins the capture below,
-                    # and hipEventQuery on an event of a stream that is capturing fails with hipErrorCapturedEvent — in the
-                    # watchdog thread, which takes the process down ("failed once in a dozen runs" in round 5, 1 of 50 in
-                    # round 6's loop: the chance that a sweep falls into the 1-2 ms of a capture; with the capture stalled for
-                    # 300 ms it is every run, profiles/r06_rccl_loop.txt).  The collectives of the eager steps have finished
-                    # (the synchronize above): give the watchdog two sweeps to drop them, so that it has nothing to poll while
-                    # this thread captures.  Collectives issued DURING a capture are never put on that list.
-                    time.sleep(float(os.environ.get("LNH_CAPTURE_DRAIN_MS", "250")) * 1e-3)
-                t_cap = time.perf_counter()
-                if self._capture_stream is None:
-                    self._capture_stream = torch.cuda.Stream()
-                with torch.cuda.stream(self._capture_stream):
-                    # (a capture that polices every thread of the process would trip over the watchdog's other HIP calls)
-                    ent["graph"].capture_begin(self._graph_pool,
-                                               capture_error_mode="thread_local" if self.dp else "global")
-                    try:
-                        ent["loss"] = self._step_fused_table(ent["rays_o"], ent["rays_d"], ent["gt"], patch).detach()
-                        if os.environ.get("LNH_DEBUG_CAPTURE_STALL_MS"):  # (diagnosis only: widens the window above)
-                            time.sleep(float(os.environ["LNH_DEBUG_CAPTURE_STALL_MS"]) * 1e-3)
-                    finally:
-                        ent["graph"].capture_end()
-                # the gradient and the scale it carries live in THIS graph's buffers: table_grad() must see the ones of
-                # the graph that was replayed last, not of the one that was captured last
-                ent["g16"] = tp._lnh_grad16
-                self.capture_ms.append(round((time.perf_counter() - t_cap) * 1e3, 2))  # (host time of this capture)
-            except Exception as e:  # noqa: BLE001 — a capture that does not go through must not cost the run
-                # (nothing of a captured step has executed: the state is what it was.)  Launch by launch from here on; the
-                # reason stays readable (bench.py reports it).
-                model._static_march = None
-                self.graph, self.graph_error = False, f"{type(e).__name__}: {e}"
-                return self._step_fused_table(rays_o, rays_d, images_lidar, patch).detach()
-            finally:
-                model._static_march = None
-            try:
-                ent["graph"].replay()
-            except Exception as e:  # noqa: BLE001 — a graph the runtime captured and then refuses to launch (same rule)
-                self.graph, self.graph_error = False, f"replay: {type(e).__name__}: {e}"
-                return self._step_fused_table(rays_o, rays_d, images_lidar, patch).detach()
-            self._graphs[key] = ent
-        else:
-            torch._foreach_copy_([ent["rays_o"], ent["rays_d"], ent["gt"]], [rays_o, rays_d, images_lidar])  # one launch
-            ent["graph"].replay()
-        tp._lnh_grad16 = ent["g16"]
-        if self.occupancy:
-            model.step_counter[model.local_step % 16].copy_(ent["counter"])
-            model.local_step += 1
-        self.scheduler.step()
-        return ent["loss"].clone()  # (the graphs share a pool: the next replay of another one may reuse this memory)
+        """Sample capacity of the marcher for a captured step (captured_step.graph_capacity); 0 while there is no mean yet."""
+        return captured_step.graph_capacity(self)
 
     def _step_table_shards(self, shards, shadow):
         """Sharded table optimizer: Adam on this rank's rows of every level window (learning rate, 1 / scale, the skip flag
         and the step counter read from the optimizer's device scalars, which lnh_train_check / lnh_train_step have set), then
         the all-gather of the fp16 compute copy (the only part of the table the next forward pass reads)."""
-        from .. import _hip
         import torch.distributed as dist
-        H = _hip
         tp, st = self.table, self.opt_state
         sp = lambda i: st.data_ptr() + 4 * i
         rank = dist.get_rank()
@@ -635,8 +286,8 @@ class LidarTrainer:
             if rows:
                 o = row0 * 2  # element offset of the shard in the [rows, 2] table
                 _hip.call("lnh_adam_table_step_dlr", tp.data_ptr() + 4 * o, self.t_m.data_ptr() + 4 * o,
-                          self.t_v.data_ptr() + 4 * o, mine.data_ptr(), flat16.data_ptr() + 2 * o, rows * 2, sp(H.TS_LR), 0.9,
-                          0.99, 1e-15, sp(H.TS_INV_TABLE), sp(H.TS_SKIPPED), sp(H.TS_T), sp(H.TS_T_NEXT))
+                          self.t_v.data_ptr() + 4 * o, mine.data_ptr(), flat16.data_ptr() + 2 * o, rows * 2, sp(_hip.TS_LR), 0.9,
+                          0.99, 1e-15, sp(_hip.TS_INV_TABLE), sp(_hip.TS_SKIPPED), sp(_hip.TS_T), sp(_hip.TS_T_NEXT))
             mine16 = torch.zeros_like(mine)
             if rows:
                 mine16[:rows] = table16[row0:row0 + rows]
@@ -771,8 +422,7 @@ class LidarTrainer:
             handle.wait()
         div = float(getattr(self.table, "_lnh_grad16_div", 1))
         # (the scale the backward ran with — the optimizer kernel has already moved loss_scale on growth / backoff steps)
-        H = _hip_consts()
-        return g16.float().reshape(self.table.shape) / (self.opt_state[H.TS_LAST_SCALE] * div)
+        return g16.float().reshape(self.table.shape) / (self.opt_state[_hip.TS_LAST_SCALE] * div)
 
     def state_dict(self):
         """Everything a resume needs: torch optimizer / scheduler / scaler state plus — fused table optimizer — the
@@ -794,10 +444,9 @@ class LidarTrainer:
 
     def load_state_dict(self, sd):
         self.optimizer.load_state_dict(sd["optimizer"])
-        self._after_optimizer_load()
+        captured_step.after_optimizer_load(self)
         self.scheduler.load_state_dict(sd["scheduler"])
         self.scaler.load_state_dict(sd["scaler"])
-        self._pending_steps = None
         ft = sd.get("fused_table")
         if (ft is None) != (self.table is None):
             raise RuntimeError("LidarTrainer.load_state_dict: checkpoint and trainer disagree on the fused table optimizer")
@@ -814,131 +463,7 @@ class LidarTrainer:
         if self.ema is not None and sd.get("ema") is not None:
             self.ema.load_state_dict(sd["ema"])
 
-    # ---- checkpoints in the reference Trainer's format (lidarnerf/nerf/utils.py:1449-1568)
-    def _optimizer_state_ref_layout(self):
-        """torch.optim.Adam.state_dict() as the reference's optimizer would write it: one entry per parameter of
-        model.get_params(lr) in order, the fused table optimizer's moments / step count included."""
-        own = self.optimizer.state_dict()
-        own_ids = {id(p): i for i, p in enumerate(p for g in self.optimizer.param_groups for p in g["params"])}
-        template = {k: v for k, v in own["param_groups"][0].items() if k != "params"} if own["param_groups"] else {}
-        # (graph mode keeps lr in a device scalar: the file carries the number, as the reference's does)
-        template = {k: (float(v) if torch.is_tensor(v) and v.dim() == 0 else v) for k, v in template.items()}
-        state, groups, idx = {}, [], 0
-        for gi, group in enumerate(self._ref_layout):
-            ids = []
-            for p in group:
-                if self.table is not None and p is self.table:
-                    state[idx] = {"step": self.t_steps[self.t_flip].detach().clone().float().cpu(),
-                                  "exp_avg": self.t_m.detach().clone(), "exp_avg_sq": self.t_v.detach().clone()}
-                elif self.table is not None and id(p) in self._small_stepped:
-                    # stepped by the fused optimizer: its moments are a slice of the flat buffers, the step count is the
-                    # table's (one counter for all parameters: a skipped step skips every one of them)
-                    k = next(i for i, q in enumerate(self.small) if q is p)
-                    sl = slice(self.small_off[k], self.small_off[k + 1])
-                    state[idx] = {"step": self.t_steps[self.t_flip].detach().clone().float().cpu(),
-                                  "exp_avg": self.small_m[sl].detach().clone().view_as(p),
-                                  "exp_avg_sq": self.small_v[sl].detach().clone().view_as(p)}
-                elif id(p) in own_ids and own_ids[id(p)] in own["state"]:
-                    state[idx] = own["state"][own_ids[id(p)]]
-                ids.append(idx)
-                idx += 1
-            g = dict(template)
-            g["params"] = ids
-            groups.append(g)
-        return {"state": state, "param_groups": groups}
-
-    def _load_optimizer_state_ref_layout(self, sd):
-        own_ids = {id(p): i for i, p in enumerate(p for g in self.optimizer.param_groups for p in g["params"])}
-        own = self.optimizer.state_dict()
-        idx, loaded_steps = 0, None
-        for group in self._ref_layout:
-            for p in group:
-                st = sd["state"].get(idx)
-                if st is not None:
-                    if self.table is not None and p is self.table:
-                        self.t_m.copy_(st["exp_avg"].to(self.t_m.device))
-                        self.t_v.copy_(st["exp_avg_sq"].to(self.t_v.device))
-                        loaded_steps = float(st["step"])
-                    elif self.table is not None and any(q is p for q in self.small):
-                        k = next(i for i, q in enumerate(self.small) if q is p)
-                        sl = slice(self.small_off[k], self.small_off[k + 1])
-                        self.small_m[sl].copy_(st["exp_avg"].to(self.small_m.device).reshape(-1))
-                        self.small_v[sl].copy_(st["exp_avg_sq"].to(self.small_v.device).reshape(-1))
-                        self._small_stepped.add(id(p))
-                        if loaded_steps is None:
-                            loaded_steps = float(st["step"])
-                    elif id(p) in own_ids:
-                        own["state"][own_ids[id(p)]] = st
-                idx += 1
-        # learning rates: the reference's groups that hold parameters stepped here, in order; when they are stepped as
-        # one merged group (see __init__) they all carry the same value and the first one is taken
-        lr_by_pos = [g.get("lr") for g in sd["param_groups"]]
-        lrs = [l for l, grp in zip(lr_by_pos, self._ref_layout) if any(id(p) in own_ids for p in grp)]
-        if len(own["param_groups"]) == 1:
-            lrs = lrs[:1]
-        for g, lr in zip(own["param_groups"], lrs):
-            if lr is not None:
-                g["lr"] = lr
-        self.optimizer.load_state_dict(own)
-        self._after_optimizer_load()
-        if self.table is not None and loaded_steps is not None:
-            self._pending_steps = loaded_steps  # (committed by load_checkpoint once the scheduler's position is loaded too)
-
-    def _drop_graphs(self):
-        """Forget every captured step: the next step runs launch by launch (taking every lazy initialisation and version
-        check with it), the one after is captured afresh."""
-        had = bool(self._graphs)
-        self._graphs.clear()
-        self._graph_warm.clear()
-        # the graphs' memory pool goes with them: a pool none of whose graphs is alive any more cannot take a new capture
-        # (the allocator asserts on it); the next capture opens a new one, and the blocks of the old one go back to the driver
-        self._graph_pool = None
-        if had and torch.cuda.is_available() and not torch.cuda.is_current_stream_capturing():
-            torch.cuda.empty_cache()
-
-    def _after_optimizer_load(self):
-        """Graph mode: every captured step is dropped after a load (the next step runs launch by launch and takes the
-        version checks and lazy initialisations with it)."""
-        if self.graph:
-            self._drop_graphs()
-
-    def _own_group_of_ref_group(self):
-        """For every parameter group of the reference's optimizer: index of the group of self.optimizer that steps its
-        parameters (the table's group, stepped by the fused kernel, and empty groups follow group 0: every group of
-        model.get_params(lr) carries the same lr and the same lambda)."""
-        own = {id(p): gi for gi, g in enumerate(self.optimizer.param_groups) for p in g["params"]}
-        return [next((own[id(p)] for p in grp if id(p) in own), 0) for grp in self._ref_layout]
-
-    def _scheduler_state_ref_layout(self):
-        """LambdaLR.state_dict() as the reference's scheduler over Adam(model.get_params(lr)) writes it: `base_lrs`,
-        `_last_lr` and `lr_lambdas` carry one entry per REFERENCE parameter group (6, or 8 with a background net), not per
-        group of the merged optimizer stepped here — a stock scheduler loading the file zips them against its groups."""
-        sd = dict(self.scheduler.state_dict())
-        m = self._own_group_of_ref_group()
-        for key in ("base_lrs", "_last_lr"):
-            if key in sd:
-                sd[key] = [float(sd[key][i]) if torch.is_tensor(sd[key][i]) else sd[key][i] for i in m]
-        if "lr_lambdas" in sd:
-            sd["lr_lambdas"] = [sd["lr_lambdas"][i] for i in m]
-        return sd
-
-    def _load_scheduler_state_ref_layout(self, sd):
-        """Inverse of the above (also accepts a state written per own group, e.g. by LidarTrainer.state_dict)."""
-        sd = dict(sd)
-        n_own, m = len(self.optimizer.param_groups), self._own_group_of_ref_group()
-        for key in ("base_lrs", "_last_lr", "lr_lambdas"):
-            vals = sd.get(key)
-            if vals is None or len(vals) == n_own:
-                continue
-            if len(vals) != len(m):
-                raise RuntimeError(f"lr_scheduler state: {len(vals)} entries in '{key}' for {len(m)} reference parameter "
-                                   f"groups / {n_own} groups stepped here")
-            first = {}
-            for ref_i, own_i in enumerate(m):
-                first.setdefault(own_i, vals[ref_i])
-            sd[key] = [first.get(i, vals[0]) for i in range(n_own)]
-        self.scheduler.load_state_dict(sd)
-
+    # ---- checkpoints in the reference Trainer's format (nerf/checkpoint.py; lidarnerf/nerf/utils.py:1449-1568)
     def save_checkpoint(self, path, full=True, gather=True, ema_model=False):
         """Same dictionary as Trainer.save_checkpoint (utils.py:1449-1480): epoch, global_step, stats, model and — `full`
         — optimizer / lr_scheduler / scaler in the layout the reference's Trainer.load_checkpoint restores (a reference
@@ -955,45 +480,7 @@ class LidarTrainer:
         A trainer with ema_decay writes the parameter average under "ema" (`full`; utils.py:1463-1464), in torch_ema's
         state-dict layout.  ema_model=True: "model" is the state dict under the AVERAGED weights (swapped in for the
         state_dict() call and back out) — what the reference's best=True checkpoint holds (utils.py:1492-1504)."""
-        if ema_model:
-            self._require_ema("save_checkpoint(ema_model=True)")
-        write = True
-        if self.sharded:
-            import torch.distributed as dist
-            if gather:
-                self.gather_table_state()
-                write = dist.get_rank() == 0
-            elif getattr(self.table, "_lnh_master_stale", False):
-                raise RuntimeError("save_checkpoint(gather=False) with the sharded table optimizer: call "
-                                   "gather_table_state() on every rank first (this rank holds only its own rows of the "
-                                   "table and the Adam moments)")
-        if not write:
-            return path
-        state = {"epoch": self.epoch, "global_step": self.global_step, "stats": self.stats}
-        if full:
-            state["optimizer"] = self._optimizer_state_ref_layout()
-            state["lr_scheduler"] = self._scheduler_state_ref_layout()
-            if self.table is not None:  # the dynamic loss scale lives with the fused table optimizer
-                state["scaler"] = {"scale": float(self.loss_scale), "growth_factor": 2.0, "backoff_factor": 0.5,
-                                   "growth_interval": 2000, "_growth_tracker": int(self.growth_tracker)}
-            else:
-                state["scaler"] = self.scaler.state_dict()
-            if self.ema is not None:
-                state["ema"] = self.ema.state_dict()
-        if getattr(self.model, "cuda_ray", False):  # a reference loader ignores the extra keys
-            state["mean_count"], state["mean_density"] = self.model.mean_count, self.model.mean_density
-            state["iter_density"], state["local_step"] = self.model.iter_density, self.model.local_step
-        if ema_model:
-            self._ema_swap()
-            try:
-                # (state_dict() returns views of the parameters: the file must hold the values they have NOW)
-                state["model"] = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
-            finally:
-                self._ema_swap()
-        else:
-            state["model"] = self.model.state_dict()
-        torch.save(state, path)
-        return path
+        return checkpoint.save_checkpoint(self, path, full=full, gather=gather, ema_model=ema_model)
 
     def load_checkpoint(self, path, model_only=False):
         """Trainer.load_checkpoint (utils.py:1511-1568): a bare state dict or the dictionary above; strict=False.
@@ -1002,46 +489,7 @@ class LidarTrainer:
         When the file has none — a bare state dict, model_only, a checkpoint written without EMA — the shadows are
         RE-SEEDED from the loaded parameters and num_updates goes back to 0: a deliberate deviation from the reference,
         which would go on averaging from its random initialisation."""
-        ck = torch.load(path, map_location=next(self.model.parameters()).device, weights_only=False)
-        # whatever the file holds, the model is about to change under the captured steps (a bare state dict and
-        # model_only=True never reach _after_optimizer_load): drop them on every path
-        self._drop_graphs()
-        if "model" not in ck:
-            self.model.load_state_dict(ck)
-            if self.table is not None:
-                self.table._lnh_master_stale = False  # a loaded table is whole
-            if self.ema is not None:
-                self.ema.reseed()
-            return [], []
-        missing, unexpected = self.model.load_state_dict(ck["model"], strict=False)
-        if getattr(self.model, "cuda_ray", False):
-            for key in ("mean_count", "mean_density", "iter_density", "local_step"):
-                if key in ck:  # without them the next 16 grid updates are full sweeps and sample buffers are N * 1024
-                    setattr(self.model, key, ck[key])
-        if self.table is not None:
-            self.table._lnh_master_stale = False  # a loaded table is whole
-        if self.ema is not None:
-            if not model_only and ck.get("ema") is not None:
-                self.ema.load_state_dict(ck["ema"])
-            else:
-                self.ema.reseed()
-        if model_only:
-            return missing, unexpected
-        self.stats, self.epoch, self.global_step = ck["stats"], ck["epoch"], ck["global_step"]
-        if "optimizer" in ck:
-            self._load_optimizer_state_ref_layout(ck["optimizer"])
-        if "lr_scheduler" in ck:
-            self._load_scheduler_state_ref_layout(ck["lr_scheduler"])
-        if self.table is not None:  # the device-side counters follow what was loaded
-            self._sync_counters(steps=getattr(self, "_pending_steps", None))
-            self._pending_steps = None
-        if "scaler" in ck and ck["scaler"]:
-            if self.table is not None:
-                self.loss_scale.fill_(float(ck["scaler"]["scale"]))
-                self.growth_tracker.fill_(int(ck["scaler"].get("_growth_tracker", 0)))
-            else:
-                self.scaler.load_state_dict(ck["scaler"])
-        return missing, unexpected
+        return checkpoint.load_checkpoint(self, path, model_only=model_only)
 
     def step(self, rays_o, rays_d, images_lidar, patch=(1, 1)):
         loss = self._step(rays_o, rays_d, images_lidar, patch)
@@ -1055,7 +503,7 @@ class LidarTrainer:
                 self.model.update_extra_state()  # refresh the occupancy grid the marcher reads (every 16 steps)
         self.global_step += 1
         if self.graph:
-            return self._step_graphed(rays_o, rays_d, images_lidar, patch)
+            return captured_step.step_graphed(self, rays_o, rays_d, images_lidar, patch)
         if self.table is not None:
             return self._step_fused_table(rays_o, rays_d, images_lidar, patch)
         self.optimizer.zero_grad(set_to_none=True)
