@@ -906,6 +906,39 @@ LNH_API int lnh_eval_points_finalize(const float *dist_pred, const float *dist_g
                                      float threshold, double *accumulator, double *history, uint32_t max_frames,
                                      lnh_stream_t stream);
 
+/* ------------------------------------------------------------------ training batches drawn on the device ----- */
+/*
+ * Replaces KITTI360Dataset.collate / NeRFMVLDataset.collate + get_lidar_rays for a sequence that is preloaded on the
+ * device (lidarnerf/dataset/base_dataset.py:16-105, kitti360_dataset.py:123-159): one launch of one thread per ray draws
+ * the batch of a training step, a second one-thread launch moves the cursor on.  No atomics, no host synchronisation,
+ * and nothing that changes from step to step is a kernel argument — a captured launch draws a fresh batch per replay.
+ * poses [F,4,4] f32 (lidar -> world, row-major); images [F,H,W,3] of image_dtype (LNH_F32 / LNH_F16); (fov_up, fov) in
+ * degrees; perm [F] int32, the frame order of the epoch (an entry is taken modulo F; may be NULL with an explicit frame);
+ * cursor [2] uint64: [0] the step within the epoch, [1] the number of draws since the sampler was made (never reset);
+ * (seed_lo, seed_hi) the 64-bit seed; stream_id >= 0 the data-parallel rank; frame = -1: perm[cursor[0] % F], else that
+ * frame.  Rows written, n (base_dataset.py:45-52, quirks included): px > 0: (min(n_rays, H*W) / (px*py)) * px*py — patches
+ * of px rows x py columns, row-major inside a patch, top-left corners uniform over [0, H-px) x [0, W-py) (the last row and
+ * column are never drawn); px <= 0: min(n_rays, H*W) independent pixels over H*W (py is ignored).
+ * Outputs: rays_o, rays_d [n,3] f32 (rays_o = the pose's translation, rays_d = R * (cos a cos b, cos a sin b, sin a) with
+ * b = -(col - W/2)/W * 2 pi, a = (fov_up - row/H * fov) * pi/180); gt [n,3] of image_dtype (the pixel's three values, bit
+ * for bit); inds [n] int32 = row * W + col.  After the draw both cursor entries are incremented (also when n == 0).
+ * Randomness: Philox-4x32-10, key (seed_lo, seed_hi), counter (patch index — ray index with px <= 0 —, cursor[1] low,
+ * cursor[1] high, stream_id); word 0 -> row (or the flat pixel), word 1 -> column; a word r maps to [0, m) as
+ * (uint64(r) * m) >> 32.  Not torch's randint stream.
+ * Refused (LNH_ERR_INVALID_ARG, the message names the argument): F <= 0, n_rays <= 0, px > 0 with py <= 0, px >= H or
+ * py >= W (the reference's randint(0, 0) raises too), a frame outside [-1, F), stream_id < 0, a NULL pointer;
+ * LNH_ERR_UNSUPPORTED: H*W > 2^24, another image_dtype.
+ */
+LNH_API int lnh_lidar_sample_batch(const float *poses, const void *images, int image_dtype, int32_t F, uint32_t H, uint32_t W,
+                                   float fov_up, float fov, const int32_t *perm, uint64_t *cursor, uint32_t seed_lo,
+                                   uint32_t seed_hi, int32_t stream_id, int32_t n_rays, int32_t px, int32_t py,
+                                   int32_t frame, float *rays_o, float *rays_d, void *gt, int32_t *inds,
+                                   lnh_stream_t stream);
+/* Every pixel of one frame, for evaluation: rays_o, rays_d [H*W,3] f32 of poses[frame] (a HOST index in [0, F)), the same
+ * arithmetic as above.  No randomness, no cursor. */
+LNH_API int lnh_lidar_frame_rays(const float *poses, int32_t F, int32_t frame, uint32_t H, uint32_t W, float fov_up,
+                                 float fov, float *rays_o, float *rays_d, lnh_stream_t stream);
+
 
 /* ------------------------------------------------------------------ bf16 MLP operands (BASELINE config 5) ---- */
 /*

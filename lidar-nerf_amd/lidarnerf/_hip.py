@@ -106,13 +106,16 @@ _SIGS = {
     "lnh_eval_points_project": [P, P, U32, U32, F32, F32, F32, I32, P, C.c_uint64, P, P, P],
     "lnh_eval_points_nn": [P, P, P, U32, P, C.c_uint64, P, P, P, P],
     "lnh_eval_points_finalize": [P, P, P, U32, F32, P, P, U32],
+    "lnh_lidar_sample_batch": [P, P, I32, I32, U32, U32, F32, F32, P, P, U32, U32, I32, I32, I32, I32, I32, P, P, P, P],
+    "lnh_lidar_frame_rays": [P, I32, I32, U32, U32, F32, F32, P, P],
 }
 # entry points added without moving lnh_version(): a library built before them still loads, and the feature is detected
 # by symbol (require_symbols)
 _OPTIONAL = {"lnh_lidar_eval_frame": "frame evaluation", "lnh_lidar_eval_ssim": "frame evaluation",
              "lnh_lidar_eval_finalize": "frame evaluation", "lnh_lidar_eval_workspace_bytes": "frame evaluation",
              "lnh_eval_points_project": "points evaluation", "lnh_eval_points_nn": "points evaluation",
-             "lnh_eval_points_finalize": "points evaluation", "lnh_eval_points_workspace_bytes": "points evaluation"}
+             "lnh_eval_points_finalize": "points evaluation", "lnh_eval_points_workspace_bytes": "points evaluation",
+             "lnh_lidar_sample_batch": "batch sampling", "lnh_lidar_frame_rays": "batch sampling"}
 for _n in ("lnh_mlp_forward", "lnh_mlp_backward", "lnh_mlp_backward_data", "lnh_mlp_wgrad", "lnh_density_mlp_forward", "lnh_density_mlp_backward",
            "lnh_lidar_dir_term", "lnh_lidar_pack_weights", "lnh_lidar_step_prologue", "lnh_lidar_color_forward", "lnh_lidar_color_backward",
            "lnh_lidar_color_composite_forward", "lnh_lidar_color_backward_image", "lnh_lidar_dir_term_freq",

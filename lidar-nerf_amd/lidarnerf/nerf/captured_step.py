@@ -44,9 +44,12 @@ def graph_capacity(trainer):
     return int(math.ceil(1024 * 2 ** (rung / per) / 1024.0)) * 1024
 
 
-def _capture(trainer, rays_o, rays_d, images_lidar, patch, cap):
+def _capture(trainer, rays_o, rays_d, images_lidar, patch, cap, sampler=None):
     """Capture one step on copies of the batch and replay it once.  Returns the entry, or None when the capture or that
-    first replay did not go through: graph mode is then off for good and graph_error says why."""
+    first replay did not go through: graph mode is then off for good and graph_error says why.
+    With a `sampler` (dataset.sampler.LidarBatchSampler) the batch tensors only give the shapes: the sampler's two launches
+    (draw, cursor advance) are captured at the head of the step and write the graph's own inputs — the capture records them
+    without running them, so the first replay below IS this step's draw."""
     model, tp = trainer.model, trainer.table
     if trainer._graph_pool is None:
         # one memory pool for all captured steps: they never run concurrently and none reads what another left
@@ -56,8 +59,11 @@ def _capture(trainer, rays_o, rays_d, images_lidar, patch, cap):
     ent = {"rays_o": torch.empty_like(rays_o), "rays_d": torch.empty_like(rays_d),
            "gt": torch.empty_like(images_lidar), "counter": torch.zeros(2, dtype=torch.int32, device=tp.device),
            "graph": torch.cuda.CUDAGraph()}
-    for k, src in (("rays_o", rays_o), ("rays_d", rays_d), ("gt", images_lidar)):
-        ent[k].copy_(src)
+    if sampler is not None:
+        ent["inds"] = torch.empty_like(sampler.inds)
+    else:
+        for k, src in (("rays_o", rays_o), ("rays_d", rays_d), ("gt", images_lidar)):
+            ent[k].copy_(src)
     if trainer.occupancy:
         model._static_march = (ent["counter"], cap - 128)  # (march_rays_train adds its 128-alignment on top)
     try:
@@ -84,6 +90,8 @@ def _capture(trainer, rays_o, rays_d, images_lidar, patch, cap):
             ent["graph"].capture_begin(trainer._graph_pool,
                                        capture_error_mode="thread_local" if trainer.dp else "global")
             try:
+                if sampler is not None:
+                    sampler.draw_into(ent["rays_o"], ent["rays_d"], ent["gt"], ent["inds"])
                 ent["loss"] = trainer._step_fused_table(ent["rays_o"], ent["rays_d"], ent["gt"], patch).detach()
                 if os.environ.get("LNH_DEBUG_CAPTURE_STALL_MS"):  # (diagnosis only: widens the window above)
                     time.sleep(float(os.environ["LNH_DEBUG_CAPTURE_STALL_MS"]) * 1e-3)
@@ -120,7 +128,10 @@ def _replayed(trainer, ent):
     return ent["loss"].clone()  # (the graphs share a pool: the next replay of another one may reuse this memory)
 
 
-def step_graphed(trainer, rays_o, rays_d, images_lidar, patch):
+def step_graphed(trainer, rays_o, rays_d, images_lidar, patch, sampler=None):
+    """One step of graph mode.  With a `sampler` the batch is the sampler's to draw (the tensors passed are its static
+    buffers, read for their shapes only): a step that runs launch by launch draws eagerly first, a captured one draws inside
+    its graph — every step draws exactly once."""
     model = trainer.model
     # (the dense step has no sample buffers to size: one graph per batch shape)
     cap = graph_capacity(trainer) if trainer.occupancy else -1
@@ -131,11 +142,17 @@ def step_graphed(trainer, rays_o, rays_d, images_lidar, patch):
         #  bound to the eager stream — alive into the capture that follows)
         trainer._graph_warm.add("eager")
         model._static_march = None
+        if sampler is not None:
+            sampler.draw()
         return trainer._step_fused_table(rays_o, rays_d, images_lidar, patch).detach()
     # what a capture bakes in as kernel arguments is part of the key: the loss weights, the scene scale, the render
     # arguments (a change of any of them captures a new step instead of silently replaying the old values)
     key = (tuple(rays_o.shape), tuple(images_lidar.shape), tuple(patch), tuple(trainer.alpha), float(trainer.scale),
            tuple(sorted((k, repr(v)) for k, v in trainer.render_kwargs.items())), trainer.loss_options, cap)
+    if sampler is not None:
+        # the draw's kernel arguments (sequence, geometry, seed, stream) join the key; the cursor lives in the sampler, so
+        # every graph of the capacity ladder reads and advances the same one
+        key += ("sampled",) + sampler.graph_key()
     tp = trainer.table
     if getattr(tp, "_lnh_table16_version", None) != tp._version:
         # somebody wrote the fp32 table through torch since the last step (model.load_state_dict, a manual
@@ -145,12 +162,15 @@ def step_graphed(trainer, rays_o, rays_d, images_lidar, patch):
         table16_of(tp)
     ent = trainer._graphs.get(key)
     if ent is None:
-        ent = _capture(trainer, rays_o, rays_d, images_lidar, patch, cap)
+        ent = _capture(trainer, rays_o, rays_d, images_lidar, patch, cap, sampler)
         if ent is None:  # (graph mode is off: this step and every later one launch by launch)
+            if sampler is not None:
+                sampler.draw()  # (nothing of the failed capture has run: this step has not drawn yet)
             return trainer._step_fused_table(rays_o, rays_d, images_lidar, patch).detach()
         trainer._graphs[key] = ent
     else:
-        torch._foreach_copy_([ent["rays_o"], ent["rays_d"], ent["gt"]], [rays_o, rays_d, images_lidar])  # one launch
+        if sampler is None:
+            torch._foreach_copy_([ent["rays_o"], ent["rays_d"], ent["gt"]], [rays_o, rays_d, images_lidar])  # one launch
         ent["graph"].replay()
     return _replayed(trainer, ent)
 

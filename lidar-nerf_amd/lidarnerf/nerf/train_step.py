@@ -497,13 +497,47 @@ class LidarTrainer:
             self.ema_update()  # (after the replay, outside any captured graph, on the same stream)
         return loss
 
-    def _step(self, rays_o, rays_d, images_lidar, patch):
+    def step_sampled(self, sampler):
+        """step() on a batch the step draws itself from `sampler` (dataset.sampler.LidarBatchSampler: frame of the epoch,
+        random patches, rays and targets in one launch): occupancy update, global_step and the EMA cadence as in step().
+        Launch by launch: sampler.draw(), then the step.  graph=True: the sampler's two launches are captured at the head of
+        the step's graph and write the graph's own inputs — a replay needs no batch from the host and no copy into the
+        graph.  The patch shape of the loss is the sampler's."""
+        loss = self._step(None, None, None, sampler.patch, sampler=sampler)
+        if self.ema_interval and self.global_step % self.ema_interval == 0:
+            self.ema_update()
+        return loss
+
+    def train_epoch(self, sampler, steps=None):
+        """The reference's train_one_epoch (utils.py:1206-1260) on a LidarBatchSampler: sampler.new_epoch() (a fresh frame
+        order), then one step_sampled per frame — or `steps` of them.  The losses are summed on the device and read ONCE
+        (the reference reads loss.item() every step); returns their mean, appends it to stats["loss"], bumps `epoch`.  The
+        reference's per-epoch EMA update is the caller's (ema_update(), or ema_interval=)."""
+        sampler.new_epoch()
+        n = len(sampler) if steps is None else int(steps)
+        if n <= 0:
+            raise ValueError(f"LidarTrainer.train_epoch(steps={steps!r}): a positive number of steps")
+        total = None
+        for _ in range(n):
+            loss = self.step_sampled(sampler).detach().float()
+            total = loss if total is None else total + loss
+        mean = float(total) / n  # (the one host read of the epoch)
+        self.epoch += 1
+        self.stats["loss"].append(mean)
+        return mean
+
+    def _step(self, rays_o, rays_d, images_lidar, patch, sampler=None):
         if self.occupancy and self.global_step % self.update_extra_interval == 0:
             with torch.autocast("cuda", dtype=self.amp_dtype, enabled=self.fp16):
                 self.model.update_extra_state()  # refresh the occupancy grid the marcher reads (every 16 steps)
         self.global_step += 1
         if self.graph:
+            if sampler is not None:
+                return captured_step.step_graphed(self, sampler.rays_o[None], sampler.rays_d[None], sampler.gt[None], patch,
+                                                  sampler=sampler)
             return captured_step.step_graphed(self, rays_o, rays_d, images_lidar, patch)
+        if sampler is not None:
+            rays_o, rays_d, images_lidar = sampler.draw()
         if self.table is not None:
             return self._step_fused_table(rays_o, rays_d, images_lidar, patch)
         self.optimizer.zero_grad(set_to_none=True)
