@@ -290,6 +290,19 @@ LNH_API int lnh_march_rays_train(const float *rays_o, const float *rays_d, const
                                  float dt_gamma, uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M,
                                  const float *nears, const float *fars, float *xyzs, float *dirs, float *deltas,
                                  int32_t *rays, int32_t *counter, const float *noises, lnh_stream_t stream);
+/* Adds (no reference counterpart: the reference's marcher hands out rows with one pair of atomics per ray, in arrival order)
+ * the RAY-ORDERED form of lnh_march_rays_train — same arguments, same refusals, no allocation, no synchronisation, N == 0
+ * returns LNH_OK.  rays[n] = (n, sum of count_m over m < n, count_n) for every n; counter [2] int32 zeroed by the caller:
+ * [0] += points, [1] += rays (the values lnh_march_rays_train leaves).  A ray with offset + count > M keeps its table entry
+ * and writes no sample (its rows stay as the caller cleared them): with ordered offsets that set depends on the inputs
+ * alone.  Per ray the samples are bit for bit lnh_march_rays_train's; the whole output equals the serial oracle's
+ * (oracle/lnh_oracle.c).  Three launches on `stream` (count per ray, one-workgroup integer scan, write per ray); no
+ * workgroup waits for another one, no float atomics. */
+LNH_API int lnh_march_rays_train_ordered(const float *rays_o, const float *rays_d, const uint8_t *grid, float bound,
+                                         float dt_gamma, uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H,
+                                         uint32_t M, const float *nears, const float *fars, float *xyzs, float *dirs,
+                                         float *deltas, int32_t *rays, int32_t *counter, const float *noises,
+                                         lnh_stream_t stream);
 /* Replaces composite_rays_train_forward / _backward  raymarching.h:45-69 (raymarching.cu:577-802). */
 LNH_API int lnh_composite_rays_train_forward(const float *sigmas, const float *rgbs, const float *deltas,
                                              const int32_t *rays, uint32_t M, uint32_t N, float T_thresh,

@@ -178,34 +178,38 @@ struct WalkState {
     float last_t;                  // t after the last emitted sample (deltas[:, 1] = t_after - last_t)
 };
 
-constexpr uint32_t kMarchRaysPerGroup = 16;
-__global__ void __launch_bounds__(64 * kMarchRaysPerGroup)
-k_march_rays_train(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
-                   const uint8_t *__restrict__ grid, float bound, float dt_gamma, uint32_t max_steps, uint32_t N,
-                   uint32_t C, uint32_t H, uint32_t M, const float *__restrict__ nears,
-                   const float *__restrict__ fars, float *__restrict__ xyzs, float *__restrict__ dirs,
-                   float *__restrict__ deltas, int32_t *__restrict__ rays, int32_t *__restrict__ counter,
-                   const float *__restrict__ noises) {
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint32_t n = blockIdx.x * kMarchRaysPerGroup + wv;
-    const bool active = n < N;  // (wave-uniform; an idle wave of the last workgroup still meets the barriers)
-    const uint32_t nc = active ? n : 0;
-    __shared__ uint32_t s_count[kMarchRaysPerGroup], s_offset[kMarchRaysPerGroup], s_ray0;
+// The walk of one ray by one wave: the ray, the lattice's parameters and the chunk of 64 lattice points described above.  k_march_rays_train (arrival-order
+// rows) and the three-launch ordered marcher (k_march_count / k_march_scan / k_march_write) both walk through THIS struct —
+// one copy of the lattice, the probes and the max_steps cap, so a ray's count and samples are the same bits in either.
+struct RayWalk {
     MarchRay r;
-    r.ox = rays_o[nc * 3]; r.oy = rays_o[nc * 3 + 1]; r.oz = rays_o[nc * 3 + 2];
-    r.dx = rays_d[nc * 3]; r.dy = rays_d[nc * 3 + 1]; r.dz = rays_d[nc * 3 + 2];
-    r.rdx = 1 / r.dx; r.rdy = 1 / r.dy; r.rdz = 1 / r.dz;
-    const float rH = 1 / (float)H, H3 = (float)(H * H * H);
-    const float far = fars[nc];
-    const float SQRT3 = 1.7320508075688772f;
-    const float dt_min = 2 * SQRT3 / max_steps;
-    const float dt_max = 2 * SQRT3 * (float)(1 << (C - 1)) / H;
-    float t0 = nears[nc];
-    t0 += march_dt(t0, dt_gamma, dt_min, dt_max) * noises[nc];
-    const unsigned long long below = (1ull << lane) - 1;
+    const uint8_t *__restrict__ grid;
+    float bound, dt_gamma, dt_min, dt_max, rH, H3, far, t0;
+    uint32_t max_steps, C, H, lane;
+    unsigned long long below;
+
+    __device__ __forceinline__ RayWalk(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
+                                       const uint8_t *__restrict__ grid_, float bound_, float dt_gamma_,
+                                       uint32_t max_steps_, uint32_t C_, uint32_t H_, const float *__restrict__ nears,
+                                       const float *__restrict__ fars, const float *__restrict__ noises, uint32_t nc,
+                                       uint32_t lane_)
+        : grid(grid_), bound(bound_), dt_gamma(dt_gamma_), max_steps(max_steps_), C(C_), H(H_), lane(lane_) {
+        r.ox = rays_o[nc * 3]; r.oy = rays_o[nc * 3 + 1]; r.oz = rays_o[nc * 3 + 2];
+        r.dx = rays_d[nc * 3]; r.dy = rays_d[nc * 3 + 1]; r.dz = rays_d[nc * 3 + 2];
+        r.rdx = 1 / r.dx; r.rdy = 1 / r.dy; r.rdz = 1 / r.dz;
+        rH = 1 / (float)H;
+        H3 = (float)(H * H * H);
+        far = fars[nc];
+        const float SQRT3 = 1.7320508075688772f;
+        dt_min = 2 * SQRT3 / max_steps;
+        dt_max = 2 * SQRT3 * (float)(1 << (C - 1)) / H;
+        t0 = nears[nc];
+        t0 += march_dt(t0, dt_gamma, dt_min, dt_max) * noises[nc];
+        below = (1ull << lane) - 1;
+    }
 
     // One chunk of the walk.  Returns the mask of the lanes whose lattice point becomes a sample; p_out = their probes.
-    auto chunk = [&](WalkState &w, Probe &p_out, float &t_lane) -> unsigned long long {
+    __device__ __forceinline__ unsigned long long chunk(WalkState &w, Probe &p_out, float &t_lane) const {
         float t = w.t_base;
 #pragma unroll 8
         for (uint32_t i = 0; i < 63; i++)
@@ -254,17 +258,64 @@ k_march_rays_train(const float *__restrict__ rays_o, const float *__restrict__ r
         }
         if (valid != ~0ull) w.done = true;  // t >= far inside this chunk (also when an empty cell's exit lies beyond it)
         return emit;
-    };
-
-    // pass 1: count
-    WalkState w{t0, 0.0f, false, !active, 0u, t0};
-    while (!w.done) {
-        Probe p;
-        float t;
-        const unsigned long long emit = chunk(w, p, t);
-        w.emitted += (uint32_t)__builtin_popcountll(emit);
     }
-    const uint32_t num_steps = w.emitted;
+
+    // pass 1: the number of samples of the ray (0 for an idle wave)
+    __device__ __forceinline__ uint32_t count(bool active) const {
+        WalkState w{t0, 0.0f, false, !active, 0u, t0};
+        while (!w.done) {
+            Probe p;
+            float t;
+            const unsigned long long emit = chunk(w, p, t);
+            w.emitted += (uint32_t)__builtin_popcountll(emit);
+        }
+        return w.emitted;
+    }
+
+    // pass 2: the same walk, writing the ray's samples into the rows from point_index on
+    __device__ __forceinline__ void write(uint32_t point_index, float *__restrict__ xyzs, float *__restrict__ dirs,
+                                          float *__restrict__ deltas) const {
+        WalkState w{t0, 0.0f, false, false, 0u, t0};
+        while (!w.done) {
+            Probe p;
+            float t;
+            const unsigned long long emit = chunk(w, p, t);
+            if (!emit) continue;
+            const float t_after = t + p.dt;  // (= the next lattice point: the serial walk's `t += dt`)
+            const unsigned long long before = emit & below;
+            // t after the previous sample: the emitted lane below this one, or the carry from the chunks before
+            const int prev = before ? 63 - (int)__builtin_clzll(before) : 0;
+            const float prev_after = __shfl(t_after, prev, 64);
+            if ((emit >> lane) & 1) {
+                const size_t row = (size_t)point_index + w.emitted + (uint32_t)__builtin_popcountll(before);
+                xyzs[row * 3] = p.x; xyzs[row * 3 + 1] = p.y; xyzs[row * 3 + 2] = p.z;
+                dirs[row * 3] = r.dx; dirs[row * 3 + 1] = r.dy; dirs[row * 3 + 2] = r.dz;
+                deltas[row * 2] = p.dt;
+                deltas[row * 2 + 1] = t_after - (before ? prev_after : w.last_t);
+            }
+            const int top = 63 - (int)__builtin_clzll(emit);
+            w.last_t = __shfl(t_after, top, 64);
+            w.emitted += (uint32_t)__builtin_popcountll(emit);
+        }
+    }
+};
+
+constexpr uint32_t kMarchRaysPerGroup = 16;
+__global__ void __launch_bounds__(64 * kMarchRaysPerGroup)
+k_march_rays_train(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
+                   const uint8_t *__restrict__ grid, float bound, float dt_gamma, uint32_t max_steps, uint32_t N,
+                   uint32_t C, uint32_t H, uint32_t M, const float *__restrict__ nears,
+                   const float *__restrict__ fars, float *__restrict__ xyzs, float *__restrict__ dirs,
+                   float *__restrict__ deltas, int32_t *__restrict__ rays, int32_t *__restrict__ counter,
+                   const float *__restrict__ noises) {
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const uint32_t n = blockIdx.x * kMarchRaysPerGroup + wv;
+    const bool active = n < N;  // (wave-uniform; an idle wave of the last workgroup still meets the barriers)
+    const uint32_t nc = active ? n : 0;
+    __shared__ uint32_t s_count[kMarchRaysPerGroup], s_offset[kMarchRaysPerGroup], s_ray0;
+    const RayWalk walk(rays_o, rays_d, grid, bound, dt_gamma, max_steps, C, H, nears, fars, noises, nc, lane);
+
+    const uint32_t num_steps = walk.count(active);
     // sample offsets and ray-table slots: ONE pair of atomics per workgroup for its 16 rays (the reference takes a pair per
     // ray, raymarching.cu:441-447; 4096 same-address returning atomics cost ~100 us by themselves — any disjoint
     // allocation is a valid arrival order)
@@ -291,30 +342,86 @@ k_march_rays_train(const float *__restrict__ rays_o, const float *__restrict__ r
     }
     if (num_steps == 0) return;
     if (point_index + num_steps > M) return;
+    walk.write(point_index, xyzs, dirs, deltas);
+}
 
-    // pass 2: the same walk, writing
-    w = WalkState{t0, 0.0f, false, false, 0u, t0};
-    while (!w.done) {
-        Probe p;
-        float t;
-        const unsigned long long emit = chunk(w, p, t);
-        if (!emit) continue;
-        const float t_after = t + p.dt;  // (= the next lattice point: the serial walk's `t += dt`)
-        const unsigned long long before = emit & below;
-        // t after the previous sample: the emitted lane below this one, or the carry from the chunks before
-        const int prev = before ? 63 - (int)__builtin_clzll(before) : 0;
-        const float prev_after = __shfl(t_after, prev, 64);
-        if ((emit >> lane) & 1) {
-            const size_t row = (size_t)point_index + w.emitted + (uint32_t)__builtin_popcountll(before);
-            xyzs[row * 3] = p.x; xyzs[row * 3 + 1] = p.y; xyzs[row * 3 + 2] = p.z;
-            dirs[row * 3] = r.dx; dirs[row * 3 + 1] = r.dy; dirs[row * 3 + 2] = r.dz;
-            deltas[row * 2] = p.dt;
-            deltas[row * 2 + 1] = t_after - (before ? prev_after : w.last_t);
-        }
-        const int top = 63 - (int)__builtin_clzll(emit);
-        w.last_t = __shfl(t_after, top, 64);
-        w.emitted += (uint32_t)__builtin_popcountll(emit);
+// ------------------------------------------------------------------------------------------------ ordered marcher
+// The same rays, rows handed out in RAY order: rays[n] = (n, sum of the counts of the rays before n, count_n).  Three launches
+// on one stream; the launch boundaries are the only ordering there is — no workgroup ever waits for another one (no look-back,
+// no flag, no ticket), and the only sums are integer ones.  The layout is the serial oracle's, and with it the set of rays a
+// full sample buffer drops is a function of the inputs alone.
+//   k_march_count  one wave per ray, pass 1 of the walk: rays[n] = (n, -, count_n)
+//   k_march_scan   ONE workgroup, exclusive scan of the counts in tiles of kScanTile rays: rays[n][1], counter += (sum, N)
+//   k_march_write  one wave per ray, pass 2 of the walk at the scanned offset
+__global__ void __launch_bounds__(64 * kMarchRaysPerGroup)
+k_march_count(const float *__restrict__ rays_o, const float *__restrict__ rays_d, const uint8_t *__restrict__ grid,
+              float bound, float dt_gamma, uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H,
+              const float *__restrict__ nears, const float *__restrict__ fars, int32_t *__restrict__ rays,
+              const float *__restrict__ noises) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t n = blockIdx.x * kMarchRaysPerGroup + (threadIdx.x >> 6);
+    if (n >= N) return;  // (wave-uniform; no barrier in this kernel)
+    const RayWalk walk(rays_o, rays_d, grid, bound, dt_gamma, max_steps, C, H, nears, fars, noises, n, lane);
+    const uint32_t num_steps = walk.count(true);
+    if (lane == 0) {
+        rays[n * 3] = (int32_t)n;
+        rays[n * 3 + 2] = (int32_t)num_steps;
     }
+}
+
+constexpr uint32_t kScanThreads = 1024, kScanPerThread = 4, kScanTile = kScanThreads * kScanPerThread;
+__global__ void __launch_bounds__(kScanThreads)
+k_march_scan(int32_t *__restrict__ rays, int32_t *__restrict__ counter, uint32_t N) {
+    constexpr uint32_t kWaves = kScanThreads / 64;
+    __shared__ uint32_t s_wave[kWaves];
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const uint32_t base0 = (uint32_t)counter[0];  // (zeroed by the caller, like the arrival-order marcher's)
+    uint32_t carry = 0;                           // counts of the tiles in front of this one: the same in every thread
+    for (uint32_t tile = 0; tile < N; tile += kScanTile) {
+        const uint32_t first = tile + threadIdx.x * kScanPerThread;  // kScanPerThread consecutive rays per thread
+        uint32_t c[kScanPerThread], mine = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < kScanPerThread; k++) {
+            c[k] = first + k < N ? (uint32_t)rays[(size_t)(first + k) * 3 + 2] : 0u;
+            mine += c[k];
+        }
+        const uint32_t incl = wave_scan_add_u32(mine);
+        if (lane == 63) s_wave[wv] = incl;
+        __syncthreads();
+        // every wave scans the kWaves wave totals itself: its own exclusive prefix and the tile's total
+        const uint32_t wt = lane < kWaves ? s_wave[lane] : 0u;
+        const uint32_t wincl = wave_scan_add_u32(wt);
+        const uint32_t wave_off = (uint32_t)__shfl((int)(wincl - wt), (int)wv, 64);
+        const uint32_t tile_total = (uint32_t)__shfl((int)wincl, (int)kWaves - 1, 64);
+        uint32_t off = base0 + carry + wave_off + (incl - mine);
+#pragma unroll
+        for (uint32_t k = 0; k < kScanPerThread; k++) {
+            if (first + k < N) rays[(size_t)(first + k) * 3 + 1] = (int32_t)off;
+            off += c[k];
+        }
+        carry += tile_total;
+        __syncthreads();  // s_wave is rewritten by the next tile
+    }
+    if (threadIdx.x == 0) {
+        counter[0] = (int32_t)(base0 + carry);
+        counter[1] += (int32_t)N;
+    }
+}
+
+__global__ void __launch_bounds__(64 * kMarchRaysPerGroup)
+k_march_write(const float *__restrict__ rays_o, const float *__restrict__ rays_d, const uint8_t *__restrict__ grid,
+              float bound, float dt_gamma, uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M,
+              const float *__restrict__ nears, const float *__restrict__ fars, float *__restrict__ xyzs,
+              float *__restrict__ dirs, float *__restrict__ deltas, const int32_t *__restrict__ rays,
+              const float *__restrict__ noises) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t n = blockIdx.x * kMarchRaysPerGroup + (threadIdx.x >> 6);
+    if (n >= N) return;  // (wave-uniform)
+    const uint32_t point_index = (uint32_t)rays[n * 3 + 1], num_steps = (uint32_t)rays[n * 3 + 2];
+    if (num_steps == 0) return;
+    if (point_index + num_steps > M) return;  // the arrival-order marcher's rule: the table entry stays, no row is written
+    const RayWalk walk(rays_o, rays_d, grid, bound, dt_gamma, max_steps, C, H, nears, fars, noises, n, lane);
+    walk.write(point_index, xyzs, dirs, deltas);
 }
 
 // raymarching.cu:577-655
@@ -700,6 +807,29 @@ int lnh_march_rays_train(const float *rays_o, const float *rays_d, const uint8_t
                (hipStream_t)stream, rays_o, rays_d, grid,
                        bound, dt_gamma, max_steps, N, C, H, M, nears, fars, xyzs, dirs, deltas, rays, counter, noises);
     return lnh_check_launch("lnh_march_rays_train");
+}
+
+int lnh_march_rays_train_ordered(const float *rays_o, const float *rays_d, const uint8_t *grid, float bound,
+                                 float dt_gamma, uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M,
+                                 const float *nears, const float *fars, float *xyzs, float *dirs, float *deltas,
+                                 int32_t *rays, int32_t *counter, const float *noises, lnh_stream_t stream) {
+    LNH_REQUIRE(rays_o && rays_d && grid && nears && fars && xyzs && dirs && deltas && rays && counter && noises,
+                LNH_ERR_INVALID_ARG, "march_rays_train_ordered: null pointer");
+    LNH_REQUIRE(C >= 1 && C <= 8 && H >= 1 && H <= 1024 && max_steps >= 1, LNH_ERR_INVALID_ARG,
+                "march_rays_train_ordered: bad cascade / grid size / max_steps");
+    if (N == 0) return LNH_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid_rays(div_up(N, kMarchRaysPerGroup)), block_rays(64 * kMarchRaysPerGroup);
+    LNH_LAUNCH(k_march_count, grid_rays, block_rays, 0, s, rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, nears,
+               fars, rays, noises);
+    int rc = lnh_check_launch("lnh_march_rays_train_ordered (count)");
+    if (rc != LNH_OK) return rc;
+    LNH_LAUNCH(k_march_scan, dim3(1), dim3(kScanThreads), 0, s, rays, counter, N);
+    rc = lnh_check_launch("lnh_march_rays_train_ordered (scan)");
+    if (rc != LNH_OK) return rc;
+    LNH_LAUNCH(k_march_write, grid_rays, block_rays, 0, s, rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M,
+               nears, fars, xyzs, dirs, deltas, rays, noises);
+    return lnh_check_launch("lnh_march_rays_train_ordered (write)");
 }
 
 int lnh_composite_rays_train_forward(const float *sigmas, const float *rgbs, const float *deltas, const int32_t *rays,

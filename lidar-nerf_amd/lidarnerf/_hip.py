@@ -42,6 +42,7 @@ _SIGS = {
     "lnh_packbits": [P, U32, F32, P],
     "lnh_occupancy_lookup": [P, P, P, F32, U32, U32, U32, P, P],
     "lnh_march_rays_train": [P, P, P, F32, F32, U32, U32, U32, U32, U32, P, P, P, P, P, P, P, P],
+    "lnh_march_rays_train_ordered": [P, P, P, F32, F32, U32, U32, U32, U32, U32, P, P, P, P, P, P, P, P],
     "lnh_composite_rays_train_forward": [P, P, P, P, U32, U32, F32, P, P, P],
     "lnh_composite_rays_train_backward": [P, P, P, P, P, P, P, P, U32, U32, F32, P, P],
     "lnh_lidar_composite_rays_train_forward": [P, P, P, P, P, P, P, U32, U32, U32, F32, P, P, P],
@@ -115,7 +116,8 @@ _OPTIONAL = {"lnh_lidar_eval_frame": "frame evaluation", "lnh_lidar_eval_ssim": 
              "lnh_lidar_eval_finalize": "frame evaluation", "lnh_lidar_eval_workspace_bytes": "frame evaluation",
              "lnh_eval_points_project": "points evaluation", "lnh_eval_points_nn": "points evaluation",
              "lnh_eval_points_finalize": "points evaluation", "lnh_eval_points_workspace_bytes": "points evaluation",
-             "lnh_lidar_sample_batch": "batch sampling", "lnh_lidar_frame_rays": "batch sampling"}
+             "lnh_lidar_sample_batch": "batch sampling", "lnh_lidar_frame_rays": "batch sampling",
+             "lnh_march_rays_train_ordered": "ordered marching"}
 for _n in ("lnh_mlp_forward", "lnh_mlp_backward", "lnh_mlp_backward_data", "lnh_mlp_wgrad", "lnh_density_mlp_forward", "lnh_density_mlp_backward",
            "lnh_lidar_dir_term", "lnh_lidar_pack_weights", "lnh_lidar_step_prologue", "lnh_lidar_color_forward", "lnh_lidar_color_backward",
            "lnh_lidar_color_composite_forward", "lnh_lidar_color_backward_image", "lnh_lidar_dir_term_freq",

@@ -15,6 +15,7 @@ processes share the 16-CPU quota of a box).  gloo cannot be captured (its collec
 
 Every function takes the trainer; the state (_graphs, _graph_warm, _graph_pool, graph, graph_error, _capture_stream,
 capture_ms) stays on it."""
+import gc
 import math
 import os
 import time
@@ -85,18 +86,28 @@ def _capture(trainer, rays_o, rays_d, images_lidar, patch, cap, sampler=None):
         t_cap = time.perf_counter()
         if trainer._capture_stream is None:
             trainer._capture_stream = torch.cuda.Stream()
-        with torch.cuda.stream(trainer._capture_stream):
-            # (a capture that polices every thread of the process would trip over the watchdog's other HIP calls)
-            ent["graph"].capture_begin(trainer._graph_pool,
-                                       capture_error_mode="thread_local" if trainer.dp else "global")
-            try:
-                if sampler is not None:
-                    sampler.draw_into(ent["rays_o"], ent["rays_d"], ent["gt"], ent["inds"])
-                ent["loss"] = trainer._step_fused_table(ent["rays_o"], ent["rays_d"], ent["gt"], patch).detach()
-                if os.environ.get("LNH_DEBUG_CAPTURE_STALL_MS"):  # (diagnosis only: widens the window above)
-                    time.sleep(float(os.environ["LNH_DEBUG_CAPTURE_STALL_MS"]) * 1e-3)
-            finally:
-                ent["graph"].capture_end()
+        # no cyclic garbage collection while the stream captures: what a collection frees is arbitrary (an older trainer's
+        # captured graphs, say, kept alive by a traceback), and destroying a graph is a HIP call the capture forbids — the
+        # process aborted with the collector running inside this window.  (torch.cuda.graph's context manager collects
+        # before it captures; this capture skips that manager for the reason above.)
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.stream(trainer._capture_stream):
+                # (a capture that polices every thread of the process would trip over the watchdog's other HIP calls)
+                ent["graph"].capture_begin(trainer._graph_pool,
+                                           capture_error_mode="thread_local" if trainer.dp else "global")
+                try:
+                    if sampler is not None:
+                        sampler.draw_into(ent["rays_o"], ent["rays_d"], ent["gt"], ent["inds"])
+                    ent["loss"] = trainer._step_fused_table(ent["rays_o"], ent["rays_d"], ent["gt"], patch).detach()
+                    if os.environ.get("LNH_DEBUG_CAPTURE_STALL_MS"):  # (diagnosis only: widens the window above)
+                        time.sleep(float(os.environ["LNH_DEBUG_CAPTURE_STALL_MS"]) * 1e-3)
+                finally:
+                    ent["graph"].capture_end()
+        finally:
+            if gc_was_on:
+                gc.enable()
         # the gradient and the scale it carries live in THIS graph's buffers: table_grad() must see the ones of
         # the graph that was replayed last, not of the one that was captured last
         ent["g16"] = tp._lnh_grad16
@@ -147,8 +158,11 @@ def step_graphed(trainer, rays_o, rays_d, images_lidar, patch, sampler=None):
         return trainer._step_fused_table(rays_o, rays_d, images_lidar, patch).detach()
     # what a capture bakes in as kernel arguments is part of the key: the loss weights, the scene scale, the render
     # arguments (a change of any of them captures a new step instead of silently replaying the old values)
+    # ... and the marcher (NeRFRenderer.ordered_march is an attribute, assignable between steps: a replay never marches the
+    # other way).  The capacity stays the last element of an unsampled step's key.
+    marcher = ("ordered_march", bool(getattr(model, "ordered_march", False))) if trainer.occupancy else ()
     key = (tuple(rays_o.shape), tuple(images_lidar.shape), tuple(patch), tuple(trainer.alpha), float(trainer.scale),
-           tuple(sorted((k, repr(v)) for k, v in trainer.render_kwargs.items())), trainer.loss_options, cap)
+           tuple(sorted((k, repr(v)) for k, v in trainer.render_kwargs.items())), trainer.loss_options) + marcher + (cap,)
     if sampler is not None:
         # the draw's kernel arguments (sequence, geometry, seed, stream) join the key; the cursor lives in the sampler, so
         # every graph of the capacity ladder reads and advances the same one

@@ -72,7 +72,7 @@ lidar_composite = _LidarComposite.apply
 
 class NeRFRenderer(nn.Module):
     def __init__(self, bound=1, density_scale=1, min_near=0.2, min_near_lidar=0.2, density_thresh=0.01, bg_radius=-1,
-                 cuda_ray=False):
+                 cuda_ray=False, ordered_march=False):
         super().__init__()
         self.bound = bound
         self.cascade = 1 + math.ceil(math.log2(bound))
@@ -91,6 +91,9 @@ class NeRFRenderer(nn.Module):
         self.cuda_ray = cuda_ray
         self.alive_march = False  # evaluation through run_cuda_alive (see run_cuda); opt-in
         self.alive_stats = None
+        # run_cuda marches with lnh_march_rays_train_ordered (sample rows in ray order: what makes two occupancy-grid runs of
+        # a seed bit-identical) and update_extra_state resolves duplicated cells by their maximum; opt-in (see run_cuda)
+        self.ordered_march = bool(ordered_march)
         if cuda_ray:
             self.register_buffer("density_grid", torch.zeros(self.cascade, self.grid_size ** 3))
             self.register_buffer("density_bitfield", torch.zeros(self.cascade * self.grid_size ** 3 // 8, dtype=torch.uint8))
@@ -196,14 +199,16 @@ class NeRFRenderer(nn.Module):
         self.mean_density, self.iter_density, self.mean_count, self.local_step = 0.0, 0, 0, 0
 
     @torch.no_grad()
-    def update_extra_state(self, decay=0.95, S=128):
+    def update_extra_state(self, decay=0.95, S=128, ordered_march=None):
         """Refresh the occupancy grid from the current density field (call every ~16 training steps): sample one
         jittered point per grid cell (every cell for the first 16 updates, then a random quarter of the cells plus a
         quarter's worth of currently occupied ones), grid = max(grid * decay, density), threshold at
         min(mean density, density_thresh) and pack to the bitfield the marcher reads.  Cell <-> flat index is the Morton
-        code of raymarching.cu:71-95 (lnh_morton3D / lnh_morton3D_invert, bit-exact)."""
+        code of raymarching.cu:71-95 (lnh_morton3D / lnh_morton3D_invert, bit-exact).
+        `ordered_march` (None: the module attribute): a cell drawn more than once takes the maximum of its densities."""
         if not self.cuda_ray:
             return
+        ordered = bool(self.ordered_march if ordered_march is None else ordered_march)
         dev, G = self.density_grid.device, self.grid_size
         tmp = -torch.ones_like(self.density_grid)
 
@@ -213,7 +218,13 @@ class NeRFRenderer(nn.Module):
             xyzs = (2 * coords.float() / (G - 1) - 1) * (bound - half)
             xyzs = xyzs + (torch.rand_like(xyzs) * 2 - 1) * half
             sig = self.density(xyzs)["sigma"].reshape(-1).detach().float() * self.density_scale
-            tmp[cas, indices] = sig
+            if ordered:
+                # the partial updates draw cells with repetition, and an indexed assignment with duplicate indices has no
+                # defined winner on the GPU: the maximum of a cell's candidates is one of the values it could have taken,
+                # whatever the order (tmp starts at -1, densities are >= 0)
+                tmp[cas].scatter_reduce_(0, indices, sig, "amax", include_self=True)
+            else:
+                tmp[cas, indices] = sig
 
         if self.iter_density < 16:  # full sweep, S^3 cells at a time
             ar = torch.arange(G, dtype=torch.int32, device=dev)
@@ -249,7 +260,7 @@ class NeRFRenderer(nn.Module):
         self.local_step = 0
 
     def run_cuda(self, rays_o, rays_d, cal_lidar_color=True, dt_gamma=0, perturb=False, force_all_rays=False,
-                 max_steps=1024, T_thresh=1e-4, alive_march=None, **kwargs):
+                 max_steps=1024, T_thresh=1e-4, alive_march=None, ordered_march=None, **kwargs):
         """Occupancy-grid render of LiDAR rays: march through the occupied cells between 1 m and 81 m (scene units,
         renderer.py:129-138) with lnh_march_rays_train, evaluate density + LiDAR colour on the ragged samples, composite
         with the K = 2 / absolute-depth kernel.  Training mode keeps autograd; evaluation marches the same way (all rays)
@@ -257,7 +268,13 @@ class NeRFRenderer(nn.Module):
 
         `alive_march=True` (or the module attribute `self.alive_march`; the keyword wins) sends an EVALUATION call through
         run_cuda_alive instead — the alive-ray loop that stops shading behind the first opaque surface.  Off by default;
-        training mode ignores it."""
+        training mode ignores it.
+
+        `ordered_march=True` (or the module attribute `self.ordered_march`; the keyword wins) marches with
+        lnh_march_rays_train_ordered, in training and in evaluation: the ray table and the sample rows in ray order instead
+        of workgroup-arrival order.  Per ray the same samples; the fixed-order sums the backward forms ALONG the rows (weight
+        gradients) then no longer change from run to run, nor does the set of rays a full sample buffer drops.  Off by
+        default; run_cuda_alive has no such order to fix."""
         if not cal_lidar_color:
             raise NotImplementedError("occupancy-grid rendering is built for the LiDAR outputs (cal_lidar_color=True)")
         if not self.training and (self.alive_march if alive_march is None else alive_march):
@@ -310,7 +327,8 @@ class NeRFRenderer(nn.Module):
                   _hip.C.cast(zb, _hip.C.c_void_p), len(regions))
         xyzs, dirs, deltas, rays = raymarching.march_rays_train(
             rays_o, rays_d, self.bound, self.density_bitfield, self.cascade, self.grid_size, nears, fars, counter,
-            mean_count, perturb, 128, force_all_rays, dt_gamma, max_steps, sample_buffer=buf)
+            mean_count, perturb, 128, force_all_rays, dt_gamma, max_steps, sample_buffer=buf,
+            ordered=bool(self.ordered_march if ordered_march is None else ordered_march))
         # the cleared colour rows of the samples that were kept (evaluation trims the buffers to the marched count)
         self._lnh_rgb_rows = buf[M * 8:M * 8 + 2 * xyzs.shape[0]].view(-1, 2) if cols == 10 else None
         if xyzs.shape[0] == 0 and not (use_fused and torch.is_grad_enabled()):

@@ -529,7 +529,8 @@ class LidarTrainer:
     def _step(self, rays_o, rays_d, images_lidar, patch, sampler=None):
         if self.occupancy and self.global_step % self.update_extra_interval == 0:
             with torch.autocast("cuda", dtype=self.amp_dtype, enabled=self.fp16):
-                self.model.update_extra_state()  # refresh the occupancy grid the marcher reads (every 16 steps)
+                # refresh the occupancy grid the marcher reads (every 16 steps)
+                self.model.update_extra_state(ordered_march=self.render_kwargs.get("ordered_march"))
         self.global_step += 1
         if self.graph:
             if sampler is not None:

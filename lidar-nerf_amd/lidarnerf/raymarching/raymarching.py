@@ -71,11 +71,15 @@ def march_capacity(N, max_steps=1024, mean_count=-1, align=-1, force_all_rays=Fa
 
 
 def march_rays_train(rays_o, rays_d, bound, density_bitfield, C, H, nears, fars, step_counter=None, mean_count=-1,
-                     perturb=False, align=-1, force_all_rays=False, dt_gamma=0, max_steps=1024, sample_buffer=None):
+                     perturb=False, align=-1, force_all_rays=False, dt_gamma=0, max_steps=1024, sample_buffer=None,
+                     ordered=False):
     """Returns xyzs [M,3], dirs [M,3], deltas [M,2], rays [N,3] (id, offset, count).  Same argument list and the same
     output-trimming rules as the reference wrapper (raymarching.py:171-282).  `sample_buffer` (this build's renderer): a
     float32 buffer of >= 8 * march_capacity(...) elements that the caller has ALREADY cleared (lnh_lidar_march_prologue
-    clears it together with the counter in its one launch) — the three sample arrays become views of it."""
+    clears it together with the counter in its one launch) — the three sample arrays become views of it.
+    `ordered=True`: lnh_march_rays_train_ordered — rays[n] = (n, exclusive prefix sum of the counts, count_n), the rows in
+    ray order instead of workgroup-arrival order: the same bits per ray, and a layout (and, on overflow, a set of dropped
+    rays) that depends on the inputs alone."""
     rays_o = rays_o.contiguous().float().view(-1, 3)
     rays_d = rays_d.contiguous().float().view(-1, 3)
     density_bitfield = density_bitfield.contiguous()
@@ -96,8 +100,11 @@ def march_rays_train(rays_o, rays_d, bound, density_bitfield, C, H, nears, fars,
     if step_counter is None:
         step_counter = torch.zeros(2, dtype=torch.int32, device=dev)
     noises = torch.rand(N, dtype=torch.float32, device=dev) if perturb else torch.zeros(N, dtype=torch.float32, device=dev)
-    _hip.call("lnh_march_rays_train", rays_o.data_ptr(), rays_d.data_ptr(), density_bitfield.data_ptr(), float(bound),
-              float(dt_gamma), int(max_steps), N, int(C), int(H), M, nears.contiguous().data_ptr(),
+    if ordered:
+        _hip.require_symbols(["lnh_march_rays_train_ordered"], "march_rays_train(ordered=True)")
+    _hip.call("lnh_march_rays_train_ordered" if ordered else "lnh_march_rays_train", rays_o.data_ptr(), rays_d.data_ptr(),
+              density_bitfield.data_ptr(), float(bound), float(dt_gamma), int(max_steps), N, int(C), int(H), M,
+              nears.contiguous().data_ptr(),
               fars.contiguous().data_ptr(), xyzs.data_ptr(), dirs.data_ptr(), deltas.data_ptr(), rays.data_ptr(),
               step_counter.data_ptr(), noises.data_ptr())
     if force_all_rays or mean_count <= 0:
