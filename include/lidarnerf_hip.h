@@ -704,6 +704,34 @@ LNH_API int lnh_lidar_to_pano(const float *points, uint32_t N, uint32_t H, uint3
 LNH_API int lnh_pano_to_lidar(const float *pano, const float *intensities, uint32_t H, uint32_t W, float fov_up,
                               float fov, float *points, uint8_t *valid, lnh_stream_t stream);
 
+/* ---- the two other projections of convert.py.  (Added without moving lnh_version: detect by symbol.)
+ * Replaces lidar_to_pano_with_intensities_with_bbox_mask   lidarnerf/convert.py:4-97.
+ * lnh_lidar_to_pano_masked: lnh_lidar_to_pano inside the window of rows [r0, r1) and columns [c0, c1) (0 <= r0 <= r1 <= H,
+ *   0 <= c0 <= c1 <= W; the caller derives it from the projected box corners), with the intensity divided by max_intensity
+ *   in float32; outside the window pano = -1 and intensities = 0.  keys_scratch: H*W*8 bytes.
+ * Replaces lidar_to_pano_with_intensities_fpa + parse_z_buffer   lidarnerf/convert.py:253-361.
+ * lnh_lidar_to_pano_fpa: "first-peak averaging".  A pixel that received n points (projection, max_depth and bounds tests of
+ *   lnh_lidar_to_pano), with L = z_buffer_len:
+ *     n == 0          (0, 0)
+ *     n == 1          that point's (dist, intensity)
+ *     2 <= n <= L     the points in point-index order WITHOUT the last-arrived one
+ *     n > L           the L smallest under (dist, point index) WITHOUT the largest of them; L == 1: the smallest point itself
+ *   of these, the ones with dist <= min dist + threshold (float64 on the float32 depths) give
+ *   pano = sum(d w) / sum(w), intensities = sum(i w) / sum(w), w = 1 / d, in float64, stored as float32.
+ *   The result depends on the order of the points in `points` (as the reference's does) and on nothing else: no float
+ *   atomics, and the order in which threads arrive is never read.  1 <= z_buffer_len <= 32, H * W <= 2^24, N < 2^32
+ *   (LNH_ERR_UNSUPPORTED otherwise).  workspace: lnh_lidar_to_pano_fpa_workspace_size(N, H, W) bytes, 8-byte aligned,
+ *   contents irrelevant (0 for an unsupported shape).  The reference's threshold is 0.2.
+ */
+LNH_API int lnh_lidar_to_pano_masked(const float *points, uint32_t N, uint32_t H, uint32_t W, float fov_up, float fov,
+                                     float max_depth, uint32_t r0, uint32_t r1, uint32_t c0, uint32_t c1,
+                                     float max_intensity, void *keys_scratch, float *pano, float *intensities,
+                                     lnh_stream_t stream);
+LNH_API uint64_t lnh_lidar_to_pano_fpa_workspace_size(uint64_t N, uint32_t H, uint32_t W);
+LNH_API int lnh_lidar_to_pano_fpa(const float *points, uint64_t N, uint32_t H, uint32_t W, float fov_up, float fov,
+                                  float max_depth, uint32_t z_buffer_len, double threshold, void *workspace,
+                                  uint64_t workspace_bytes, float *pano, float *intensities, lnh_stream_t stream);
+
 /* ---- evaluation: nearest-neighbour pass of the chamfer distance (extern/chamfer3D/chamfer3D.cu:9-138)
  * dist[j] = min_k |xyz1[j] - xyz2[k]|^2 (squared), idx[j] = the first k attaining it; xyz* are [n,3] / [m,3] f32.
  */
