@@ -732,6 +732,32 @@ LNH_API int lnh_lidar_to_pano_fpa(const float *points, uint64_t N, uint32_t H, u
                                   float max_depth, uint32_t z_buffer_len, double threshold, void *workspace,
                                   uint64_t workspace_bytes, float *pano, float *intensities, lnh_stream_t stream);
 
+/* ---- mesh export: marching cubes over a density volume.  (Added without moving lnh_version: detect by symbol.)
+ * Replaces extract_geometry / mcubes.marching_cubes, nerf/utils.py:169-184.
+ * volume: fp32 [nx, ny, nz], z fastest (the reference's u[x, y, z]).  A corner is below iff v < iso (a value equal to iso and
+ *   a NaN are not below); an edge crosses iff exactly one end is below.  The 256 cases are derived by csrc/gen_mc_tables.py
+ *   (its own face rule and triangle order, not PyMCubes' table; the vertex set does not depend on the table).
+ * lnh_marching_cubes_count: counts u32[4] (device) = vertices V, triangles T, non-finite samples of the volume, 0.  A count
+ *   that does not fit 32 bits is stored as 0xffffffff.  Leaves in the workspace what lnh_marching_cubes_emit reads: call emit
+ *   after it on the same stream with the same volume, sizes, iso and workspace.
+ * lnh_marching_cubes_emit: vertices f32 [V,3] in index units (as mcubes returns them), triangles i32 [T,3]; never writes
+ *   past max_vertices / max_triangles rows.  Order: a vertex belongs to the lattice point at the lower end of its edge;
+ *   vertices in lattice-point order (flattened [x,y,z]), within a point its +x, +y, +z edge; a vertex shared by up to four
+ *   cells appears once.  On an edge from value va to its +axis neighbour vb: t = (iso - va) / (vb - va), moving coordinate
+ *   float(i) + t, in fp32.  Triangles in cell order (flattened [x,y,z] over (nx-1)(ny-1)(nz-1) cells), within a cell the
+ *   table's; normals ((b - a) x (c - a)) point to the below side — on a density field, out of the dense matter.
+ *   The mesh is a function of (volume, iso) alone: no atomics, and no workgroup waits for another.
+ * Errors (before any launch): LNH_ERR_INVALID_ARG for a null pointer, a dimension below 2, a NaN iso, a workspace smaller
+ *   than lnh_marching_cubes_workspace_size(nx, ny, nz) (4-byte aligned, contents irrelevant; 0 for a refused size), a
+ *   capacity of 0; LNH_ERR_UNSUPPORTED for nx * ny * nz >= 2^31 and max_vertices >= 2^31.
+ */
+LNH_API uint64_t lnh_marching_cubes_workspace_size(uint32_t nx, uint32_t ny, uint32_t nz);
+LNH_API int lnh_marching_cubes_count(const float *volume, uint32_t nx, uint32_t ny, uint32_t nz, float iso, void *ws,
+                                     uint64_t ws_bytes, uint32_t *counts, lnh_stream_t stream);
+LNH_API int lnh_marching_cubes_emit(const float *volume, uint32_t nx, uint32_t ny, uint32_t nz, float iso, void *ws,
+                                    uint64_t ws_bytes, float *vertices, uint32_t max_vertices, int32_t *triangles,
+                                    uint32_t max_triangles, lnh_stream_t stream);
+
 /* ---- evaluation: nearest-neighbour pass of the chamfer distance (extern/chamfer3D/chamfer3D.cu:9-138)
  * dist[j] = min_k |xyz1[j] - xyz2[k]|^2 (squared), idx[j] = the first k attaining it; xyz* are [n,3] / [m,3] f32.
  */

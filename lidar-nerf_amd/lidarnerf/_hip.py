@@ -76,6 +76,8 @@ _SIGS = {
     "lnh_pano_to_lidar": [P, P, U32, U32, F32, F32, P, P],
     "lnh_lidar_to_pano_masked": [P, U32, U32, U32, F32, F32, F32, U32, U32, U32, U32, F32, P, P, P],
     "lnh_lidar_to_pano_fpa": [P, C.c_uint64, U32, U32, F32, F32, F32, U32, C.c_double, P, C.c_uint64, P, P],
+    "lnh_marching_cubes_count": [P, U32, U32, U32, F32, P, C.c_uint64, P],
+    "lnh_marching_cubes_emit": [P, U32, U32, U32, F32, P, C.c_uint64, P, U32, P, U32],
     "lnh_chamfer_nn": [P, U32, P, U32, P, P],
     "lnh_grad_check_f16": [P, C.c_uint64, P],
     "lnh_adam_table_step": [P, P, P, P, P, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double, P, P, P, P],
@@ -121,7 +123,9 @@ _OPTIONAL = {"lnh_lidar_eval_frame": "frame evaluation", "lnh_lidar_eval_ssim": 
              "lnh_lidar_sample_batch": "batch sampling", "lnh_lidar_frame_rays": "batch sampling",
              "lnh_march_rays_train_ordered": "ordered marching",
              "lnh_lidar_to_pano_masked": "bbox-mask conversion", "lnh_lidar_to_pano_fpa": "fpa conversion",
-             "lnh_lidar_to_pano_fpa_workspace_size": "fpa conversion"}
+             "lnh_lidar_to_pano_fpa_workspace_size": "fpa conversion",
+             "lnh_marching_cubes_count": "mesh export", "lnh_marching_cubes_emit": "mesh export",
+             "lnh_marching_cubes_workspace_size": "mesh export"}
 for _n in ("lnh_mlp_forward", "lnh_mlp_backward", "lnh_mlp_backward_data", "lnh_mlp_wgrad", "lnh_density_mlp_forward", "lnh_density_mlp_backward",
            "lnh_lidar_dir_term", "lnh_lidar_pack_weights", "lnh_lidar_step_prologue", "lnh_lidar_color_forward", "lnh_lidar_color_backward",
            "lnh_lidar_color_composite_forward", "lnh_lidar_color_backward_image", "lnh_lidar_dir_term_freq",
@@ -133,7 +137,8 @@ EXPORTS = sorted(list(_SIGS) + ["lnh_version", "lnh_last_error", "lnh_arch", "ln
                                  "lnh_grid_backward_plan_info", "lnh_grid_backward_workspace_clear_bytes",
                                  "lnh_grid_backward_set_slice_entries", "lnh_wgrad_workspace_bytes",
                                  "lnh_lidar_loss_ex_workspace_bytes", "lnh_lidar_eval_workspace_bytes",
-                                 "lnh_eval_points_workspace_bytes", "lnh_lidar_to_pano_fpa_workspace_size"])
+                                 "lnh_eval_points_workspace_bytes", "lnh_lidar_to_pano_fpa_workspace_size",
+                                 "lnh_marching_cubes_workspace_size"])
 
 LNH_F32, LNH_F16 = 0, 1
 LNH_BWD_WS_CLEARED, LNH_BWD_TABLE_ZERO = 1, 2
@@ -181,6 +186,9 @@ def lib():
         if hasattr(L, "lnh_lidar_to_pano_fpa_workspace_size"):
             L.lnh_lidar_to_pano_fpa_workspace_size.argtypes = [C.c_uint64, U32, U32]
             L.lnh_lidar_to_pano_fpa_workspace_size.restype = C.c_uint64
+        if hasattr(L, "lnh_marching_cubes_workspace_size"):
+            L.lnh_marching_cubes_workspace_size.argtypes = [U32, U32, U32]
+            L.lnh_marching_cubes_workspace_size.restype = C.c_uint64
         L.lnh_last_error.restype = C.c_char_p
         L.lnh_arch.restype = C.c_char_p
         L.lnh_build_variant.restype = C.c_char_p

@@ -410,6 +410,19 @@ class LidarTrainer:
         return evaluate.evaluate(self, frames, points_intrinsics=points_intrinsics, ema=ema, save_dir=save_dir,
                                  fused_points=self.fused_points)
 
+    # ---- mesh export (nerf/mesh.py; the reference's save_mesh, utils.py:1011-1040)
+    def save_mesh(self, save_path, resolution=256, threshold=10, ema=True):
+        """The reference's Trainer.save_mesh: the density on a resolution^3 lattice over model.aabb_infer (model.density
+        under no_grad and the trainer's autocast setting, the volume kept on the device), marching cubes at `threshold` on
+        the device (csrc/mesh.hip), vertices mapped into the box in float64, a binary PLY at save_path (its directory is
+        created).  With `ema` and a trainer that keeps a parameter average the mesh is that of the averaged weights
+        (ema_weights(), as evaluate() does).  Parameters, optimizer state, counters and captured steps are left as they
+        were.  Not from inside a capture: the two counts are read back once.  Sharded table optimizer: COLLECTIVE
+        (gather_table_state) — call it on every rank.  Triangle order and the choice on ambiguous cells are this package's
+        own, not PyMCubes' (DESIGN §14).  Returns (n_vertices, n_triangles)."""
+        from . import mesh
+        return mesh.save_mesh(self, save_path, resolution=resolution, threshold=threshold, ema=ema)
+
     # ---- what lives outside torch.optim / GradScaler when the table is stepped by the fused kernel
     def table_grad(self):
         """fp32, unscaled gradient of the hash table of the LAST step (the fused path keeps it in fp16 and never sets
