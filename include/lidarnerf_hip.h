@@ -758,6 +758,56 @@ LNH_API int lnh_marching_cubes_emit(const float *volume, uint32_t nx, uint32_t n
                                     uint64_t ws_bytes, float *vertices, uint32_t max_vertices, int32_t *triangles,
                                     uint32_t max_triangles, lnh_stream_t stream);
 
+/* ---- mesh ray casting: watertight closest hit.  (Added without moving lnh_version: detect by symbol.)
+ * Replaces RaycastingScene.cast_rays (Open3D / Embree on the host) of lidarnvs/lidarnvs_meshing.py:293-353.
+ * Mesh: vertices f32 [V,3], triangles i32 [T,3].  Rays: rays_o, rays_d f32 [N,3]; d need not be normalised.
+ * The intersection function (fp32, one rounded operation per operator, nothing contracted), after Woop, Benthin, Wald,
+ * "Watertight Ray/Triangle Intersection", JCGT 2013:
+ *   kz = axis of the largest |d| (ties: the lowest axis); kx = (kz + 1) % 3, ky = (kx + 1) % 3, swapped when d[kz] < 0
+ *   Sx = d[kx] / d[kz], Sy = d[ky] / d[kz], Sz = 1 / d[kz]
+ *   per vertex P of (A, B, C) = (v0, v1, v2): Pkx = P[kx] - o[kx], Pky = P[ky] - o[ky], Pkz = P[kz] - o[kz],
+ *     Px = Pkx - Sx * Pkz, Py = Pky - Sy * Pkz
+ *   U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax; if one of them == 0, all three again from the same
+ *     fp32 operands in double (exact products, the difference rounded to double), each converted to fp32
+ *   miss if their signs are mixed (two-sided, no culling); det = (U + V) + W, miss if det == 0
+ *   Pz = Sz * Pkz, t = ((U * Az + V * Bz) + W * Cz) / det; miss unless t >= 0 and finite; -0 is stored as +0
+ *   t is in units of |d| as given (Open3D's t_hit).  A ray with a zero or non-finite direction or a non-finite origin misses.
+ * Answer for a ray: the minimum over all triangles that hit of the key (bits of t) << 32 | triangle index — the nearest
+ *   hit, among equal t (a shared edge or vertex) the smallest index.  This tie rule and the orientation of the normal are this
+ *   library's own; Embree's are not pinned.
+ *   t_hit f32 [N] (+inf on a miss), primitive_ids i32 [N] (-1), primitive_normals f32 [N,3]: with e1 = v1 - v0, e2 = v2 - v0,
+ *   n = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), len = sqrtf((nx nx + ny ny) + nz nz), n / len (zeros on a
+ *   miss and when len is 0 or not finite); incidences f32 [N] = |(d0 n0 + d1 n1) + d2 n2| (0 on a miss; NULL: not written).
+ * Acceleration: a uniform grid of nx x ny x nz cells (1 ... 1024 each) over the vertices' bounding box.  For every ray and
+ *   every grid the result is exactly the minimum key over ALL triangles; nx = ny = nz = 1 reads the triangle
+ *   array itself.  The order of the entries inside a cell is arrival order and no output depends on it.
+ * lnh_raycast_bounds: box f32[9] (device) = min[3], max[3] of the finite vertex coordinates (exact, no atomics) and the largest
+ *   extent of one triangle per axis; counts u32[4] = non-finite vertex coordinates, triangle indices outside [0, V), 0, 0.
+ *   A scene with a non-zero count must not be built further.
+ * lnh_raycast_build_count: cell_start u32[nx*ny*nz + 1] (exclusive scan of the per-cell list lengths; integer atomics only),
+ *   counts[2], counts[3] = low and high word of the 64-bit entry total.  The caller reads it, refuses a total above
+ *   2^31 - 1, allocates cell_tris u32[entries] and calls lnh_raycast_build_fill with the same mesh, box, grid and cell_start.
+ * lnh_raycast_cast: one thread per ray, no host read, no allocation (capturable).  Never writes outside the N rows.
+ * workspace: lnh_raycast_workspace_size(V, T, nx, ny, nz, entries) bytes, 4-byte aligned, contents irrelevant; serves the
+ *   three build calls (0 for a refused size).
+ * Errors (before any launch): LNH_ERR_INVALID_ARG for a null pointer, an empty mesh (V or T = 0), a grid dimension of 0,
+ *   entries = 0, a workspace too small; LNH_ERR_UNSUPPORTED for V, T or N >= 2^31, more than 1024 cells on an axis, entries
+ *   above 2^31 - 1.
+ */
+LNH_API uint64_t lnh_raycast_workspace_size(uint32_t V, uint32_t T, uint32_t nx, uint32_t ny, uint32_t nz, uint64_t entries);
+LNH_API int lnh_raycast_bounds(const float *vertices, uint32_t V, const int32_t *triangles, uint32_t T, void *ws,
+                               uint64_t ws_bytes, float *box, uint32_t *counts, lnh_stream_t stream);
+LNH_API int lnh_raycast_build_count(const float *vertices, uint32_t V, const int32_t *triangles, uint32_t T, const float *box,
+                                    uint32_t nx, uint32_t ny, uint32_t nz, void *ws, uint64_t ws_bytes, uint32_t *cell_start,
+                                    uint32_t *counts, lnh_stream_t stream);
+LNH_API int lnh_raycast_build_fill(const float *vertices, uint32_t V, const int32_t *triangles, uint32_t T, const float *box,
+                                   uint32_t nx, uint32_t ny, uint32_t nz, void *ws, uint64_t ws_bytes,
+                                   const uint32_t *cell_start, uint32_t *cell_tris, uint64_t entries, lnh_stream_t stream);
+LNH_API int lnh_raycast_cast(const float *vertices, uint32_t V, const int32_t *triangles, uint32_t T, const float *box,
+                             uint32_t nx, uint32_t ny, uint32_t nz, const uint32_t *cell_start, const uint32_t *cell_tris,
+                             uint64_t entries, const float *rays_o, const float *rays_d, uint32_t N, float *t_hit,
+                             int32_t *primitive_ids, float *primitive_normals, float *incidences, lnh_stream_t stream);
+
 /* ---- evaluation: nearest-neighbour pass of the chamfer distance (extern/chamfer3D/chamfer3D.cu:9-138)
  * dist[j] = min_k |xyz1[j] - xyz2[k]|^2 (squared), idx[j] = the first k attaining it; xyz* are [n,3] / [m,3] f32.
  */

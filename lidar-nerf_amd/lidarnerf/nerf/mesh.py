@@ -124,21 +124,72 @@ def write_ply(path, vertices, triangles):
         f.write(faces.tobytes())
 
 
-def save_mesh(trainer, save_path, resolution=256, threshold=10, ema=True):
-    """LidarTrainer.save_mesh: the density volume of the model (of its averaged weights with `ema` and a trainer that keeps an
-    average), marching cubes at `threshold`, vertices mapped into aabb_infer, a PLY file.  Returns (n_vertices, n_triangles)."""
+def read_ply(path):
+    """(vertices float32 [V,3], triangles int32 [T,3]) of a file in exactly the format write_ply writes."""
+    with open(path, "rb") as f:
+        data = f.read()
+    head, sep, body = data.partition(b"end_header\n")
+    lines = head.decode("ascii", "replace").split("\n")
+    if not sep or lines[:2] != ["ply", "format binary_little_endian 1.0"]:
+        raise ValueError(f"read_ply: {path} is not a binary little-endian PLY file")
+    if [ln for ln in lines if ln.startswith("property")] != ["property float x", "property float y", "property float z",
+                                                             "property list uchar int vertex_indices"]:
+        raise ValueError(f"read_ply: {path} does not have the properties write_ply writes (float x y z, list uchar int "
+                         "vertex_indices)")
+    try:
+        nv = int(next(ln for ln in lines if ln.startswith("element vertex")).split()[-1])
+        nf = int(next(ln for ln in lines if ln.startswith("element face")).split()[-1])
+    except (StopIteration, ValueError):
+        raise ValueError(f"read_ply: {path} lacks the vertex / face element lines") from None
+    if len(body) != nv * 12 + nf * 13:
+        raise ValueError(f"read_ply: {path} holds {len(body)} bytes of data, {nv} vertices and {nf} triangles need "
+                         f"{nv * 12 + nf * 13}")
+    vertices = np.frombuffer(body, "<f4", nv * 3).reshape(nv, 3).astype(np.float32)
+    faces = np.frombuffer(body, np.dtype([("n", "u1"), ("idx", "<i4", (3,))]), nf, offset=nv * 12)
+    if nf and not (faces["n"] == 3).all():
+        raise ValueError(f"read_ply: {path} holds a face that is not a triangle")
+    return vertices, faces["idx"].astype(np.int32).reshape(nf, 3)
+
+
+def _trainer_mesh(trainer, resolution, threshold, ema):
+    """(vertices [V,3] fp32 in index units, triangles [T,3] int32) of the trainer's density field, on the device."""
     import contextlib
-    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-        raise RuntimeError("LidarTrainer.save_mesh: not while a stream is capturing (it reads counts back)")
     model = trainer.model
     use_ema = bool(ema) and trainer.ema is not None
-    directory = os.path.dirname(os.path.abspath(save_path))
-    os.makedirs(directory, exist_ok=True)
     trainer.gather_table_state()  # (sharded table optimizer: density reads the fp32 table; collective there, a no-op elsewhere)
     with (trainer.ema_weights() if use_ema else contextlib.nullcontext()):
         u = density_volume(model, resolution, fp16=trainer.fp16, amp_dtype=trainer.amp_dtype)
-    vertices, triangles = marching_cubes(u, threshold)
-    box = model.aabb_infer
+    return marching_cubes(u, threshold)
+
+
+def to_world_device(vertices, box, resolution):
+    """_to_world on the device: the same float64 operations in the same order, rounded to float32 as write_ply rounds them."""
+    box = box.detach().to(vertices.device, torch.float32)
+    b_min, b_max = box[:3], box[3:]
+    world = vertices.double() / (resolution - 1.0) * (b_max - b_min)[None, :].double() + b_min[None, :].double()
+    return world.float()
+
+
+def save_mesh(trainer, save_path, resolution=256, threshold=10, ema=True):
+    """LidarTrainer.save_mesh: the density volume of the model (of its averaged weights with `ema` and a trainer that keeps an
+    average), marching cubes at `threshold`, vertices mapped into aabb_infer, a PLY file.  Returns (n_vertices, n_triangles)."""
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("LidarTrainer.save_mesh: not while a stream is capturing (it reads counts back)")
+    directory = os.path.dirname(os.path.abspath(save_path))
+    os.makedirs(directory, exist_ok=True)
+    vertices, triangles = _trainer_mesh(trainer, resolution, threshold, ema)
+    box = trainer.model.aabb_infer
     world = _to_world(vertices.cpu().numpy(), box[:3], box[3:], resolution)
     write_ply(save_path, world, triangles.cpu().numpy())
     return int(vertices.shape[0]), int(triangles.shape[0])
+
+
+def mesh_scene(trainer, resolution=256, threshold=10, ema=True, grid_resolution=None):
+    """LidarTrainer.mesh_scene: save_mesh's mesh without the file, as a lidarnerf.raycast.RaycastingScene in world
+    coordinates.  The vertices are what read_ply returns from save_mesh's file, bit for bit."""
+    from ..raycast import RaycastingScene
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("LidarTrainer.mesh_scene: not while a stream is capturing (it reads counts back)")
+    vertices, triangles = _trainer_mesh(trainer, resolution, threshold, ema)
+    return RaycastingScene(to_world_device(vertices, trainer.model.aabb_infer, resolution), triangles,
+                           grid_resolution=grid_resolution)

@@ -423,6 +423,14 @@ class LidarTrainer:
         from . import mesh
         return mesh.save_mesh(self, save_path, resolution=resolution, threshold=threshold, ema=ema)
 
+    def mesh_scene(self, resolution=256, threshold=10, ema=True, grid_resolution=None):
+        """save_mesh without the file: the same mesh (vertices in world coordinates, equal bit for bit to what read_ply returns
+        from save_mesh's file) as a lidarnerf.raycast.RaycastingScene on the device, ready for cast_rays / intersect_lidar /
+        raydrop_features (the reference's LidarNVSMeshing, lidarnvs/lidarnvs_meshing.py).  Training state is left as save_mesh
+        leaves it.  Not from inside a capture.  Raises on an empty mesh."""
+        from . import mesh
+        return mesh.mesh_scene(self, resolution=resolution, threshold=threshold, ema=ema, grid_resolution=grid_resolution)
+
     # ---- what lives outside torch.optim / GradScaler when the table is stepped by the fused kernel
     def table_grad(self):
         """fp32, unscaled gradient of the hash table of the LAST step (the fused path keeps it in fp16 and never sets
