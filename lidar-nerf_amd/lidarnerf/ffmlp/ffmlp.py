@@ -186,8 +186,9 @@ class FFMLP(nn.Module):
     """Every width of the reference (16 .. 256, ffmlp.py:202-209) runs on fused MFMA kernels: hidden 16 zero-padded onto the
     hidden-32 kernels, 32 / 64 with at most 3 hidden layers with weights AND weight gradients in registers (forward and
     backward one kernel each), 128 / 256 and deeper nets with weight fragments loaded where they are used and the backward
-    split as the reference splits its own — a fused kernel for the activation / input gradients, library GEMMs for the
-    weight gradients (ffmlp.cu:578-733, 1107-1263).  What has no kernel — input_dim > 128, more than 15 hidden layers — the
+    split as the reference splits its own — a fused kernel for the activation / input gradients, one lnh_mlp_wgrad launch
+    per matrix (csrc/mlp_wgrad.hip, a fixed-order sum over the batch) for the weight gradients (ffmlp.cu:578-733,
+    1107-1263).  What has no kernel — input_dim > 128, more than 15 hidden layers — the
     reference's constructor accepts (any input_dim % 16 == 0, ffmlp.py:202-216), so it is accepted here too and runs every
     layer as a library GEMM (torch.matmul, the same 16-bit storage model, autograd) with a one-time warning;
     `gemm_chain=True` asks for that chain explicitly (no warning), `strict_fused=True` refuses such shapes the way the C
@@ -252,15 +253,15 @@ class FFMLP(nn.Module):
         return torch.cat(parts)
 
     def forward(self, inputs):
-        if self.hidden_dim == 16 and kernel_supported(self.input_dim, 32, self.num_layers - 1):
-            y = _FusedMLP.apply(inputs, self._weights_padded_to_32(), self.input_dim, 32, self.num_layers - 1,
-                                self.activation, self.output_activation, not self.training)
-        elif kernel_supported(self.input_dim, self.hidden_dim, self.num_layers - 1):
-            y = _FusedMLP.apply(inputs, self.weights, self.input_dim, self.hidden_dim, self.num_layers - 1,
-                                self.activation, self.output_activation, not self.training)
-        else:  # wider-input or very deep nets, asked for with gemm_chain=True: library GEMM chain, same semantics
+        if self.gemm_chain:  # no fused kernel for the shape, or the chain was asked for: library GEMM chain, same semantics
             if not inputs.is_cuda:
                 raise RuntimeError("lidarnerf_hip: tensor must live on the GPU (no CPU path in this library)")
             y = gemm_mlp(inputs, self.weights, self.input_dim, self.hidden_dim, self.num_layers - 1, self.activation,
                          self.output_activation)
+        elif self.hidden_dim == 16:
+            y = _FusedMLP.apply(inputs, self._weights_padded_to_32(), self.input_dim, 32, self.num_layers - 1,
+                                self.activation, self.output_activation, not self.training)
+        else:  # (the constructor set gemm_chain for every shape without a fused kernel)
+            y = _FusedMLP.apply(inputs, self.weights, self.input_dim, self.hidden_dim, self.num_layers - 1,
+                                self.activation, self.output_activation, not self.training)
         return y[:, :self.output_dim] if self.output_dim != self.padded_output_dim else y

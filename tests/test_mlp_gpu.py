@@ -125,6 +125,58 @@ def test_hidden_32_forward_backward(in_dim, nhm):
     np.testing.assert_allclose(host(dw).astype(np.float64), dw_want, rtol=5e-3, atol=2e-3 * np.abs(dw_want).max())
 
 
+@pytest.mark.parametrize("sfx", ["", "_bf16"])
+@pytest.mark.parametrize("act", [mlp_ref.ACT_EXP, mlp_ref.ACT_SIGMOID, mlp_ref.ACT_SQUAREPLUS, mlp_ref.ACT_SOFTPLUS])
+@pytest.mark.parametrize("in_dim,H,nhm", [(32, 64, 1), (96, 64, 2), (48, 32, 2), (128, 64, 0)])
+def test_backward_non_relu_activations(in_dim, H, nhm, act, sfx):
+    """The ACT = -1 instantiations of the one-kernel backward (k_mlp_backward, and k_mlp_backward_wi for the one-hidden-layer
+    nets up to 64 inputs; (128, 64, 0) takes k_mlp_backward) with the transcendental activations, against the oracle with
+    the element type's storage roundings.  Inputs scaled as in test_forward_activations (x * 0.5, weights * 0.15).  Bounds:
+    fp16 those of test_backward (rtol 5e-3, atol 2e-3 for gx, 2e-3 * max|dW| for dW), bf16 8x those (2^-8 against 2^-11
+    significant bits, the EPS ratio of tests/test_g7_config1_gpu.py).  Each figure is printed before it is asserted."""
+    from gpu_util import call, host, wgrad
+    dt = torch.bfloat16 if sfx else torch.float16
+    half, k = ("bf16", 8.0) if sfx else (True, 1.0)
+    rnd = (lambda a: mlp_ref.round_bf16(a).astype(np.float64)) if sfx else (lambda a: a.astype(np.float16).astype(np.float64))
+    for B in (130, 1000):
+        r = np.random.default_rng([in_dim, H, nhm, act, B])
+        x = rnd(r.standard_normal((B, in_dim)) * 0.5)
+        n = mlp_ref.ffmlp_num_params(in_dim, 16, H, nhm + 1)
+        w = rnd(r.uniform(-1, 1, n) * 0.15)
+        gy = rnd(r.standard_normal((B, 16)) * 0.1)
+        mats = mlp_ref.ffmlp_split_weights(w, in_dim, 16, H, nhm + 1)
+        gx_want, dws = mlp_ref.mlp_backward(x, mats, gy, act=act, half=half)
+        dw_want = np.concatenate([d.ravel() for d in dws])
+        t = lambda a: torch.from_numpy(a.astype(np.float32)).cuda().to(dt)
+        gx = torch.zeros((B, in_dim), dtype=dt, device="cuda")
+        dw = torch.zeros(n, dtype=torch.float32, device="cuda")
+        call("lnh_mlp_backward" + sfx, t(gy), t(x), t(w), B, in_dim, 16, H, nhm, act, 6, gx, dw, *wgrad())
+        gx_got, dw_got = host(gx.float()).astype(np.float64), host(dw).astype(np.float64)
+        scale = np.abs(dw_want).max()
+        print(f"non-relu backward in {in_dim} H {H} nhm {nhm} act {act} {sfx or 'fp16'} B {B}: max|gx err| "
+              f"{np.abs(gx_got - gx_want).max():.3e} (max|gx| {np.abs(gx_want).max():.3e}), max|dW err| / max|dW| "
+              f"{np.abs(dw_got - dw_want).max() / scale:.3e}")
+        np.testing.assert_allclose(gx_got, gx_want, rtol=5e-3 * k, atol=2e-3 * k)
+        np.testing.assert_allclose(dw_got, dw_want, rtol=5e-3 * k, atol=2e-3 * k * scale)
+        # weights-only variant (grad_inputs == NULL): the same sums
+        dw2 = torch.zeros(n, dtype=torch.float32, device="cuda")
+        call("lnh_mlp_backward" + sfx, t(gy), t(x), t(w), B, in_dim, 16, H, nhm, act, 6, None, dw2, *wgrad())
+        np.testing.assert_allclose(host(dw2), host(dw), rtol=1e-4, atol=1e-4 * scale)
+
+
+@pytest.mark.parametrize("sfx", ["", "_bf16"])
+def test_backward_refuses_sine_by_name(sfx):
+    from gpu_util import call, wgrad
+    dt = torch.bfloat16 if sfx else torch.float16
+    z = torch.zeros((64, 32), dtype=dt, device="cuda")
+    gw = torch.zeros(mlp_ref.ffmlp_num_params(32, 16, 64, 2), device="cuda")
+    with pytest.raises(RuntimeError, match="Sine"):
+        call("lnh_mlp_backward" + sfx, z, z, z, 64, 32, 16, 64, 1, mlp_ref.ACT_SINE, 6, z, gw, *wgrad())
+    with pytest.raises(RuntimeError, match="Sine"):
+        call("lnh_mlp_backward_data" + sfx, z, z, z, 64, 32, 16, 128, 1, mlp_ref.ACT_SINE, z, z)
+    assert float(gw.abs().max()) == 0.0
+
+
 # ------------------------------------------------------------------------------------------------ bf16 operands
 def _bf(a):
     """numpy float array -> CUDA bfloat16 tensor (values are rounded to bf16 by the oracle's own model first)."""
