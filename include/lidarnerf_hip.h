@@ -808,6 +808,50 @@ LNH_API int lnh_raycast_cast(const float *vertices, uint32_t V, const int32_t *t
                              uint64_t entries, const float *rays_o, const float *rays_d, uint32_t N, float *t_hit,
                              int32_t *primitive_ids, float *primitive_normals, float *incidences, lnh_stream_t stream);
 
+/* ---- exact k-nearest neighbours of a point cloud over a uniform grid.  (Added without moving lnh_version: detect by symbol.)
+ * Replaces KDTreeFlann.search_knn_vector_3d (Open3D on the host, one call per hit point) and the np.mean over the neighbours'
+ * intensities of lidarnvs/lidarnvs_meshing.py:132-140 (predict_frame).
+ * Cloud: points f32 [N,3].  Queries: queries f32 [Q,3], 1 <= k <= 16.
+ * The distance (fp32, one rounded operation per operator, nothing contracted):
+ *   dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z, d2 = ((dx * dx) + (dy * dy)) + (dz * dz)
+ * Answer for a query: the min(k, N) smallest keys (bits of d2) << 32 | point index over ALL points, in ascending key order —
+ *   nearest first, among equal distances the smallest index (d2 >= 0: its bit pattern orders like its value).  This tie rule
+ *   is this library's own; KDTreeFlann's is not pinned.
+ *   indices i32 [Q,k], dist2 f32 [Q,k] (squared distances); either may be NULL; ranks >= min(k, N) hold -1 / +inf.
+ *   values f32 [N] and mean f32 [Q] go together (both or NULL): mean = the sum of the neighbours' values in rank order,
+ *   accumulated in fp64, divided by their count, rounded once to fp32.
+ *   valid u8 [Q] (NULL: every query): a query with valid == 0, or with a non-finite coordinate, gets -1 / +inf / mean 0.
+ * Acceleration: a uniform grid of nx x ny x nz cells (1 ... 1024 each) over the points' bounding box.  For every query and every
+ *   grid the outputs are bit-identical to those of nx = ny = nz = 1, which reads the point array itself (DESIGN §16 has the
+ *   stopping rule and its argument: no ulp slack anywhere).  The order of the points inside a cell is arrival order and no output
+ *   depends on it.
+ * lnh_knn_bounds: box, 8 words on the device = min[3], max[3] of the finite coordinates as f32 (exact, no atomics), then the
+ *   count of non-finite coordinates as u32 (saturating), then 0.  A cloud with a non-zero count must not be built further.
+ *   The caller reads the box (the one host read of a build) to choose a grid.
+ * lnh_knn_build_count: cell_start u32[nx*ny*nz + 1] (exclusive scan of the per-cell counts; integer atomics only) and
+ *   slabs f32[2 * (nx + ny + nz)]: per axis (x, then y, then z) smin[i] = the smallest coordinate of the points whose cell index
+ *   along the axis is >= i (+inf where there is none), then in the same layout pmax[i] = the largest coordinate of the points
+ *   whose cell index is <= i (-inf).
+ * lnh_knn_build_fill: sorted f32 [N,4] (16-byte aligned), the points ordered by cell as rows (x, y, z, bits of the original
+ *   index); same cloud, box, grid and cell_start as the count.
+ * lnh_knn_search: one thread per query, ONE launch, no host read, no allocation (capturable).  Never writes outside the Q rows.
+ * workspace: lnh_knn_workspace_size(N, nx, ny, nz) bytes, 4-byte aligned, contents irrelevant; serves the three build calls (0 for
+ *   a refused size).
+ * Errors (before any launch): LNH_ERR_INVALID_ARG for a null pointer, an empty cloud (N = 0), a grid dimension of 0, k outside
+ *   1 ... 16, values without mean or mean without values, no output at all, a workspace too small; LNH_ERR_UNSUPPORTED for N or
+ *   Q >= 2^31, more than 1024 cells on an axis.
+ */
+LNH_API uint64_t lnh_knn_workspace_size(uint32_t N, uint32_t nx, uint32_t ny, uint32_t nz);
+LNH_API int lnh_knn_bounds(const float *points, uint32_t N, void *ws, uint64_t ws_bytes, float *box, lnh_stream_t stream);
+LNH_API int lnh_knn_build_count(const float *points, uint32_t N, const float *box, uint32_t nx, uint32_t ny, uint32_t nz,
+                                void *ws, uint64_t ws_bytes, uint32_t *cell_start, float *slabs, lnh_stream_t stream);
+LNH_API int lnh_knn_build_fill(const float *points, uint32_t N, const float *box, uint32_t nx, uint32_t ny, uint32_t nz,
+                               void *ws, uint64_t ws_bytes, const uint32_t *cell_start, float *sorted, lnh_stream_t stream);
+LNH_API int lnh_knn_search(const float *points, uint32_t N, const float *box, uint32_t nx, uint32_t ny, uint32_t nz,
+                           const uint32_t *cell_start, const float *sorted, const float *slabs, const float *queries,
+                           const uint8_t *valid, uint32_t Q, uint32_t k, const float *values, int32_t *indices, float *dist2,
+                           float *mean, lnh_stream_t stream);
+
 /* ---- evaluation: nearest-neighbour pass of the chamfer distance (extern/chamfer3D/chamfer3D.cu:9-138)
  * dist[j] = min_k |xyz1[j] - xyz2[k]|^2 (squared), idx[j] = the first k attaining it; xyz* are [n,3] / [m,3] f32.
  */

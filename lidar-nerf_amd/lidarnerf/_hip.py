@@ -82,6 +82,10 @@ _SIGS = {
     "lnh_raycast_build_count": [P, U32, P, U32, P, U32, U32, U32, P, C.c_uint64, P, P],
     "lnh_raycast_build_fill": [P, U32, P, U32, P, U32, U32, U32, P, C.c_uint64, P, P, C.c_uint64],
     "lnh_raycast_cast": [P, U32, P, U32, P, U32, U32, U32, P, P, C.c_uint64, P, P, U32, P, P, P, P],
+    "lnh_knn_bounds": [P, U32, P, C.c_uint64, P],
+    "lnh_knn_build_count": [P, U32, P, U32, U32, U32, P, C.c_uint64, P, P],
+    "lnh_knn_build_fill": [P, U32, P, U32, U32, U32, P, C.c_uint64, P, P],
+    "lnh_knn_search": [P, U32, P, U32, U32, U32, P, P, P, P, P, U32, U32, P, P, P, P],
     "lnh_chamfer_nn": [P, U32, P, U32, P, P],
     "lnh_grad_check_f16": [P, C.c_uint64, P],
     "lnh_adam_table_step": [P, P, P, P, P, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double, P, P, P, P],
@@ -132,7 +136,10 @@ _OPTIONAL = {"lnh_lidar_eval_frame": "frame evaluation", "lnh_lidar_eval_ssim": 
              "lnh_marching_cubes_workspace_size": "mesh export",
              "lnh_raycast_bounds": "mesh ray casting", "lnh_raycast_build_count": "mesh ray casting",
              "lnh_raycast_build_fill": "mesh ray casting", "lnh_raycast_cast": "mesh ray casting",
-             "lnh_raycast_workspace_size": "mesh ray casting"}
+             "lnh_raycast_workspace_size": "mesh ray casting",
+             "lnh_knn_bounds": "nearest-neighbour search", "lnh_knn_build_count": "nearest-neighbour search",
+             "lnh_knn_build_fill": "nearest-neighbour search", "lnh_knn_search": "nearest-neighbour search",
+             "lnh_knn_workspace_size": "nearest-neighbour search"}
 for _n in ("lnh_mlp_forward", "lnh_mlp_backward", "lnh_mlp_backward_data", "lnh_mlp_wgrad", "lnh_density_mlp_forward", "lnh_density_mlp_backward",
            "lnh_lidar_dir_term", "lnh_lidar_pack_weights", "lnh_lidar_step_prologue", "lnh_lidar_color_forward", "lnh_lidar_color_backward",
            "lnh_lidar_color_composite_forward", "lnh_lidar_color_backward_image", "lnh_lidar_dir_term_freq",
@@ -145,7 +152,8 @@ EXPORTS = sorted(list(_SIGS) + ["lnh_version", "lnh_last_error", "lnh_arch", "ln
                                  "lnh_grid_backward_set_slice_entries", "lnh_wgrad_workspace_bytes",
                                  "lnh_lidar_loss_ex_workspace_bytes", "lnh_lidar_eval_workspace_bytes",
                                  "lnh_eval_points_workspace_bytes", "lnh_lidar_to_pano_fpa_workspace_size",
-                                 "lnh_marching_cubes_workspace_size", "lnh_raycast_workspace_size"])
+                                 "lnh_marching_cubes_workspace_size", "lnh_raycast_workspace_size",
+                                 "lnh_knn_workspace_size"])
 
 LNH_F32, LNH_F16 = 0, 1
 LNH_BWD_WS_CLEARED, LNH_BWD_TABLE_ZERO = 1, 2
@@ -199,6 +207,9 @@ def lib():
         if hasattr(L, "lnh_raycast_workspace_size"):
             L.lnh_raycast_workspace_size.argtypes = [U32, U32, U32, U32, U32, C.c_uint64]
             L.lnh_raycast_workspace_size.restype = C.c_uint64
+        if hasattr(L, "lnh_knn_workspace_size"):
+            L.lnh_knn_workspace_size.argtypes = [U32, U32, U32, U32]
+            L.lnh_knn_workspace_size.restype = C.c_uint64
         L.lnh_last_error.restype = C.c_char_p
         L.lnh_arch.restype = C.c_char_p
         L.lnh_build_variant.restype = C.c_char_p
