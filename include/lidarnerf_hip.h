@@ -852,6 +852,35 @@ LNH_API int lnh_knn_search(const float *points, uint32_t N, const float *box, ui
                            const uint8_t *valid, uint32_t Q, uint32_t k, const float *values, int32_t *indices, float *dist2,
                            float *mean, lnh_stream_t stream);
 
+/* ---- the ray-drop MLP of the PCGen baseline (lidarnvs/raydrop_train_pcgen.py: RayDrop, run_network with the
+ * identity embedding, img2mse / l1loss, torch.optim.Adam) — csrc/raydrop.hip.  Everything is fp32; no operand is narrowed.
+ * params: ONE flat buffer in torch's nn.Linear layout, 16-byte aligned: for hidden layer l = 0 .. D-1 weight[l] [W, in_l]
+ *   row-major (in_0 = 5, else W) then bias[l] [W]; then output.weight [1, W] and output.bias [1].
+ *   lnh_raydrop_param_count(D, W) = 5 W + W + (D - 1)(W^2 + W) + W + 1 floats (0 for an unsupported shape).
+ *   Supported: W 128 or 256, 1 <= D <= 8; anything else returns LNH_ERR_INVALID_ARG.
+ * rows: [N, stride] f32, stride >= 5: direction x, y, z, depth, intensity, [target] (lnh_raydrop_grad: stride 6).  A row at or
+ *   behind N is never read.
+ * lnh_raydrop_forward: out[N] = the raw network output (no sigmoid).  One launch.
+ * lnh_raydrop_grad: forward, loss, backward and every weight and bias gradient of rows [B, 6]; two launches.
+ *   loss_type 0: e_i = (out_i - t_i)^2 (img2mse, mseloss), 1: |out_i - t_i| (l1loss).  loss[0] = (sum_i e_i) / B with one
+ *   division.  The backward carries the unnormalised output gradient 2 (out_i - t_i) (L1: sign, 0 at 0); every element of
+ *   grad[P] is its sum over the batch divided by B once, and is OVERWRITTEN.  No float atomics: loss and grad are functions of
+ *   (params, rows, B) alone — the order of every sum depends on B, D and W only — and two calls are bit-identical.
+ *   ws: lnh_raydrop_workspace_size(D, W, B) bytes (0 for a refused shape or B), 16-byte aligned, contents irrelevant.
+ * lnh_raydrop_adam: torch.optim.Adam (no weight decay, no amsgrad) on the flat buffer.  The step count lives on the device,
+ *   double-buffered (step_in != step_out, one float each, as in lnh_adam_table_step): t = *step_in is the count BEFORE this
+ *   step, *step_out = t + 1, and the learning rate is lr_table[min(t, lr_len - 1)], read from device memory.
+ * No call reads the host or allocates; all three can be captured in a hipGraph. */
+LNH_API uint64_t lnh_raydrop_param_count(uint32_t D, uint32_t W);
+LNH_API uint64_t lnh_raydrop_workspace_size(uint32_t D, uint32_t W, uint32_t B);
+LNH_API int lnh_raydrop_forward(const float *params, uint32_t D, uint32_t W, const float *rows, uint32_t stride, uint32_t N,
+                                float *out, lnh_stream_t stream);
+LNH_API int lnh_raydrop_grad(const float *params, uint32_t D, uint32_t W, const float *rows, uint32_t B, uint32_t loss_type,
+                             void *ws, uint64_t ws_bytes, float *loss, float *grad, lnh_stream_t stream);
+LNH_API int lnh_raydrop_adam(float *params, float *exp_avg, float *exp_avg_sq, const float *grad, uint32_t P,
+                             const float *lr_table, uint32_t lr_len, const float *step_in, float *step_out, double beta1,
+                             double beta2, double eps, lnh_stream_t stream);
+
 /* ---- evaluation: nearest-neighbour pass of the chamfer distance (extern/chamfer3D/chamfer3D.cu:9-138)
  * dist[j] = min_k |xyz1[j] - xyz2[k]|^2 (squared), idx[j] = the first k attaining it; xyz* are [n,3] / [m,3] f32.
  */

@@ -86,6 +86,9 @@ _SIGS = {
     "lnh_knn_build_count": [P, U32, P, U32, U32, U32, P, C.c_uint64, P, P],
     "lnh_knn_build_fill": [P, U32, P, U32, U32, U32, P, C.c_uint64, P, P],
     "lnh_knn_search": [P, U32, P, U32, U32, U32, P, P, P, P, P, U32, U32, P, P, P, P],
+    "lnh_raydrop_forward": [P, U32, U32, P, U32, U32, P],
+    "lnh_raydrop_grad": [P, U32, U32, P, U32, U32, P, C.c_uint64, P, P],
+    "lnh_raydrop_adam": [P, P, P, P, U32, P, U32, P, P, C.c_double, C.c_double, C.c_double],
     "lnh_chamfer_nn": [P, U32, P, U32, P, P],
     "lnh_grad_check_f16": [P, C.c_uint64, P],
     "lnh_adam_table_step": [P, P, P, P, P, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double, P, P, P, P],
@@ -139,7 +142,9 @@ _OPTIONAL = {"lnh_lidar_eval_frame": "frame evaluation", "lnh_lidar_eval_ssim": 
              "lnh_raycast_workspace_size": "mesh ray casting",
              "lnh_knn_bounds": "nearest-neighbour search", "lnh_knn_build_count": "nearest-neighbour search",
              "lnh_knn_build_fill": "nearest-neighbour search", "lnh_knn_search": "nearest-neighbour search",
-             "lnh_knn_workspace_size": "nearest-neighbour search"}
+             "lnh_knn_workspace_size": "nearest-neighbour search",
+             "lnh_raydrop_forward": "ray-drop MLP", "lnh_raydrop_grad": "ray-drop MLP", "lnh_raydrop_adam": "ray-drop MLP",
+             "lnh_raydrop_workspace_size": "ray-drop MLP", "lnh_raydrop_param_count": "ray-drop MLP"}
 for _n in ("lnh_mlp_forward", "lnh_mlp_backward", "lnh_mlp_backward_data", "lnh_mlp_wgrad", "lnh_density_mlp_forward", "lnh_density_mlp_backward",
            "lnh_lidar_dir_term", "lnh_lidar_pack_weights", "lnh_lidar_step_prologue", "lnh_lidar_color_forward", "lnh_lidar_color_backward",
            "lnh_lidar_color_composite_forward", "lnh_lidar_color_backward_image", "lnh_lidar_dir_term_freq",
@@ -153,7 +158,7 @@ EXPORTS = sorted(list(_SIGS) + ["lnh_version", "lnh_last_error", "lnh_arch", "ln
                                  "lnh_lidar_loss_ex_workspace_bytes", "lnh_lidar_eval_workspace_bytes",
                                  "lnh_eval_points_workspace_bytes", "lnh_lidar_to_pano_fpa_workspace_size",
                                  "lnh_marching_cubes_workspace_size", "lnh_raycast_workspace_size",
-                                 "lnh_knn_workspace_size"])
+                                 "lnh_knn_workspace_size", "lnh_raydrop_workspace_size", "lnh_raydrop_param_count"])
 
 LNH_F32, LNH_F16 = 0, 1
 LNH_BWD_WS_CLEARED, LNH_BWD_TABLE_ZERO = 1, 2
@@ -210,6 +215,11 @@ def lib():
         if hasattr(L, "lnh_knn_workspace_size"):
             L.lnh_knn_workspace_size.argtypes = [U32, U32, U32, U32]
             L.lnh_knn_workspace_size.restype = C.c_uint64
+        if hasattr(L, "lnh_raydrop_workspace_size"):
+            L.lnh_raydrop_workspace_size.argtypes = [U32, U32, U32]
+            L.lnh_raydrop_workspace_size.restype = C.c_uint64
+            L.lnh_raydrop_param_count.argtypes = [U32, U32]
+            L.lnh_raydrop_param_count.restype = C.c_uint64
         L.lnh_last_error.restype = C.c_char_p
         L.lnh_arch.restype = C.c_char_p
         L.lnh_build_variant.restype = C.c_char_p

@@ -5,8 +5,12 @@ the GPU.
 
 What is not pinned against the reference: Open3D's order among equidistant neighbours and NumPy's float32 np.mean
 (here: smallest index first, an fp64 rank-order sum rounded once), and its float64 pose matrices (here fp32).  The pose is taken
-as affine (last row 0 0 0 1), which is what homo_project's division by w amounts to for a LiDAR pose.  The ray-drop U-Net, its
-training and the meshing itself (fit) are not part of this.  No CPU fallback."""
+as affine (last row 0 0 0 1), which is what homo_project's division by w amounts to for a LiDAR pose.  The ray-drop U-Net of the
+mesh baselines, its training and the meshing itself (MeshNVS has no fit) are not part of this.  No CPU fallback.
+
+PointCloudNVS is the point-cloud baseline, LidarNVSPCGen of lidarnvs/lidarnvs_pcgen.py:16-248: the training cloud itself is
+projected ("cp": closest point, "fpa": first-peak averaging over a z-buffer), turned back into a cloud, and masked by the
+ray-drop MLP (lidarnerf/raydrop.py) — DESIGN §17."""
 import math
 
 import numpy as np
@@ -15,6 +19,7 @@ import torch
 from . import convert
 from .knn import PointCloudIndex, _check_k, _cloud
 from .raycast import RaycastingScene
+from .raydrop import IN_FEATURES
 
 CLOUD_KEYS = ("points", "point_intensities", "local_points", "local_point_intensities")
 
@@ -127,3 +132,132 @@ class MeshNVS:
         return {"pano": pano, "intensities": intensities, "points": transform_points(local_points, pose),
                 "point_intensities": local_inten, "local_points": local_points, "local_point_intensities": local_inten,
                 "hit_dict": frame["hit_dict"]}
+
+
+PCGEN_KEYS = ("pano", "intensities") + CLOUD_KEYS
+
+
+class PointCloudNVS:
+    """LidarNVSPCGen with every array on the device.  points float [N,3] / point_intensities float [N]: the world-frame
+    training cloud (tensors or NumPy arrays; `device` or the current GPU), or None until fit().  raycasting: "cp"
+    (convert.lidar_to_pano_with_intensities) or "fpa" (..._fpa with z_buffer_len).  raydrop: a raydrop.RayDropMLP or any callable
+    from the [H*W, 5] rows (direction, depth, intensity) to [H*W, 1]; a ray is kept where the output is > 0.5."""
+
+    def __init__(self, points=None, point_intensities=None, raycasting="cp", raydrop=None, z_buffer_len=10, device=None):
+        if raycasting not in ("cp", "fpa"):
+            raise ValueError(f"PointCloudNVS: raycasting must be 'cp' or 'fpa', got {raycasting!r}")
+        if int(z_buffer_len) < 1:
+            raise ValueError("PointCloudNVS: z_buffer_len must be at least 1")
+        if not torch.cuda.is_available():
+            raise RuntimeError("PointCloudNVS: needs a GPU (no CPU fallback)")
+        self.raycasting, self.raydrop, self.z_buffer_len = raycasting, raydrop, int(z_buffer_len)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.points = self.point_intensities = None
+        if points is not None:
+            self._set_cloud(points, point_intensities)
+
+    def _set_cloud(self, points, point_intensities):
+        def tensor(a):
+            return torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
+        pts, inten = tensor(points), tensor(point_intensities)
+        if not torch.is_tensor(pts) or pts.dim() != 2 or pts.shape[1] != 3 or not pts.is_floating_point():
+            raise ValueError("PointCloudNVS: points must be a float [N, 3] tensor or NumPy array")
+        if not torch.is_tensor(inten) or not inten.is_floating_point() or inten.numel() != pts.shape[0]:
+            raise ValueError(f"PointCloudNVS: point_intensities must be {pts.shape[0]} floats")
+        self.points = pts.detach().to(self.device, torch.float32).contiguous()
+        self.point_intensities = inten.detach().reshape(-1).to(self.device, torch.float32).contiguous()
+
+    def fit(self, frames):
+        """frames: an iterable of dicts with "points" [n,3] and "point_intensities" [n] in WORLD coordinates (what the
+        reference's extract_dataset_frame returns); their concatenation becomes the cloud, which is all the reference's fit
+        does."""
+        frames = list(frames)
+        if not frames:
+            raise ValueError("PointCloudNVS.fit: no frames")
+
+        def tensor(a):
+            return (torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a).to(self.device, torch.float32)
+        self._set_cloud(torch.cat([tensor(f["points"]).reshape(-1, 3) for f in frames]),
+                        torch.cat([tensor(f["point_intensities"]).reshape(-1) for f in frames]))
+        return self
+
+    def _cloud(self):
+        if self.points is None:
+            raise RuntimeError("PointCloudNVS: no cloud yet (pass points or call fit)")
+        return self.points, self.point_intensities
+
+    def directions(self, lidar_K, lidar_H, lidar_W):
+        """get_direction of lidarnvs_pcgen.py:236-248 in fp32 on the device: [H, W, 3], the operations in the reference's order."""
+        H, W = int(lidar_H), int(lidar_W)
+        fov_up, fov = float(lidar_K[0]), float(lidar_K[1])
+        i = torch.arange(W, dtype=torch.float32, device=self.device)[None, :].expand(H, W)
+        j = torch.arange(H, dtype=torch.float32, device=self.device)[:, None].expand(H, W)
+        beta = -(i - W / 2) / W * 2 * math.pi
+        alpha = (fov_up - j / H * fov) / 180 * math.pi
+        ca = torch.cos(alpha)
+        return torch.stack([ca * torch.cos(beta), ca * torch.sin(beta), torch.sin(alpha)], -1)
+
+    def predict_frame(self, lidar_K, lidar_pose, lidar_H, lidar_W, compact=True):
+        """The reference's predict_dict as device tensors: pano f32 [H,W], intensities f32 [H,W] and, with compact=True, the
+        clouds read back from them — local_points [M,3], local_point_intensities [M], points [M,3] (the pose applied),
+        point_intensities [M].  With compact=False only the two images are returned and nothing reads the host."""
+        H, W = int(lidar_H), int(lidar_W)
+        pose = _pose(lidar_pose, self.device)
+        points, inten = self._cloud()
+        rows = torch.cat([world_to_lidar(points, pose), inten[:, None]], dim=1)
+        if self.raycasting == "cp":
+            pano, intensities = convert.lidar_to_pano_with_intensities(rows, H, W, lidar_K)
+        else:
+            pano, intensities = convert.lidar_to_pano_with_intensities_fpa(rows, H, W, lidar_K, z_buffer_len=self.z_buffer_len)
+        out = {"pano": pano, "intensities": intensities}
+        if compact:
+            out.update(self._clouds(pano, intensities, lidar_K, pose))
+        return out
+
+    @staticmethod
+    def _clouds(pano, intensities, lidar_K, pose):
+        local4 = convert.pano_to_lidar_with_intensities(pano, intensities, lidar_K)
+        local_points = local4[:, :3].contiguous()
+        local_inten = local4[:, 3].contiguous()
+        return {"points": transform_points(local_points, pose), "point_intensities": local_inten,
+                "local_points": local_points, "local_point_intensities": local_inten}
+
+    def raydrop_rows(self, lidar_K, lidar_pose, lidar_H, lidar_W, gt_pano=None, frame=None):
+        """The ray-drop MLP's input rows of a frame, [H*W, 5]: direction, predicted depth, predicted intensity (the order of
+        run_network's cat).  With gt_pano [H,W] the training rows [n, 6] after the filtering of raydrop_train_pcgen.py:317-328:
+        only pixels with gt_pano > -1, target 0 where gt_pano == 0, else 1."""
+        H, W = int(lidar_H), int(lidar_W)
+        if frame is None:
+            frame = self.predict_frame(lidar_K, lidar_pose, H, W, compact=False)
+        rows = torch.cat([self.directions(lidar_K, H, W).reshape(-1, 3), frame["pano"].reshape(-1, 1),
+                          frame["intensities"].reshape(-1, 1)], dim=1)
+        if gt_pano is None:
+            return rows
+        gt = torch.from_numpy(np.ascontiguousarray(gt_pano)) if isinstance(gt_pano, np.ndarray) else gt_pano
+        gt = gt.detach().to(self.device, torch.float32).reshape(-1)
+        if gt.numel() != H * W:
+            raise ValueError(f"PointCloudNVS.raydrop_rows: gt_pano must be [{H}, {W}]")
+        target = torch.where(gt == 0, 0.0, 1.0).to(torch.float32)
+        return torch.cat([rows, target[:, None]], dim=1)[gt > -1]
+
+    @torch.no_grad()
+    def predict_frame_with_raydrop(self, lidar_K, lidar_pose, lidar_H, lidar_W, raydrop=None):
+        """lidarnvs_pcgen.py:131-194: pano and intensities multiplied by the mask `output > 0.5` — unless the mask is zero
+        everywhere, which leaves the frame as it is (the reference's rule) — and turned back into the clouds."""
+        model = self.raydrop if raydrop is None else raydrop
+        if model is None:
+            raise RuntimeError("PointCloudNVS.predict_frame_with_raydrop: no ray-drop model")
+        H, W = int(lidar_H), int(lidar_W)
+        pose = _pose(lidar_pose, self.device)
+        frame = self.predict_frame(lidar_K, pose, H, W, compact=False)
+        rows = self.raydrop_rows(lidar_K, pose, H, W, frame=frame)
+        assert rows.shape == (H * W, IN_FEATURES)
+        out = model(rows)
+        if not torch.is_tensor(out) or tuple(out.shape) != (H * W, 1):
+            raise ValueError(f"PointCloudNVS.predict_frame_with_raydrop: the model must return [{H * W}, 1] outputs")
+        keep = (out.detach().to(self.device, torch.float32) > 0.5).reshape(H, W)
+        keep = torch.where(keep.any(), keep, torch.ones_like(keep)).to(torch.float32)
+        pano, intensities = frame["pano"] * keep, frame["intensities"] * keep
+        result = {"pano": pano, "intensities": intensities}
+        result.update(self._clouds(pano, intensities, lidar_K, pose))
+        return result
