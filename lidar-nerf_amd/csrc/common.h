@@ -88,6 +88,21 @@ __device__ __forceinline__ double wave_sum(double v) {
     for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
     return v;
 }
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
+    return v;
+}
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
 // sum over the workgroup (kT threads) in a fixed order; every thread receives it.  `sh`: kT / 64 doubles of LDS.
 template <uint32_t kT>
 __device__ __forceinline__ double block_sum(double v, double *sh) {

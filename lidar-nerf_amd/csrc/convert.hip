@@ -15,6 +15,7 @@
 // resolve pipeline further down.  All three project with pano_pixel().
 #include "common.h"
 #include "pano_geom.h"
+#include "scan.h"
 
 namespace {
 
@@ -90,7 +91,7 @@ k_lidar_to_pano_resolve_masked(const float *__restrict__ pts, const unsigned lon
 // convert.py:253-361 (lidar_to_pano_with_intensities_fpa + parse_z_buffer).  Four launches on one stream; the launch
 // boundaries are the only ordering there is, and the only atomics are integer ones:
 //   k_fpa_count    one thread per point: pix[i] = pixel id (kNoPixel = dropped), count[pixel] += 1
-//   k_fpa_scan     ONE workgroup: offset = exclusive scan of count (the pattern of raymarch.hip's k_march_scan)
+//   k_fpa_scan     ONE workgroup: offset = exclusive scan of count (scan.h workgroup_scan)
 //   k_fpa_scatter  one thread per point: keys[offset[pixel] + cursor[pixel]++] = (dist bits << 32 | point index)
 //   k_fpa_resolve  one wavefront per pixel: the reference's rule on the bucket, read as a SET (slot order is arbitrary)
 // Workspace: keys u64[N] | pix u32[N] | count u32[HW] | cursor u32[HW] | offset u32[HW].
@@ -105,37 +106,10 @@ k_fpa_count(const float *__restrict__ pts, uint32_t N, PanoGeom g, uint32_t *__r
     if (p != kNoPixel) atomicAdd(&count[p], 1u);
 }
 
-constexpr uint32_t kFpaScanThreads = 1024, kFpaScanPerThread = 4, kFpaScanTile = kFpaScanThreads * kFpaScanPerThread;
-__global__ void __launch_bounds__(kFpaScanThreads)
+__global__ void __launch_bounds__(kScanThreads)
 k_fpa_scan(const uint32_t *__restrict__ count, uint32_t *__restrict__ offset, uint32_t HW) {
-    constexpr uint32_t kWaves = kFpaScanThreads / 64;
-    __shared__ uint32_t s_wave[kWaves];
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint32_t carry = 0;  // counts of the tiles in front of this one: the same in every thread
-    for (uint32_t tile = 0; tile < HW; tile += kFpaScanTile) {
-        const uint32_t first = tile + threadIdx.x * kFpaScanPerThread;
-        uint32_t c[kFpaScanPerThread], mine = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < kFpaScanPerThread; k++) {
-            c[k] = first + k < HW ? count[first + k] : 0u;
-            mine += c[k];
-        }
-        const uint32_t incl = wave_scan_add_u32(mine);
-        if (lane == 63) s_wave[wv] = incl;
-        __syncthreads();
-        const uint32_t wt = lane < kWaves ? s_wave[lane] : 0u;
-        const uint32_t wincl = wave_scan_add_u32(wt);
-        const uint32_t wave_off = (uint32_t)__shfl((int)(wincl - wt), (int)wv, 64);
-        const uint32_t tile_total = (uint32_t)__shfl((int)wincl, (int)kWaves - 1, 64);
-        uint32_t off = carry + wave_off + (incl - mine);
-#pragma unroll
-        for (uint32_t k = 0; k < kFpaScanPerThread; k++) {
-            if (first + k < HW) offset[first + k] = off;
-            off += c[k];
-        }
-        carry += tile_total;
-        __syncthreads();  // s_wave is rewritten by the next tile
-    }
+    (void)workgroup_scan<uint32_t>(
+        HW, 0u, [&](uint32_t p, bool) { return count[p]; }, [&](uint32_t p, uint32_t off) { offset[p] = off; });
 }
 
 __global__ void __launch_bounds__(256)
@@ -353,7 +327,7 @@ int lnh_lidar_to_pano_fpa(const float *points, uint64_t N, uint32_t H, uint32_t 
     if (n) {
         LNH_LAUNCH(k_fpa_count, dim3(div_up(n, 256)), dim3(256), 0, s, points, n, g, pix, count);
         if ((rc = lnh_check_launch("lnh_lidar_to_pano_fpa(count)"))) return rc;
-        LNH_LAUNCH(k_fpa_scan, dim3(1), dim3(kFpaScanThreads), 0, s, (const uint32_t *)count, offset, hw);
+        LNH_LAUNCH(k_fpa_scan, dim3(1), dim3(kScanThreads), 0, s, (const uint32_t *)count, offset, hw);
         if ((rc = lnh_check_launch("lnh_lidar_to_pano_fpa(scan)"))) return rc;
         LNH_LAUNCH(k_fpa_scatter, dim3(div_up(n, 256)), dim3(256), 0, s, points, n, (const uint32_t *)pix,
                    (const uint32_t *)offset, cursor, keys);

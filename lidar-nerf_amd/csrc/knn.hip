@@ -21,21 +21,20 @@
 // A column (x, y) or a cell of a shell is skipped when the same kind of lower bound already exceeds the k-th key: the points
 // skipped could not have entered.  A grid of 1 x 1 x 1 reads the point array itself.
 //
+// The grid itself (box -> cells, cell_of, the bounds passes' reduce) is cell_grid.h, shared with raycast.hip; the scan is scan.h.
 // Build passes, none waits for another workgroup: k_knn_bounds (per-workgroup min / max / count, no atomics), k_knn_bounds_finish
 // (one workgroup), k_knn_count (integer atomics: a counter per cell, min / max per slab on an order-preserving integer encoding
-// of the float), k_knn_scan (one workgroup, tiles of kKnnScanTile; its first threads also form smin / pmax), k_knn_fill (an
+// of the float), k_knn_scan (one workgroup, scan.h workgroup_scan; its first threads also form smin / pmax), k_knn_fill (an
 // integer cursor per cell: the order inside a cell is arrival order and no output depends on it).  The fill writes the points
 // sorted by cell as 16-byte rows (x, y, z, bits of the original index): the cells (x, y, z0 ... z1) are ONE contiguous read.
 #include "common.h"
 #include "knn_walk.h"
+#include "scan.h"
 
 namespace {
 
-constexpr uint32_t kKnnThreads = 256;
-constexpr uint32_t kKnnBoundsGroupsMax = 1024;
-constexpr uint32_t kKnnBoundsWords = 8;  // per-workgroup partial: lo[3], hi[3], non-finite coordinates, 0
-constexpr uint32_t kKnnScanThreads = 1024, kKnnScanPerThread = 4, kKnnScanTile = kKnnScanThreads * kKnnScanPerThread;
-constexpr uint32_t kKnnMaxCellsPerAxis = 1024;
+constexpr uint32_t kKnnThreads = kCellThreads;
+constexpr uint32_t kKnnBoundsWords = 8;  // per-workgroup partial (cell_grid.h): lo[3], hi[3], non-finite coordinates, 0
 constexpr uint32_t kKnnSearchThreads = 128;
 constexpr uint32_t kKnnMaxK = 16;
 
@@ -47,82 +46,23 @@ __device__ __forceinline__ uint32_t knn_enc(float x) {
 __device__ __forceinline__ float knn_dec(uint32_t e) { return __uint_as_float(e & 0x80000000u ? e & 0x7fffffffu : ~e); }
 
 // --------------------------------------------------------------------------------------------------------------- bounds
-__device__ __forceinline__ float knn_wave_min(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float knn_wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ uint32_t knn_wave_add(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
-    return v;
-}
-// min / max / sum over the 256 threads; thread 0 writes the 8 words of the partial
-__device__ __forceinline__ void knn_block_reduce(float (&lo)[3], float (&hi)[3], uint32_t bad, uint32_t *__restrict__ out) {
-    __shared__ float s_f[4][6];
-    __shared__ uint32_t s_u[4];
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int a = 0; a < 3; a++) lo[a] = knn_wave_min(lo[a]), hi[a] = knn_wave_max(hi[a]);
-    bad = knn_wave_add(bad);
-    if (lane == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; a++) s_f[wv][a] = lo[a], s_f[wv][3 + a] = hi[a];
-        s_u[wv] = bad;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int a = 0; a < 6; a++) {
-            float v = s_f[0][a];
-            for (int w = 1; w < 4; w++) v = a < 3 ? fminf(v, s_f[w][a]) : fmaxf(v, s_f[w][a]);
-            out[a] = __float_as_uint(v);
-        }
-        out[6] = s_u[0] + s_u[1] + s_u[2] + s_u[3];
-        out[7] = 0u;
-    }
-}
-
 __global__ void __launch_bounds__(kKnnThreads)
 k_knn_bounds(const float *__restrict__ points, uint32_t N, uint32_t *__restrict__ partials) {
     const float inf = __uint_as_float(0x7f800000u);
-    float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
-    uint32_t bad = 0;
-    const uint32_t stride = gridDim.x * kKnnThreads;
-    for (uint32_t i = blockIdx.x * kKnnThreads + threadIdx.x; i < N; i += stride) {  // (i + stride < 2^32: N < 2^31, stride <= 2^18)
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            const float x = points[(size_t)i * 3 + a];
-            if (knn_finite(x))
-                lo[a] = fminf(lo[a], x), hi[a] = fmaxf(hi[a], x);
-            else
-                bad++;
-        }
-    }
-    knn_block_reduce(lo, hi, bad, partials + (size_t)blockIdx.x * kKnnBoundsWords);
+    float f[6] = {inf, inf, inf, -inf, -inf, -inf};
+    uint32_t bad[1] = {0};
+    cell_bounds_accumulate(points, N, f, f + 3, bad[0]);
+    cell_block_reduce(f, bad, partials + (size_t)blockIdx.x * kKnnBoundsWords);
 }
 
 __global__ void __launch_bounds__(kKnnThreads)
 k_knn_bounds_finish(const uint32_t *__restrict__ partials, uint32_t G, uint32_t *__restrict__ box) {
     const float inf = __uint_as_float(0x7f800000u);
-    float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
-    uint32_t bad = 0;
-    for (uint32_t g = threadIdx.x; g < G; g += kKnnThreads) {
-        const uint32_t *p = partials + (size_t)g * kKnnBoundsWords;
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            lo[a] = fminf(lo[a], __uint_as_float(p[a]));
-            hi[a] = fmaxf(hi[a], __uint_as_float(p[3 + a]));
-        }
-        bad = bad + p[6] < bad ? 0xffffffffu : bad + p[6];  // a count that does not fit 32 bits saturates
-    }
+    float f[6] = {inf, inf, inf, -inf, -inf, -inf};
+    uint32_t bad[1] = {0};
+    cell_merge_partials(partials, G, f, bad);
     __shared__ uint32_t s_out[kKnnBoundsWords];
-    knn_block_reduce(lo, hi, min(bad, 0xffffffu), s_out);  // (256 * 2^24 fits; nonzero stays nonzero)
+    cell_block_reduce(f, bad, s_out);
     __syncthreads();
     if (threadIdx.x < kKnnBoundsWords) box[threadIdx.x] = s_out[threadIdx.x];
 }
@@ -132,12 +72,12 @@ struct KnnCell {
     uint32_t c[3];
     float p[3];
 };
-__device__ __forceinline__ KnnCell knn_point_cell(const float *__restrict__ points, uint32_t i, const KnnGrid &g) {
+__device__ __forceinline__ KnnCell knn_point_cell(const float *__restrict__ points, uint32_t i, const CellGrid &g) {
     KnnCell k;
 #pragma unroll
     for (int a = 0; a < 3; a++) {
         k.p[a] = points[(size_t)i * 3 + a];
-        k.c[a] = knn_cell_of(k.p[a], g.lo[a], g.inv[a], g.n[a]);
+        k.c[a] = cell_of(k.p[a], g.lo[a], g.inv[a], g.n[a]);
     }
     return k;
 }
@@ -148,7 +88,7 @@ k_knn_count(const float *__restrict__ points, uint32_t N, const float *__restric
             uint32_t *__restrict__ cell_count, uint32_t *__restrict__ slab_enc) {
     const uint32_t i = blockIdx.x * kKnnThreads + threadIdx.x;
     if (i >= N) return;
-    const KnnGrid g = knn_grid(box, nx, ny, nz);
+    const CellGrid g = cell_grid(box, nx, ny, nz);
     const KnnCell k = knn_point_cell(points, i, g);
     atomicAdd(&cell_count[(k.c[0] * ny + k.c[1]) * nz + k.c[2]], 1u);  // < cells
     const uint32_t S = nx + ny + nz, off[3] = {0u, nx, nx + ny};
@@ -170,12 +110,9 @@ k_knn_slab_preset(uint32_t *__restrict__ slab_enc, uint32_t S) {
 
 // exclusive scan of cell_count[cells] -> cell_start[cells + 1]; threads 0 ... 5 also turn the slab extremes into
 // slabs f32 [2][nx + ny + nz]: smin (minimum over the slabs >= i) and pmax (maximum over the slabs <= i) per axis
-__global__ void __launch_bounds__(kKnnScanThreads)
+__global__ void __launch_bounds__(kScanThreads)
 k_knn_scan(const uint32_t *__restrict__ cell_count, uint32_t cells, uint32_t *__restrict__ cell_start,
            const uint32_t *__restrict__ slab_enc, uint32_t nx, uint32_t ny, uint32_t nz, float *__restrict__ slabs) {
-    constexpr uint32_t kWaves = kKnnScanThreads / 64;
-    __shared__ uint32_t s_w[kWaves];
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (threadIdx.x < 6) {
         const uint32_t a = threadIdx.x % 3, S = nx + ny + nz;
         const uint32_t n = a == 0 ? nx : (a == 1 ? ny : nz), off = a == 0 ? 0u : (a == 1 ? nx : nx + ny);
@@ -195,40 +132,9 @@ k_knn_scan(const uint32_t *__restrict__ cell_count, uint32_t cells, uint32_t *__
             }
         }
     }
-    uint32_t carry = 0;  // total of the tiles in front of this one: the same in every thread (the total is N < 2^31)
-    for (uint32_t tile = 0; tile < cells; tile += kKnnScanTile) {
-        const uint32_t first = tile + threadIdx.x * kKnnScanPerThread;
-        uint32_t c[kKnnScanPerThread], mine = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < kKnnScanPerThread; k++) {
-            c[k] = first + k < cells ? cell_count[first + k] : 0u;
-            mine += c[k];
-        }
-        uint32_t incl = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t up = (uint32_t)__shfl_up((int)incl, o, 64);
-            if ((int)lane >= o) incl += up;
-        }
-        if (lane == 63) s_w[wv] = incl;
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < kWaves; w++) {
-            const uint32_t x = s_w[w];
-            before += w < wv ? x : 0u;
-            total += x;
-        }
-        uint32_t at = carry + before + (incl - mine);
-#pragma unroll
-        for (uint32_t k = 0; k < kKnnScanPerThread; k++) {
-            if (first + k < cells) cell_start[first + k] = at;
-            at += c[k];
-        }
-        carry += total;
-        __syncthreads();  // s_w is rewritten by the next tile
-    }
-    if (threadIdx.x == 0) cell_start[cells] = carry;
+    const uint32_t total = workgroup_scan<uint32_t>(  // (the total is N < 2^31)
+        cells, 0u, [&](uint32_t c, bool) { return cell_count[c]; }, [&](uint32_t c, uint32_t at) { cell_start[c] = at; });
+    if (threadIdx.x == 0) cell_start[cells] = total;
 }
 
 __global__ void __launch_bounds__(kKnnThreads)
@@ -236,7 +142,7 @@ k_knn_fill(const float *__restrict__ points, uint32_t N, const float *__restrict
            const uint32_t *__restrict__ cell_start, uint32_t *__restrict__ cursor, float4_t *__restrict__ sorted) {
     const uint32_t i = blockIdx.x * kKnnThreads + threadIdx.x;
     if (i >= N) return;
-    const KnnGrid g = knn_grid(box, nx, ny, nz);
+    const CellGrid g = cell_grid(box, nx, ny, nz);
     const KnnCell k = knn_point_cell(points, i, g);
     const uint32_t c = (k.c[0] * ny + k.c[1]) * nz + k.c[2];
     const uint32_t slot = cell_start[c] + atomicAdd(&cursor[c], 1u);
@@ -259,7 +165,7 @@ k_knn_search(KnnArgs A) {
     const uint32_t k = A.k, N = A.N;
     KnnBest<K> best;
     best.clear(k);
-    const bool live = (!A.valid || A.valid[qi] != 0) && knn_finite(q[0]) && knn_finite(q[1]) && knn_finite(q[2]);
+    const bool live = (!A.valid || A.valid[qi] != 0) && cell_finite(q[0]) && cell_finite(q[1]) && cell_finite(q[2]);
     if (live) knn_walk<K>(A, q, best);
     double sum = 0.0;
     uint32_t held = 0;
@@ -279,16 +185,9 @@ k_knn_search(KnnArgs A) {
 }
 
 // ------------------------------------------------------------------------------------------------------------ host side
-bool knn_grid_ok(uint32_t nx, uint32_t ny, uint32_t nz) {
-    return nx >= 1 && ny >= 1 && nz >= 1 && nx <= kKnnMaxCellsPerAxis && ny <= kKnnMaxCellsPerAxis && nz <= kKnnMaxCellsPerAxis;
-}
-uint32_t knn_bounds_groups(uint32_t N) {
-    const uint32_t g = div_up(N, kKnnThreads);
-    return g < 1 ? 1 : (g > kKnnBoundsGroupsMax ? kKnnBoundsGroupsMax : g);
-}
 // workspace: the cell counters u32[cells], then the slab extremes u32[2][nx + ny + nz]; the bounds partials overlay them
 uint64_t knn_ws_bytes(uint32_t N, uint32_t nx, uint32_t ny, uint32_t nz) {
-    const uint64_t bounds = 4ull * kKnnBoundsWords * knn_bounds_groups(N);
+    const uint64_t bounds = 4ull * kKnnBoundsWords * cell_bounds_groups(N);
     const uint64_t cells = 4ull * nx * ny * nz + 8ull * ((uint64_t)nx + ny + nz);
     return ((bounds > cells ? bounds : cells) + 15) & ~15ull;
 }
@@ -298,20 +197,8 @@ int knn_check_cloud(const char *who, const float *points, uint32_t N) {
     LNH_REQUIRE(N < (1u << 31), LNH_ERR_UNSUPPORTED, "%s: %u points, indices are int32 (< 2^31)", who, N);
     return LNH_OK;
 }
-int knn_check_grid(const char *who, const float *box, uint32_t nx, uint32_t ny, uint32_t nz) {
-    LNH_REQUIRE(box && ((uintptr_t)box & 3) == 0, LNH_ERR_INVALID_ARG, "%s: null pointer (box)", who);
-    LNH_REQUIRE(nx >= 1 && ny >= 1 && nz >= 1, LNH_ERR_INVALID_ARG, "%s: grid of %u x %u x %u cells, every dimension must be >= 1",
-                who, nx, ny, nz);
-    LNH_REQUIRE(knn_grid_ok(nx, ny, nz), LNH_ERR_UNSUPPORTED, "%s: grid of %u x %u x %u cells, at most %u per axis", who, nx, ny, nz,
-                kKnnMaxCellsPerAxis);
-    return LNH_OK;
-}
 int knn_check_ws(const char *who, uint32_t N, uint32_t nx, uint32_t ny, uint32_t nz, const void *ws, uint64_t ws_bytes) {
-    const uint64_t need = knn_ws_bytes(N, nx, ny, nz);
-    LNH_REQUIRE(ws && ((uintptr_t)ws & 3) == 0 && ws_bytes >= need, LNH_ERR_INVALID_ARG,
-                "%s: workspace of %llu bytes (4-byte aligned) needed, got %llu", who, (unsigned long long)need,
-                (unsigned long long)ws_bytes);
-    return LNH_OK;
+    return cell_check_ws(who, knn_ws_bytes(N, nx, ny, nz), ws, ws_bytes);
 }
 
 template <int K>
@@ -324,7 +211,7 @@ void knn_launch(const KnnArgs &A, hipStream_t s) {
 extern "C" {
 
 uint64_t lnh_knn_workspace_size(uint32_t N, uint32_t nx, uint32_t ny, uint32_t nz) {
-    if (N < 1 || N >= (1u << 31) || !knn_grid_ok(nx, ny, nz)) return 0;
+    if (N < 1 || N >= (1u << 31) || !cell_grid_ok(nx, ny, nz)) return 0;
     return knn_ws_bytes(N, nx, ny, nz);
 }
 
@@ -333,7 +220,7 @@ int lnh_knn_bounds(const float *points, uint32_t N, void *ws, uint64_t ws_bytes,
     if (rc) return rc;
     LNH_REQUIRE(box && ((uintptr_t)box & 3) == 0, LNH_ERR_INVALID_ARG, "knn_bounds: null pointer (box)");
     if ((rc = knn_check_ws("knn_bounds", N, 1, 1, 1, ws, ws_bytes))) return rc;
-    const uint32_t G = knn_bounds_groups(N);
+    const uint32_t G = cell_bounds_groups(N);
     hipStream_t s = (hipStream_t)stream;
     LNH_LAUNCH(k_knn_bounds, dim3(G), dim3(kKnnThreads), 0, s, points, N, (uint32_t *)ws);
     if ((rc = lnh_check_launch("lnh_knn_bounds(partials)"))) return rc;
@@ -345,7 +232,7 @@ int lnh_knn_build_count(const float *points, uint32_t N, const float *box, uint3
                         uint64_t ws_bytes, uint32_t *cell_start, float *slabs, lnh_stream_t stream) {
     int rc = knn_check_cloud("knn_build_count", points, N);
     if (rc) return rc;
-    if ((rc = knn_check_grid("knn_build_count", box, nx, ny, nz))) return rc;
+    if ((rc = cell_check_grid("knn_build_count", box, nx, ny, nz))) return rc;
     LNH_REQUIRE(cell_start && slabs && ((uintptr_t)cell_start & 3) == 0 && ((uintptr_t)slabs & 3) == 0, LNH_ERR_INVALID_ARG,
                 "knn_build_count: null pointer (cell_start / slabs)");
     if ((rc = knn_check_ws("knn_build_count", N, nx, ny, nz, ws, ws_bytes))) return rc;
@@ -357,7 +244,7 @@ int lnh_knn_build_count(const float *points, uint32_t N, const float *box, uint3
     if ((rc = lnh_check_launch("lnh_knn_build_count(preset)"))) return rc;
     LNH_LAUNCH(k_knn_count, dim3(div_up(N, kKnnThreads)), dim3(kKnnThreads), 0, s, points, N, box, nx, ny, nz, cell_count, slab_enc);
     if ((rc = lnh_check_launch("lnh_knn_build_count(count)"))) return rc;
-    LNH_LAUNCH(k_knn_scan, dim3(1), dim3(kKnnScanThreads), 0, s, (const uint32_t *)cell_count, cells, cell_start,
+    LNH_LAUNCH(k_knn_scan, dim3(1), dim3(kScanThreads), 0, s, (const uint32_t *)cell_count, cells, cell_start,
                (const uint32_t *)slab_enc, nx, ny, nz, slabs);
     return lnh_check_launch("lnh_knn_build_count(scan)");
 }
@@ -366,7 +253,7 @@ int lnh_knn_build_fill(const float *points, uint32_t N, const float *box, uint32
                        uint64_t ws_bytes, const uint32_t *cell_start, float *sorted, lnh_stream_t stream) {
     int rc = knn_check_cloud("knn_build_fill", points, N);
     if (rc) return rc;
-    if ((rc = knn_check_grid("knn_build_fill", box, nx, ny, nz))) return rc;
+    if ((rc = cell_check_grid("knn_build_fill", box, nx, ny, nz))) return rc;
     LNH_REQUIRE(cell_start && sorted && ((uintptr_t)cell_start & 3) == 0, LNH_ERR_INVALID_ARG,
                 "knn_build_fill: null pointer (cell_start / sorted)");
     LNH_REQUIRE(((uintptr_t)sorted & 15) == 0, LNH_ERR_INVALID_ARG, "knn_build_fill: sorted must be 16-byte aligned (rows of 16 bytes)");
@@ -383,7 +270,7 @@ int lnh_knn_search(const float *points, uint32_t N, const float *box, uint32_t n
                    uint32_t Q, uint32_t k, const float *values, int32_t *indices, float *dist2, float *mean, lnh_stream_t stream) {
     int rc = knn_check_cloud("knn_search", points, N);
     if (rc) return rc;
-    if ((rc = knn_check_grid("knn_search", box, nx, ny, nz))) return rc;
+    if ((rc = cell_check_grid("knn_search", box, nx, ny, nz))) return rc;
     LNH_REQUIRE(cell_start && sorted && slabs && ((uintptr_t)cell_start & 3) == 0 && ((uintptr_t)slabs & 3) == 0, LNH_ERR_INVALID_ARG,
                 "knn_search: null pointer (cell_start / sorted / slabs)");
     LNH_REQUIRE(((uintptr_t)sorted & 15) == 0, LNH_ERR_INVALID_ARG, "knn_search: sorted must be 16-byte aligned (rows of 16 bytes)");

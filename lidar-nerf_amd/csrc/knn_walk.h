@@ -2,49 +2,13 @@
 // compiles as plain C++: tools/knn_walk_host.cpp runs exactly this code on the host, under the address and undefined-behaviour
 // sanitizers, against a brute-force search.  Nothing here launches anything.
 #pragma once
-#include <stddef.h>
-#include <stdint.h>
+#include "cell_grid.h"
 
-#include <cmath>
-
-#if defined(__HIPCC__)
-#define KNN_HD __host__ __device__ __forceinline__
-#else
-#define KNN_HD inline
-#endif
-
-KNN_HD uint32_t knn_bits(float x) { return __builtin_bit_cast(uint32_t, x); }
-KNN_HD float knn_float(uint32_t b) { return __builtin_bit_cast(float, b); }
-KNN_HD int knn_imin(int a, int b) { return a < b ? a : b; }
-KNN_HD int knn_imax(int a, int b) { return a > b ? a : b; }
-KNN_HD uint32_t knn_umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
-KNN_HD bool knn_finite(float x) { return (knn_bits(x) & 0x7f800000u) != 0x7f800000u; }
-
-struct KnnGrid {
-    float lo[3], inv[3];
-    uint32_t n[3];
-};
-KNN_HD KnnGrid knn_grid(const float *__restrict__ box, uint32_t nx, uint32_t ny, uint32_t nz) {
-    KnnGrid g;
-    g.n[0] = nx, g.n[1] = ny, g.n[2] = nz;
-    float emax = 0.0f;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        g.lo[a] = box[a];
-        emax = fmaxf(emax, box[3 + a] - box[a]);
-    }
-    if (!(emax > 0.0f) || !knn_finite(emax)) emax = 1.0f;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        const float e = fmaxf(box[3 + a] - box[a], emax * 0.0009765625f);
-        g.inv[a] = (float)g.n[a] / e;
-    }
-    return g;
-}
-KNN_HD uint32_t knn_cell_of(float x, float lo, float inv, uint32_t n) {
-    const float c = floorf((x - lo) * inv);
-    return (uint32_t)fminf(fmaxf(c, 0.0f), (float)(n - 1));  // (a NaN becomes cell 0)
-}
+LNH_HD uint32_t knn_bits(float x) { return __builtin_bit_cast(uint32_t, x); }
+LNH_HD float knn_float(uint32_t b) { return __builtin_bit_cast(float, b); }
+LNH_HD int knn_imin(int a, int b) { return a < b ? a : b; }
+LNH_HD int knn_imax(int a, int b) { return a > b ? a : b; }
+LNH_HD uint32_t knn_umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
 
 // The k smallest keys seen, ascending, in registers: every index below is a compile-time constant.  The array has K >= k slots;
 // the first K - k hold 0, smaller than every key (a key carries index + 1), so they never move, the k slots behind them hold the
@@ -52,22 +16,22 @@ KNN_HD uint32_t knn_cell_of(float x, float lo, float inv, uint32_t n) {
 template <int K>
 struct KnnBest {
     unsigned long long key[K];
-    KNN_HD void clear(uint32_t k) {
+    LNH_HD void clear(uint32_t k) {
 #pragma unroll
         for (int j = 0; j < K; j++) key[j] = (uint32_t)j + k < (uint32_t)K ? 0ull : ~0ull;
     }
-    KNN_HD void insert(unsigned long long k) {
+    LNH_HD void insert(unsigned long long k) {
         if (k < key[K - 1]) {
 #pragma unroll
             for (int j = K - 1; j > 0; j--) key[j] = k < key[j - 1] ? key[j - 1] : (k < key[j] ? k : key[j]);
             key[0] = k < key[0] ? k : key[0];
         }
     }
-    KNN_HD unsigned long long kth() const { return key[K - 1]; }
+    LNH_HD unsigned long long kth() const { return key[K - 1]; }
 };
 
 // (bits of d2) << 32 | (index + 1): the order of the contract's key (index < 2^31)
-KNN_HD unsigned long long knn_key(float px, float py, float pz, uint32_t index, const float (&q)[3]) {
+LNH_HD unsigned long long knn_key(float px, float py, float pz, uint32_t index, const float (&q)[3]) {
     const float dx = px - q[0], dy = py - q[1], dz = pz - q[2];
     const float d2 = ((dx * dx) + (dy * dy)) + (dz * dz);
     return (unsigned long long)knn_bits(d2) << 32 | (index + 1u);
@@ -95,7 +59,7 @@ struct KnnArgs {
 
 // the walk of one query with finite coordinates: on return `best` holds the answer
 template <int K>
-KNN_HD void knn_walk(const KnnArgs &A, const float (&q)[3], KnnBest<K> &best) {
+LNH_HD void knn_walk(const KnnArgs &A, const float (&q)[3], KnnBest<K> &best) {
     const float inf = knn_float(0x7f800000u);
     const uint32_t N = A.N;
     const uint32_t nx = A.nx, ny = A.ny, nz = A.nz;
@@ -103,9 +67,9 @@ KNN_HD void knn_walk(const KnnArgs &A, const float (&q)[3], KnnBest<K> &best) {
         for (uint32_t i = 0; i < N; i++)
             best.insert(knn_key(A.points[(size_t)i * 3], A.points[(size_t)i * 3 + 1], A.points[(size_t)i * 3 + 2], i, q));
     } else {
-        const KnnGrid g = knn_grid(A.box, nx, ny, nz);
-        const int cx = (int)knn_cell_of(q[0], g.lo[0], g.inv[0], nx), cy = (int)knn_cell_of(q[1], g.lo[1], g.inv[1], ny),
-                  cz = (int)knn_cell_of(q[2], g.lo[2], g.inv[2], nz);
+        const CellGrid g = cell_grid(A.box, nx, ny, nz);
+        const int cx = (int)cell_of(q[0], g.lo[0], g.inv[0], nx), cy = (int)cell_of(q[1], g.lo[1], g.inv[1], ny),
+                  cz = (int)cell_of(q[2], g.lo[2], g.inv[2], nz);
         const uint32_t S = nx + ny + nz;
         const float *smin_x = A.slabs, *smin_y = A.slabs + nx, *smin_z = A.slabs + nx + ny;
         const float *pmax_x = A.slabs + S, *pmax_y = pmax_x + nx, *pmax_z = pmax_x + nx + ny;

@@ -15,8 +15,8 @@
 // Passes, one thread per lattice point, 256 points per workgroup, no atomics of any kind:
 //   k_mc_count      case of the point's cell, its triangle count, its 0-3 owned crossing edges, non-finite sample -> ONE packed
 //                   word of totals per workgroup
-//   k_mc_scan       ONE workgroup: exclusive scans of the workgroup totals (vertices, triangles) in tiles of kMcScanTile, the
-//                   pattern of k_march_scan / k_fpa_scan; writes counts[4]
+//   k_mc_scan       ONE workgroup: exclusive scans of the workgroup totals (vertices, triangles) side by side with scan.h's
+//                   workgroup_scan; writes counts[4]
 //   k_mc_vertices   case again, scan inside the workgroup -> every point's global vertex offset (workspace) and the vertices
 //   k_mc_triangles  case again, scan inside the workgroup -> the triangles; a corner is the owner's vertex offset + the rank
 //                   of the edge among that owner's crossing edges.  Owners live in other workgroups, hence the launch boundary
@@ -25,6 +25,7 @@
 // G = ceil(N / 256).
 #include "common.h"
 #include "mc_tables.h"
+#include "scan.h"
 
 namespace {
 
@@ -35,7 +36,6 @@ constexpr uint32_t kMcTriShift = 10, kMcBadShift = 21;
 static_assert(3 * kMcThreads < (1u << kMcTriShift), "vertex total of a workgroup must fit its field");
 static_assert(kMcMaxTriangles * kMcThreads < (1u << (kMcBadShift - kMcTriShift)), "per-cell bound against the table's maximum");
 static_assert(kMcMaxTriangles <= 5, "k_mc_triangles writes at most 5 triangles per cell");
-constexpr uint32_t kMcScanThreads = 1024, kMcScanPerThread = 4, kMcScanTile = kMcScanThreads * kMcScanPerThread;
 
 struct McDims {
     uint32_t nx, ny, nz, n;  // n = nx * ny * nz < 2^31
@@ -70,17 +70,6 @@ __device__ __forceinline__ McPoint mc_point(const float *__restrict__ vol, const
     return q;
 }
 
-// exclusive scan over the 256 threads of a workgroup; `total` = the sum.  s_wave: 4 words of LDS.
-__device__ __forceinline__ uint32_t mc_block_scan(uint32_t v, uint32_t *s_wave, uint32_t &total) {
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint32_t incl = wave_scan_add_u32(v);
-    if (lane == 63) s_wave[wv] = incl;
-    __syncthreads();
-    const uint32_t w0 = s_wave[0], w1 = s_wave[1], w2 = s_wave[2], w3 = s_wave[3];
-    total = w0 + w1 + w2 + w3;
-    return incl - v + (wv > 0 ? w0 : 0u) + (wv > 1 ? w1 : 0u) + (wv > 2 ? w2 : 0u);
-}
-
 __global__ void __launch_bounds__(kMcThreads)
 k_mc_count(const float *__restrict__ vol, McDims d, float iso, uint32_t *__restrict__ wg_totals) {
     __shared__ uint32_t s_wave[4];
@@ -93,59 +82,49 @@ k_mc_count(const float *__restrict__ vol, McDims d, float iso, uint32_t *__restr
         packed = nv | nt << kMcTriShift | bad << kMcBadShift;
     }
     uint32_t total;
-    (void)mc_block_scan(packed, s_wave, total);  // (the fields cannot carry into each other: static_asserts above)
+    (void)block_scan_256(packed, s_wave, total);  // (the fields cannot carry into each other: static_asserts above)
     if (threadIdx.x == 0) wg_totals[blockIdx.x] = total;
 }
 
-__global__ void __launch_bounds__(kMcScanThreads)
+// the two sums k_mc_scan forms side by side (vertices, triangles): 32 bits inside a tile of 4096 workgroups of 256 points,
+// 64 bits over the tiles
+struct McSums {
+    uint32_t v, t;
+    __device__ __forceinline__ McSums &operator+=(const McSums &o) { return v += o.v, t += o.t, *this; }
+};
+__device__ __forceinline__ McSums operator+(McSums a, const McSums &b) { return a += b; }
+__device__ __forceinline__ McSums operator-(const McSums &a, const McSums &b) { return {a.v - b.v, a.t - b.t}; }
+__device__ __forceinline__ McSums scan_wave(const McSums &s) { return {::scan_wave(s.v), ::scan_wave(s.t)}; }
+__device__ __forceinline__ McSums scan_lane(const McSums &s, uint32_t lane) { return {::scan_lane(s.v, lane), ::scan_lane(s.t, lane)}; }
+struct McTotals {
+    unsigned long long v, t;
+    __device__ __forceinline__ McTotals &operator+=(const McSums &o) { return v += o.v, t += o.t, *this; }
+};
+__device__ __forceinline__ McTotals operator+(McTotals a, const McSums &b) { return a += b; }
+
+__global__ void __launch_bounds__(kScanThreads)
 k_mc_scan(const uint32_t *__restrict__ wg_totals, uint32_t G, uint32_t *__restrict__ wg_voff, uint32_t *__restrict__ wg_toff,
           uint32_t *__restrict__ counts) {
-    constexpr uint32_t kWaves = kMcScanThreads / 64;
-    __shared__ uint32_t s_v[kWaves], s_t[kWaves], s_b[kWaves];
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    unsigned long long carry_v = 0, carry_t = 0;  // totals of the tiles in front of this one: the same in every thread
-    uint32_t my_bad = 0;
-    for (uint32_t tile = 0; tile < G; tile += kMcScanTile) {
-        const uint32_t first = tile + threadIdx.x * kMcScanPerThread;
-        uint32_t cv[kMcScanPerThread], ct[kMcScanPerThread], mv = 0, mt = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < kMcScanPerThread; k++) {
-            const uint32_t w = first + k < G ? wg_totals[first + k] : 0u;
-            cv[k] = w & ((1u << kMcTriShift) - 1);
-            ct[k] = (w >> kMcTriShift) & ((1u << (kMcBadShift - kMcTriShift)) - 1);
-            my_bad += w >> kMcBadShift;
-            mv += cv[k];
-            mt += ct[k];
-        }
-        const uint32_t iv = wave_scan_add_u32(mv), it = wave_scan_add_u32(mt);
-        if (lane == 63) s_v[wv] = iv, s_t[wv] = it;
-        __syncthreads();
-        const uint32_t wtv = lane < kWaves ? s_v[lane] : 0u, wtt = lane < kWaves ? s_t[lane] : 0u;
-        const uint32_t wiv = wave_scan_add_u32(wtv), wit = wave_scan_add_u32(wtt);
-        const uint32_t off_v = (uint32_t)__shfl((int)(wiv - wtv), (int)wv, 64);
-        const uint32_t off_t = (uint32_t)__shfl((int)(wit - wtt), (int)wv, 64);
-        const uint32_t tot_v = (uint32_t)__shfl((int)wiv, (int)kWaves - 1, 64);
-        const uint32_t tot_t = (uint32_t)__shfl((int)wit, (int)kWaves - 1, 64);
-        uint32_t ov = (uint32_t)carry_v + off_v + (iv - mv), ot = (uint32_t)carry_t + off_t + (it - mt);
-#pragma unroll
-        for (uint32_t k = 0; k < kMcScanPerThread; k++) {
-            if (first + k < G) wg_voff[first + k] = ov, wg_toff[first + k] = ot;
-            ov += cv[k];
-            ot += ct[k];
-        }
-        carry_v += tot_v;
-        carry_t += tot_t;
-        __syncthreads();  // s_v / s_t are rewritten by the next tile
-    }
+    constexpr uint32_t kWaves = kScanThreads / 64;
+    __shared__ uint32_t s_b[kWaves];
+    uint32_t my_bad = 0;  // non-finite samples of the workgroups this thread loads: summed once, behind the scan
+    const McTotals end = workgroup_scan<McTotals, McSums>(
+        G, McTotals{0, 0},
+        [&](uint32_t g, bool live) {
+            const uint32_t w = wg_totals[g];
+            my_bad += live ? w >> kMcBadShift : 0u;
+            return McSums{w & ((1u << kMcTriShift) - 1), (w >> kMcTriShift) & ((1u << (kMcBadShift - kMcTriShift)) - 1)};
+        },
+        [&](uint32_t g, const McTotals &off) { wg_voff[g] = (uint32_t)off.v, wg_toff[g] = (uint32_t)off.t; });
     const uint32_t ib = wave_scan_add_u32(my_bad);
-    if (lane == 63) s_b[wv] = ib;
+    if ((threadIdx.x & 63) == 63) s_b[threadIdx.x >> 6] = ib;
     __syncthreads();
     if (threadIdx.x == 0) {
         uint32_t bad = 0;
         for (uint32_t w = 0; w < kWaves; w++) bad += s_b[w];
         // a count that does not fit 32 bits saturates: the caller refuses it (the offsets above have wrapped)
-        counts[0] = carry_v > 0xffffffffull ? 0xffffffffu : (uint32_t)carry_v;
-        counts[1] = carry_t > 0xffffffffull ? 0xffffffffu : (uint32_t)carry_t;
+        counts[0] = end.v > 0xffffffffull ? 0xffffffffu : (uint32_t)end.v;
+        counts[1] = end.t > 0xffffffffull ? 0xffffffffu : (uint32_t)end.t;
         counts[2] = bad;
         counts[3] = 0u;
     }
@@ -163,7 +142,7 @@ k_mc_vertices(const float *__restrict__ vol, McDims d, float iso, const uint32_t
         nv = (uint32_t)q.cx + q.cy + q.cz;
     }
     uint32_t total;
-    uint32_t k = wg_voff[blockIdx.x] + mc_block_scan(nv, s_wave, total);
+    uint32_t k = wg_voff[blockIdx.x] + block_scan_256(nv, s_wave, total);
     if (p >= d.n) return;
     point_voff[p] = k;
     if (nv == 0) return;
@@ -200,7 +179,7 @@ k_mc_triangles(const float *__restrict__ vol, McDims d, float iso, const uint32_
         nt = q.cell ? kMcTriCount[q.kase] : 0u;
     }
     uint32_t total;
-    const uint32_t first = wg_toff[blockIdx.x] + mc_block_scan(nt, s_wave, total);
+    const uint32_t first = wg_toff[blockIdx.x] + block_scan_256(nt, s_wave, total);
     if (nt == 0) return;  // (nt > 0: the point has a cell, so all 8 corners are distinct lattice points)
     const uint32_t sx = d.ny * d.nz, sy = d.nz;
     for (uint32_t j = 0; j < nt; j++) {
@@ -280,7 +259,7 @@ int lnh_marching_cubes_count(const float *volume, uint32_t nx, uint32_t ny, uint
     hipStream_t s = (hipStream_t)stream;
     LNH_LAUNCH(k_mc_count, dim3(l.groups), dim3(kMcThreads), 0, s, volume, d, iso, totals);
     if ((rc = lnh_check_launch("lnh_marching_cubes_count(count)"))) return rc;
-    LNH_LAUNCH(k_mc_scan, dim3(1), dim3(kMcScanThreads), 0, s, (const uint32_t *)totals, l.groups, voff, toff, counts);
+    LNH_LAUNCH(k_mc_scan, dim3(1), dim3(kScanThreads), 0, s, (const uint32_t *)totals, l.groups, voff, toff, counts);
     return lnh_check_launch("lnh_marching_cubes_count(scan)");
 }
 

@@ -35,52 +35,41 @@
 // for which the error bound of this arithmetic, E = 2^-18 * max(|box|, |o|), is not below delta / 4 (an origin very far
 // away, a mesh very far from zero, absurd magnitudes) takes the list of ALL triangles instead: the answer is the same.
 //
+// The grid itself (box -> cells, cell_of, the bounds passes' reduce) is cell_grid.h, shared with knn.hip; the scan is scan.h.
 // Build passes, none waits for another workgroup: k_rc_bounds (per-workgroup min / max / counts, no atomics), k_rc_bounds_finish
-// (one workgroup), k_rc_count (integer atomics per cell), k_rc_scan (one workgroup, tiles of kRcScanTile), k_rc_fill (an
-// integer cursor per cell: the order inside a cell is arrival order and no output depends on it).
+// (one workgroup), k_rc_count (integer atomics per cell), k_rc_scan (one workgroup, scan.h workgroup_scan in 64 bits), k_rc_fill
+// (an integer cursor per cell: the order inside a cell is arrival order and no output depends on it).
+#include "cell_grid.h"
 #include "common.h"
+#include "scan.h"
 
 namespace {
 
-constexpr uint32_t kRcThreads = 256;
-constexpr uint32_t kRcBoundsGroupsMax = 1024;
-constexpr uint32_t kRcBoundsWords = 12;  // per-workgroup partial: lo[3], hi[3], largest triangle extent[3], bad coords, bad indices, 0
-constexpr uint32_t kRcScanThreads = 1024, kRcScanPerThread = 4, kRcScanTile = kRcScanThreads * kRcScanPerThread;
-constexpr uint32_t kRcMaxCellsPerAxis = 1024;
+constexpr uint32_t kRcThreads = kCellThreads;
+// per-workgroup partial (cell_grid.h): lo[3], hi[3], largest triangle extent[3], bad coords, bad indices, 0
+constexpr uint32_t kRcBoundsWords = 12;
 constexpr uint32_t kRcCastThreads = 128;
 constexpr float kRcDilate = 0.0625f;                 // delta = w / 16
 constexpr float kRcErrScale = 3.814697265625e-06f;   // 2^-18 = 64 ulp-fractions of fp32: E = this * magnitude
 constexpr float kRcBig = 1.152921504606846976e18f, kRcSmall = 8.67361737988403547e-19f;  // 2^60, 2^-60
 
 __device__ __forceinline__ float sel3(float a, float b, float c, uint32_t k) { return k == 0 ? a : (k == 1 ? b : c); }
-__device__ __forceinline__ bool rc_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 
-struct RcGrid {
-    float lo[3], hi[3], w[3], inv[3], delta[3], maxext[3];
-    uint32_t n[3];
+// the cells (cell_grid.h) and what the cast needs besides: the box's far corner, the cell width w = e / n from the same floored
+// extent e as inv = n / e, the dilation delta = w / 16, the largest triangle extent per axis
+struct RcGrid : CellGrid {
+    float hi[3], w[3], delta[3], maxext[3];
 };
 __device__ __forceinline__ RcGrid rc_grid(const float *__restrict__ box, uint32_t nx, uint32_t ny, uint32_t nz) {
     RcGrid g;
-    g.n[0] = nx, g.n[1] = ny, g.n[2] = nz;
-    float emax = 0.0f;
+    const uint32_t n[3] = {nx, ny, nz};
 #pragma unroll
-    for (int a = 0; a < 3; a++) {
-        g.lo[a] = box[a], g.hi[a] = box[3 + a], g.maxext[a] = box[6 + a];
-        emax = fmaxf(emax, g.hi[a] - g.lo[a]);
-    }
-    if (!(emax > 0.0f) || !rc_finite(emax)) emax = 1.0f;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        const float e = fmaxf(g.hi[a] - g.lo[a], emax * 0.0009765625f);
-        g.w[a] = e / (float)g.n[a];
-        g.inv[a] = (float)g.n[a] / e;
+    for (int a = 0; a < 3; a++) g.hi[a] = box[3 + a], g.maxext[a] = box[6 + a];
+    static_cast<CellGrid &>(g) = cell_grid(box, nx, ny, nz, [&](int a, float e) {
+        g.w[a] = e / (float)n[a];
         g.delta[a] = g.w[a] * kRcDilate;
-    }
+    });
     return g;
-}
-__device__ __forceinline__ uint32_t rc_cell_of(float x, float lo, float inv, uint32_t n) {
-    const float c = floorf((x - lo) * inv);
-    return (uint32_t)fminf(fmaxf(c, 0.0f), (float)(n - 1));  // (a NaN becomes cell 0)
 }
 
 // ------------------------------------------------------------------------------------------------------- intersection
@@ -131,7 +120,7 @@ __device__ __forceinline__ bool rc_intersect_sheared(const float (&o)[3], const 
     if (det == 0.0f) return false;
     const float Az = s.Sz * Akz, Bz = s.Sz * Bkz, Cz = s.Sz * Ckz;
     float t = ((U * Az + V * Bz) + W * Cz) / det;
-    if (!(t >= 0.0f) || !rc_finite(t)) return false;  // (a NaN fails t >= 0)
+    if (!(t >= 0.0f) || !cell_finite(t)) return false;  // (a NaN fails t >= 0)
     if (t == 0.0f) t = 0.0f;                            // -0 -> +0: the key orders by the bits
     t_out = t;
     return true;
@@ -161,101 +150,38 @@ __device__ __forceinline__ void rc_test(const RcMesh &m, uint32_t tri, const flo
 }
 
 // --------------------------------------------------------------------------------------------------------------- bounds
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_add(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
-    return v;
-}
-// min / max / sums of 9 + 2 values over the 256 threads; thread 0 writes the 12 words of the partial
-__device__ __forceinline__ void rc_block_reduce(float (&lo)[3], float (&hi)[3], float (&ext)[3], uint32_t bad_c, uint32_t bad_i,
-                                                uint32_t *__restrict__ out) {
-    __shared__ float s_f[4][9];
-    __shared__ uint32_t s_u[4][2];
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int a = 0; a < 3; a++) lo[a] = wave_min(lo[a]), hi[a] = wave_max(hi[a]), ext[a] = wave_max(ext[a]);
-    bad_c = wave_add(bad_c), bad_i = wave_add(bad_i);
-    if (lane == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; a++) s_f[wv][a] = lo[a], s_f[wv][3 + a] = hi[a], s_f[wv][6 + a] = ext[a];
-        s_u[wv][0] = bad_c, s_u[wv][1] = bad_i;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int a = 0; a < 9; a++) {
-            float v = s_f[0][a];
-            for (int w = 1; w < 4; w++) v = a < 3 ? fminf(v, s_f[w][a]) : fmaxf(v, s_f[w][a]);
-            out[a] = __float_as_uint(v);
-        }
-        out[9] = s_u[0][0] + s_u[1][0] + s_u[2][0] + s_u[3][0];
-        out[10] = s_u[0][1] + s_u[1][1] + s_u[2][1] + s_u[3][1];
-        out[11] = 0u;
-    }
-}
-
 __global__ void __launch_bounds__(kRcThreads)
 k_rc_bounds(RcMesh m, uint32_t *__restrict__ partials) {
     const float inf = __uint_as_float(0x7f800000u);
-    float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf}, ext[3] = {0.0f, 0.0f, 0.0f};
-    uint32_t bad_c = 0, bad_i = 0;
-    const uint32_t stride = gridDim.x * kRcThreads, first = blockIdx.x * kRcThreads + threadIdx.x;
-    for (uint32_t v = first; v < m.V; v += stride) {  // (v + stride < 2^32: V < 2^31 and stride <= 2^18)
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            const float x = m.vertices[(size_t)v * 3 + a];
-            if (rc_finite(x))
-                lo[a] = fminf(lo[a], x), hi[a] = fmaxf(hi[a], x);
-            else
-                bad_c++;
-        }
-    }
-    for (uint32_t t = first; t < m.T; t += stride) {
+    float f[9] = {inf, inf, inf, -inf, -inf, -inf, 0.0f, 0.0f, 0.0f};  // lo, hi, largest triangle extent
+    uint32_t bad[2] = {0, 0};                                           // coordinates, indices
+    cell_bounds_accumulate(m.vertices, m.V, f, f + 3, bad[0]);
+    const uint32_t stride = gridDim.x * kRcThreads;
+    for (uint32_t t = blockIdx.x * kRcThreads + threadIdx.x; t < m.T; t += stride) {  // (t + stride < 2^32: T < 2^31, stride <= 2^18)
         const int32_t *ix = m.triangles + (size_t)t * 3;
         const uint32_t i0 = (uint32_t)ix[0], i1 = (uint32_t)ix[1], i2 = (uint32_t)ix[2];
-        const uint32_t bad = (i0 >= m.V) + (i1 >= m.V) + (i2 >= m.V);  // (a negative index is a large unsigned one)
-        bad_i += bad;
-        if (bad == 0) {
+        const uint32_t out = (i0 >= m.V) + (i1 >= m.V) + (i2 >= m.V);  // (a negative index is a large unsigned one)
+        bad[1] += out;
+        if (out == 0) {
 #pragma unroll
             for (int a = 0; a < 3; a++) {
                 const float x0 = m.vertices[(size_t)i0 * 3 + a], x1 = m.vertices[(size_t)i1 * 3 + a],
                             x2 = m.vertices[(size_t)i2 * 3 + a];
-                ext[a] = fmaxf(ext[a], fmaxf(fmaxf(x0, x1), x2) - fminf(fminf(x0, x1), x2));  // (fmaxf drops a NaN)
+                f[6 + a] = fmaxf(f[6 + a], fmaxf(fmaxf(x0, x1), x2) - fminf(fminf(x0, x1), x2));  // (fmaxf drops a NaN)
             }
         }
     }
-    rc_block_reduce(lo, hi, ext, bad_c, bad_i, partials + (size_t)blockIdx.x * kRcBoundsWords);
+    cell_block_reduce(f, bad, partials + (size_t)blockIdx.x * kRcBoundsWords);
 }
 
 __global__ void __launch_bounds__(kRcThreads)
 k_rc_bounds_finish(const uint32_t *__restrict__ partials, uint32_t G, float *__restrict__ box, uint32_t *__restrict__ counts) {
     const float inf = __uint_as_float(0x7f800000u);
-    float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf}, ext[3] = {0.0f, 0.0f, 0.0f};
-    uint32_t bad_c = 0, bad_i = 0;
-    for (uint32_t g = threadIdx.x; g < G; g += kRcThreads) {
-        const uint32_t *p = partials + (size_t)g * kRcBoundsWords;
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            lo[a] = fminf(lo[a], __uint_as_float(p[a]));
-            hi[a] = fmaxf(hi[a], __uint_as_float(p[3 + a]));
-            ext[a] = fmaxf(ext[a], __uint_as_float(p[6 + a]));
-        }
-        // a count that does not fit 32 bits saturates
-        bad_c = bad_c + p[9] < bad_c ? 0xffffffffu : bad_c + p[9];
-        bad_i = bad_i + p[10] < bad_i ? 0xffffffffu : bad_i + p[10];
-    }
+    float f[9] = {inf, inf, inf, -inf, -inf, -inf, 0.0f, 0.0f, 0.0f};
+    uint32_t bad[2] = {0, 0};
+    cell_merge_partials(partials, G, f, bad);
     __shared__ uint32_t s_out[kRcBoundsWords];
-    rc_block_reduce(lo, hi, ext, min(bad_c, 0xffffffu), min(bad_i, 0xffffffu), s_out);  // (256 * 2^24 fits; nonzero stays nonzero)
+    cell_block_reduce(f, bad, s_out);
     __syncthreads();
     if (threadIdx.x < 9) box[threadIdx.x] = __uint_as_float(s_out[threadIdx.x]);
     if (threadIdx.x == 0) counts[0] = s_out[9], counts[1] = s_out[10], counts[2] = 0u, counts[3] = 0u;
@@ -272,8 +198,8 @@ __device__ __forceinline__ RcRange rc_triangle_cells(const RcMesh &m, const RcGr
 #pragma unroll
     for (int a = 0; a < 3; a++) {
         const float x0 = m.vertices[(size_t)i0 * 3 + a], x1 = m.vertices[(size_t)i1 * 3 + a], x2 = m.vertices[(size_t)i2 * 3 + a];
-        r.c0[a] = rc_cell_of(fminf(fminf(x0, x1), x2) - g.delta[a], g.lo[a], g.inv[a], g.n[a]);
-        r.c1[a] = rc_cell_of(fmaxf(fmaxf(x0, x1), x2) + g.delta[a], g.lo[a], g.inv[a], g.n[a]);
+        r.c0[a] = cell_of(fminf(fminf(x0, x1), x2) - g.delta[a], g.lo[a], g.inv[a], g.n[a]);
+        r.c1[a] = cell_of(fmaxf(fmaxf(x0, x1), x2) + g.delta[a], g.lo[a], g.inv[a], g.n[a]);
         if (r.c1[a] < r.c0[a]) r.c1[a] = r.c0[a];  // (cannot happen for finite vertices: cell_of is monotone)
     }
     return r;
@@ -291,49 +217,15 @@ k_rc_count(RcMesh m, const float *__restrict__ box, uint32_t nx, uint32_t ny, ui
 }
 
 // exclusive scan of cell_count[cells] -> cell_start[cells + 1] (32 bits, wrapping), the 64-bit total -> counts[2], counts[3]
-__global__ void __launch_bounds__(kRcScanThreads)
+__global__ void __launch_bounds__(kScanThreads)
 k_rc_scan(const uint32_t *__restrict__ cell_count, uint32_t cells, uint32_t *__restrict__ cell_start, uint32_t *__restrict__ counts) {
-    constexpr uint32_t kWaves = kRcScanThreads / 64;
-    __shared__ unsigned long long s_w[kWaves];
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    unsigned long long carry = 0;  // total of the tiles in front of this one: the same in every thread
-    for (uint32_t tile = 0; tile < cells; tile += kRcScanTile) {
-        const uint32_t first = tile + threadIdx.x * kRcScanPerThread;
-        uint32_t c[kRcScanPerThread];
-        unsigned long long mine = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < kRcScanPerThread; k++) {
-            c[k] = first + k < cells ? cell_count[first + k] : 0u;
-            mine += c[k];
-        }
-        // inclusive scan across the wave, 64 bits
-        unsigned long long incl = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long up = __shfl_up(incl, o, 64);
-            if ((int)lane >= o) incl += up;
-        }
-        if (lane == 63) s_w[wv] = incl;
-        __syncthreads();
-        unsigned long long before = 0, total = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < kWaves; w++) {
-            const unsigned long long x = s_w[w];
-            before += w < wv ? x : 0ull;
-            total += x;
-        }
-        unsigned long long at = carry + before + (incl - mine);
-#pragma unroll
-        for (uint32_t k = 0; k < kRcScanPerThread; k++) {
-            if (first + k < cells) cell_start[first + k] = (uint32_t)at;
-            at += c[k];
-        }
-        carry += total;
-        __syncthreads();  // s_w is rewritten by the next tile
-    }
+    // 64 bits from the sum of a thread's cells to the total: a single tile of cells can list more than 2^32 entries
+    const unsigned long long total = workgroup_scan<unsigned long long>(
+        cells, 0ull, [&](uint32_t c, bool) { return cell_count[c]; },
+        [&](uint32_t c, unsigned long long at) { cell_start[c] = (uint32_t)at; });
     if (threadIdx.x == 0) {
-        cell_start[cells] = (uint32_t)carry;
-        counts[2] = (uint32_t)carry, counts[3] = (uint32_t)(carry >> 32);
+        cell_start[cells] = (uint32_t)total;
+        counts[2] = (uint32_t)total, counts[3] = (uint32_t)(total >> 32);
     }
 }
 
@@ -365,8 +257,8 @@ k_rc_cast(RcMesh m, const float *__restrict__ box, uint32_t nx, uint32_t ny, uin
     const float o[3] = {rays_o[(size_t)ray * 3], rays_o[(size_t)ray * 3 + 1], rays_o[(size_t)ray * 3 + 2]};
     const float d[3] = {rays_d[(size_t)ray * 3], rays_d[(size_t)ray * 3 + 1], rays_d[(size_t)ray * 3 + 2]};
     unsigned long long best = ~0ull;
-    const bool valid = rc_finite(o[0]) && rc_finite(o[1]) && rc_finite(o[2]) && rc_finite(d[0]) && rc_finite(d[1]) &&
-                       rc_finite(d[2]) && (d[0] != 0.0f || d[1] != 0.0f || d[2] != 0.0f);
+    const bool valid = cell_finite(o[0]) && cell_finite(o[1]) && cell_finite(o[2]) && cell_finite(d[0]) && cell_finite(d[1]) &&
+                       cell_finite(d[2]) && (d[0] != 0.0f || d[1] != 0.0f || d[2] != 0.0f);
     if (valid) {
         const RcShear s = rc_shear(d[0], d[1], d[2]);
         const RcGrid g = rc_grid(box, nx, ny, nz);
@@ -409,7 +301,7 @@ k_rc_cast(RcMesh m, const float *__restrict__ box, uint32_t nx, uint32_t ny, uin
 #pragma unroll
                 for (int a = 0; a < 3; a++) {
                     const float p = d[a] != 0.0f ? o[a] + ts * d[a] : o[a];
-                    ic[a] = rc_cell_of(p, g.lo[a], g.inv[a], g.n[a]);
+                    ic[a] = cell_of(p, g.lo[a], g.inv[a], g.n[a]);
                 }
                 // parameter at which the ray crosses the far plane of cell k along axis a; the outermost planes are the
                 // dilated box's, so the boundary cells own the shell around the box
@@ -456,7 +348,7 @@ k_rc_cast(RcMesh m, const float *__restrict__ box, uint32_t nx, uint32_t ny, uin
         const float e2x = c[0] - a[0], e2y = c[1] - a[1], e2z = c[2] - a[2];
         const float cx = e1y * e2z - e1z * e2y, cy = e1z * e2x - e1x * e2z, cz = e1x * e2y - e1y * e2x;
         const float len = sqrtf((cx * cx + cy * cy) + cz * cz);
-        if (len > 0.0f && rc_finite(len)) {
+        if (len > 0.0f && cell_finite(len)) {
             n0 = cx / len, n1 = cy / len, n2 = cz / len;
             inc = fabsf((d[0] * n0 + d[1] * n1) + d[2] * n2);
         }
@@ -468,13 +360,7 @@ k_rc_cast(RcMesh m, const float *__restrict__ box, uint32_t nx, uint32_t ny, uin
 }
 
 // ------------------------------------------------------------------------------------------------------------ host side
-bool rc_grid_ok(uint32_t nx, uint32_t ny, uint32_t nz) {
-    return nx >= 1 && ny >= 1 && nz >= 1 && nx <= kRcMaxCellsPerAxis && ny <= kRcMaxCellsPerAxis && nz <= kRcMaxCellsPerAxis;
-}
-uint32_t rc_bounds_groups(uint32_t V, uint32_t T) {
-    const uint32_t g = div_up(V > T ? V : T, kRcThreads);
-    return g < 1 ? 1 : (g > kRcBoundsGroupsMax ? kRcBoundsGroupsMax : g);
-}
+uint32_t rc_bounds_groups(uint32_t V, uint32_t T) { return cell_bounds_groups(V > T ? V : T); }
 uint64_t rc_ws_bytes(uint32_t V, uint32_t T, uint32_t nx, uint32_t ny, uint32_t nz) {
     const uint64_t bounds = 4ull * kRcBoundsWords * rc_bounds_groups(V, T), cells = 4ull * nx * ny * nz;
     return ((bounds > cells ? bounds : cells) + 15) & ~15ull;
@@ -486,20 +372,8 @@ int rc_check_mesh(const char *who, const float *vertices, uint32_t V, const int3
                 who, V, T);
     return LNH_OK;
 }
-int rc_check_grid(const char *who, const float *box, uint32_t nx, uint32_t ny, uint32_t nz) {
-    LNH_REQUIRE(box && ((uintptr_t)box & 3) == 0, LNH_ERR_INVALID_ARG, "%s: null pointer (box)", who);
-    LNH_REQUIRE(nx >= 1 && ny >= 1 && nz >= 1, LNH_ERR_INVALID_ARG, "%s: grid of %u x %u x %u cells, every dimension must be >= 1",
-                who, nx, ny, nz);
-    LNH_REQUIRE(rc_grid_ok(nx, ny, nz), LNH_ERR_UNSUPPORTED, "%s: grid of %u x %u x %u cells, at most %u per axis", who, nx, ny, nz,
-                kRcMaxCellsPerAxis);
-    return LNH_OK;
-}
 int rc_check_ws(const char *who, uint32_t V, uint32_t T, uint32_t nx, uint32_t ny, uint32_t nz, const void *ws, uint64_t ws_bytes) {
-    const uint64_t need = rc_ws_bytes(V, T, nx, ny, nz);
-    LNH_REQUIRE(ws && ((uintptr_t)ws & 3) == 0 && ws_bytes >= need, LNH_ERR_INVALID_ARG,
-                "%s: workspace of %llu bytes (4-byte aligned) needed, got %llu", who, (unsigned long long)need,
-                (unsigned long long)ws_bytes);
-    return LNH_OK;
+    return cell_check_ws(who, rc_ws_bytes(V, T, nx, ny, nz), ws, ws_bytes);
 }
 
 }  // namespace
@@ -507,7 +381,7 @@ int rc_check_ws(const char *who, uint32_t V, uint32_t T, uint32_t nx, uint32_t n
 extern "C" {
 
 uint64_t lnh_raycast_workspace_size(uint32_t V, uint32_t T, uint32_t nx, uint32_t ny, uint32_t nz, uint64_t entries) {
-    if (V < 1 || T < 1 || V >= (1u << 31) || T >= (1u << 31) || !rc_grid_ok(nx, ny, nz) || entries > 0x7fffffffull) return 0;
+    if (V < 1 || T < 1 || V >= (1u << 31) || T >= (1u << 31) || !cell_grid_ok(nx, ny, nz) || entries > 0x7fffffffull) return 0;
     return rc_ws_bytes(V, T, nx, ny, nz);
 }
 
@@ -532,7 +406,7 @@ int lnh_raycast_build_count(const float *vertices, uint32_t V, const int32_t *tr
                             uint32_t *counts, lnh_stream_t stream) {
     int rc = rc_check_mesh("raycast_build_count", vertices, V, triangles, T);
     if (rc) return rc;
-    if ((rc = rc_check_grid("raycast_build_count", box, nx, ny, nz))) return rc;
+    if ((rc = cell_check_grid("raycast_build_count", box, nx, ny, nz))) return rc;
     LNH_REQUIRE(cell_start && counts && ((uintptr_t)cell_start & 3) == 0 && ((uintptr_t)counts & 3) == 0, LNH_ERR_INVALID_ARG,
                 "raycast_build_count: null pointer (cell_start / counts)");
     if ((rc = rc_check_ws("raycast_build_count", V, T, nx, ny, nz, ws, ws_bytes))) return rc;
@@ -542,7 +416,7 @@ int lnh_raycast_build_count(const float *vertices, uint32_t V, const int32_t *tr
     if ((rc = lnh_zero_async(ws, 4ull * cells, s, "lnh_raycast_build_count(clear)"))) return rc;
     LNH_LAUNCH(k_rc_count, dim3(div_up(T, kRcThreads)), dim3(kRcThreads), 0, s, m, box, nx, ny, nz, (uint32_t *)ws);
     if ((rc = lnh_check_launch("lnh_raycast_build_count(count)"))) return rc;
-    LNH_LAUNCH(k_rc_scan, dim3(1), dim3(kRcScanThreads), 0, s, (const uint32_t *)ws, cells, cell_start, counts);
+    LNH_LAUNCH(k_rc_scan, dim3(1), dim3(kScanThreads), 0, s, (const uint32_t *)ws, cells, cell_start, counts);
     return lnh_check_launch("lnh_raycast_build_count(scan)");
 }
 
@@ -551,7 +425,7 @@ int lnh_raycast_build_fill(const float *vertices, uint32_t V, const int32_t *tri
                            uint32_t *cell_tris, uint64_t entries, lnh_stream_t stream) {
     int rc = rc_check_mesh("raycast_build_fill", vertices, V, triangles, T);
     if (rc) return rc;
-    if ((rc = rc_check_grid("raycast_build_fill", box, nx, ny, nz))) return rc;
+    if ((rc = cell_check_grid("raycast_build_fill", box, nx, ny, nz))) return rc;
     LNH_REQUIRE(cell_start && cell_tris && ((uintptr_t)cell_start & 3) == 0 && ((uintptr_t)cell_tris & 3) == 0, LNH_ERR_INVALID_ARG,
                 "raycast_build_fill: null pointer (cell_start / cell_tris)");
     LNH_REQUIRE(entries >= 1, LNH_ERR_INVALID_ARG, "raycast_build_fill: %llu entries: every triangle is listed at least once",
@@ -573,7 +447,7 @@ int lnh_raycast_cast(const float *vertices, uint32_t V, const int32_t *triangles
                      float *primitive_normals, float *incidences, lnh_stream_t stream) {
     int rc = rc_check_mesh("raycast_cast", vertices, V, triangles, T);
     if (rc) return rc;
-    if ((rc = rc_check_grid("raycast_cast", box, nx, ny, nz))) return rc;
+    if ((rc = cell_check_grid("raycast_cast", box, nx, ny, nz))) return rc;
     LNH_REQUIRE(cell_start && cell_tris && ((uintptr_t)cell_start & 3) == 0 && ((uintptr_t)cell_tris & 3) == 0, LNH_ERR_INVALID_ARG,
                 "raycast_cast: null pointer (cell_start / cell_tris)");
     LNH_REQUIRE(entries >= 1, LNH_ERR_INVALID_ARG, "raycast_cast: %llu entries: the scene was not built",

@@ -7,6 +7,7 @@
 // counts, (id, offset, count) ray table) are bit-identical to the CPU oracle.
 #include "common.h"
 #include "march_cell.h"
+#include "scan.h"
 
 namespace {
 
@@ -351,7 +352,7 @@ k_march_rays_train(const float *__restrict__ rays_o, const float *__restrict__ r
 // no flag, no ticket), and the only sums are integer ones.  The layout is the serial oracle's, and with it the set of rays a
 // full sample buffer drops is a function of the inputs alone.
 //   k_march_count  one wave per ray, pass 1 of the walk: rays[n] = (n, -, count_n)
-//   k_march_scan   ONE workgroup, exclusive scan of the counts in tiles of kScanTile rays: rays[n][1], counter += (sum, N)
+//   k_march_scan   ONE workgroup, exclusive scan of the counts (scan.h workgroup_scan): rays[n][1], counter += (sum, N)
 //   k_march_write  one wave per ray, pass 2 of the walk at the scanned offset
 __global__ void __launch_bounds__(64 * kMarchRaysPerGroup)
 k_march_count(const float *__restrict__ rays_o, const float *__restrict__ rays_d, const uint8_t *__restrict__ grid,
@@ -369,41 +370,14 @@ k_march_count(const float *__restrict__ rays_o, const float *__restrict__ rays_d
     }
 }
 
-constexpr uint32_t kScanThreads = 1024, kScanPerThread = 4, kScanTile = kScanThreads * kScanPerThread;
 __global__ void __launch_bounds__(kScanThreads)
 k_march_scan(int32_t *__restrict__ rays, int32_t *__restrict__ counter, uint32_t N) {
-    constexpr uint32_t kWaves = kScanThreads / 64;
-    __shared__ uint32_t s_wave[kWaves];
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint32_t base0 = (uint32_t)counter[0];  // (zeroed by the caller, like the arrival-order marcher's)
-    uint32_t carry = 0;                           // counts of the tiles in front of this one: the same in every thread
-    for (uint32_t tile = 0; tile < N; tile += kScanTile) {
-        const uint32_t first = tile + threadIdx.x * kScanPerThread;  // kScanPerThread consecutive rays per thread
-        uint32_t c[kScanPerThread], mine = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < kScanPerThread; k++) {
-            c[k] = first + k < N ? (uint32_t)rays[(size_t)(first + k) * 3 + 2] : 0u;
-            mine += c[k];
-        }
-        const uint32_t incl = wave_scan_add_u32(mine);
-        if (lane == 63) s_wave[wv] = incl;
-        __syncthreads();
-        // every wave scans the kWaves wave totals itself: its own exclusive prefix and the tile's total
-        const uint32_t wt = lane < kWaves ? s_wave[lane] : 0u;
-        const uint32_t wincl = wave_scan_add_u32(wt);
-        const uint32_t wave_off = (uint32_t)__shfl((int)(wincl - wt), (int)wv, 64);
-        const uint32_t tile_total = (uint32_t)__shfl((int)wincl, (int)kWaves - 1, 64);
-        uint32_t off = base0 + carry + wave_off + (incl - mine);
-#pragma unroll
-        for (uint32_t k = 0; k < kScanPerThread; k++) {
-            if (first + k < N) rays[(size_t)(first + k) * 3 + 1] = (int32_t)off;
-            off += c[k];
-        }
-        carry += tile_total;
-        __syncthreads();  // s_wave is rewritten by the next tile
-    }
+    const uint32_t end = workgroup_scan<uint32_t>(
+        N, base0, [&](uint32_t n, bool) { return (uint32_t)rays[(size_t)n * 3 + 2]; },
+        [&](uint32_t n, uint32_t off) { rays[(size_t)n * 3 + 1] = (int32_t)off; });
     if (threadIdx.x == 0) {
-        counter[0] = (int32_t)(base0 + carry);
+        counter[0] = (int32_t)end;
         counter[1] += (int32_t)N;
     }
 }

@@ -9,10 +9,9 @@ import numpy as np
 import torch
 
 from . import _hip
-from .raycast import _device
+from ._cellgrid import MAX_CELLS_PER_AXIS, cubic_cells, device as _device, grid_triple
 
 _SYMBOLS = ("lnh_knn_workspace_size", "lnh_knn_bounds", "lnh_knn_build_count", "lnh_knn_build_fill", "lnh_knn_search")
-MAX_CELLS_PER_AXIS = 1024  # kKnnMaxCellsPerAxis
 MAX_K = 16                 # kKnnMaxK
 # the default grid (tools/bench_knn.py sweeps it, profiles/knn_bench.txt): points per cell, cubic cells.  A finer grid costs
 # 4 bytes per cell next to the 28 bytes per point of the cloud and its sorted copy.
@@ -23,31 +22,8 @@ def default_grid_resolution(n_points, box):
     """The rule behind grid_resolution=None: about DEFAULT_POINTS_PER_CELL points per cell, cubic cells as far as the limit of
     1 ... 1024 cells per axis allows; an axis without extent gets the kernel's floored width (largest extent / 1024).  A speed
     choice, not a contract: every grid gives the same answer.  box: the six numbers lo[3], hi[3]."""
-    lo, hi = np.asarray(box[:3], np.float64), np.asarray(box[3:6], np.float64)
-    ext = hi - lo
-    emax = float(ext.max()) if float(ext.max()) > 0 else 1.0
-    ext = np.maximum(ext, emax / 1024.0)  # (the kernel's floor for a flat axis)
-    cells = max(1.0, float(n_points) / DEFAULT_POINTS_PER_CELL)
-    side = (float(np.prod(ext)) / cells) ** (1.0 / 3.0)
+    _, _, ext, side = cubic_cells(box, float(n_points) / DEFAULT_POINTS_PER_CELL)
     return tuple(max(1, min(int(round(ext[a] / side)), MAX_CELLS_PER_AXIS)) for a in range(3))
-
-
-def _grid_triple(grid_resolution):
-    is_int = lambda x: isinstance(x, (int, np.integer)) and not isinstance(x, bool)
-    g = grid_resolution
-    if is_int(g):
-        g = (g,) * 3
-    else:
-        try:
-            g = tuple(g)
-        except TypeError:
-            g = ()
-    if len(g) != 3 or not all(is_int(x) for x in g):
-        raise ValueError(f"PointCloudIndex: grid_resolution must be None, an int or three ints, got {grid_resolution!r}")
-    g = tuple(int(x) for x in g)
-    if any(x < 1 or x > MAX_CELLS_PER_AXIS for x in g):
-        raise ValueError(f"PointCloudIndex: grid_resolution {g}: 1 ... {MAX_CELLS_PER_AXIS} cells per axis")
-    return g
 
 
 def _cloud(points):
@@ -102,7 +78,7 @@ class PointCloudIndex:
 
     def __init__(self, points, grid_resolution=None):
         p = _cloud(points)
-        grid = None if grid_resolution is None else _grid_triple(grid_resolution)
+        grid = None if grid_resolution is None else grid_triple(grid_resolution, "PointCloudIndex")
         dev = p.device if p.is_cuda else _device()
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("PointCloudIndex: not while a stream is capturing (the build reads the box back)")

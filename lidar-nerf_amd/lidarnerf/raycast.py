@@ -12,10 +12,10 @@ import numpy as np
 import torch
 
 from . import _hip
+from ._cellgrid import MAX_CELLS_PER_AXIS, cubic_cells, device as _device, grid_triple
 
 _SYMBOLS = ("lnh_raycast_workspace_size", "lnh_raycast_bounds", "lnh_raycast_build_count", "lnh_raycast_build_fill",
             "lnh_raycast_cast")
-MAX_CELLS_PER_AXIS = 1024  # kRcMaxCellsPerAxis
 MAX_ENTRIES = (1 << 31) - 1
 # the default grid (tools/bench_raycast.py chose it, profiles/raycast_bench.txt): cells per triangle, spread over the axes in
 # the proportions of the box
@@ -27,12 +27,7 @@ def default_grid_resolution(n_triangles, box):
     limits allow — 1 ... 1024 cells per axis, and a cell no finer than the walk's arithmetic resolves at the distance of the box
     from zero (n <= extent * 2^11 / largest |coordinate|; the kernel falls back to all triangles for a ray it cannot walk, a
     finer grid would only make every ray do so).  box: the six numbers lo[3], hi[3]."""
-    lo, hi = np.asarray(box[:3], np.float64), np.asarray(box[3:6], np.float64)
-    ext = hi - lo
-    emax = float(ext.max()) if float(ext.max()) > 0 else 1.0
-    ext = np.maximum(ext, emax / 1024.0)  # (the kernel's floor for a flat axis)
-    cells = max(1.0, DEFAULT_CELLS_PER_TRIANGLE * float(n_triangles))
-    side = (float(np.prod(ext)) / cells) ** (1.0 / 3.0)
+    lo, hi, ext, side = cubic_cells(box, DEFAULT_CELLS_PER_TRIANGLE * float(n_triangles))
     mag = max(float(np.abs(lo).max()), float(np.abs(hi).max()), 1e-30)
     out = []
     for a in range(3):
@@ -40,30 +35,6 @@ def default_grid_resolution(n_triangles, box):
         n = min(n, int(ext[a] * 2048.0 / mag), MAX_CELLS_PER_AXIS)
         out.append(max(n, 1))
     return tuple(out)
-
-
-def _grid_triple(grid_resolution):
-    is_int = lambda x: isinstance(x, (int, np.integer)) and not isinstance(x, bool)
-    g = grid_resolution
-    if is_int(g):
-        g = (g,) * 3
-    else:
-        try:
-            g = tuple(g)
-        except TypeError:
-            g = ()
-    if len(g) != 3 or not all(is_int(x) for x in g):
-        raise ValueError(f"RaycastingScene: grid_resolution must be None, an int or three ints, got {grid_resolution!r}")
-    g = tuple(int(x) for x in g)
-    if any(x < 1 or x > MAX_CELLS_PER_AXIS for x in g):
-        raise ValueError(f"RaycastingScene: grid_resolution {g}: 1 ... {MAX_CELLS_PER_AXIS} cells per axis")
-    return g
-
-
-def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("lidarnerf.raycast: the scene lives on the GPU and none is available (no CPU fallback)")
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 def _mesh_arrays(vertices, triangles):
@@ -113,7 +84,7 @@ class RaycastingScene:
 
     def __init__(self, vertices, triangles, grid_resolution=None):
         v, t = _mesh_arrays(vertices, triangles)
-        grid = None if grid_resolution is None else _grid_triple(grid_resolution)
+        grid = None if grid_resolution is None else grid_triple(grid_resolution, "RaycastingScene")
         dev = v.device if v.is_cuda else (t.device if t.is_cuda else _device())
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("RaycastingScene: not while a stream is capturing (the build reads counts back)")

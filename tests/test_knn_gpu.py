@@ -22,13 +22,16 @@ KS = (1, 5, 9, 16)
 QUERY_COUNTS = (1, 63, 64, 65, 257, 4099)
 CLOUD_SIZES = (1, 2, 255, 256, 257, 4099)
 PAST_ONE_TILE = (17, 19, 16)  # 5168 cells
-GRIDS = {"all_points": (1, 1, 1), "2x3x5": (2, 3, 5), "default": None, "past_one_scan_tile": PAST_ONE_TILE}
+ONE_TILE = (16, 16, 16)  # 4096 cells: exactly one tile of the scan
+ONE_PAST_A_TILE = (1, 17, 241)  # 4097 cells: the second tile holds one cell
+GRIDS = {"all_points": (1, 1, 1), "2x3x5": (2, 3, 5), "default": None, "past_one_scan_tile": PAST_ONE_TILE,
+         "one_scan_tile": ONE_TILE, "one_past_a_scan_tile": ONE_PAST_A_TILE}
 
 
 def _scan_tile():
-    """kKnnScanTile of csrc/knn.hip: the cells one tile of the one-workgroup scan covers."""
-    text = open(os.path.join(ROOT, "lidar-nerf_amd", "csrc", "knn.hip")).read()
-    m = re.search(r"kKnnScanThreads = (\d+), kKnnScanPerThread = (\d+), kKnnScanTile = kKnnScanThreads \* kKnnScanPerThread;", text)
+    """kScanTile of csrc/scan.h: the cells one tile of the one-workgroup scan covers."""
+    text = open(os.path.join(ROOT, "lidar-nerf_amd", "csrc", "scan.h")).read()
+    m = re.search(r"kScanThreads = (\d+), kScanPerThread = (\d+), kScanTile = kScanThreads \* kScanPerThread;", text)
     return int(m.group(1)) * int(m.group(2))
 
 
@@ -85,6 +88,10 @@ def test_the_whole_output_equals_the_brute_force_at_every_grid(name, grid):
     points, values, queries, idx, d2, means = _case(name)
     if grid == "past_one_scan_tile":
         assert np.prod(PAST_ONE_TILE) > _scan_tile() + 1000
+    if grid == "one_scan_tile":
+        assert np.prod(ONE_TILE) == _scan_tile()
+    if grid == "one_past_a_scan_tile":
+        assert np.prod(ONE_PAST_A_TILE) == _scan_tile() + 1
     index = _index(points, GRIDS[grid])
     assert GRIDS[grid] is None or index.grid == GRIDS[grid]
     assert index.N == len(points) and index.bounds == (tuple(points.min(0).tolist()), tuple(points.max(0).tolist()))

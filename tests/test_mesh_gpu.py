@@ -6,6 +6,7 @@ and float(i) + t, each one IEEE fp32 operation on both sides (hipcc's fp32 divis
 flags, nothing is contracted: -ffp-contract=off).  No tolerance is used anywhere in this file."""
 import functools
 import os
+import re
 
 import numpy as np
 import pytest
@@ -14,10 +15,20 @@ import torch
 import marching_cubes_ref as ref
 
 pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SENTINEL = 0x5ca1ab1e
 # csrc/mesh.hip: one workgroup holds kMcThreads = 256 lattice points, and k_mc_scan scans the workgroup totals in tiles of
-# kMcScanTile = 1024 threads x 4 = 4096 totals: a volume of more than 4096 * 256 = 1 048 576 samples needs a second tile.
-MC_THREADS, MC_SCAN_TILE = 256, 4096
+# kScanTile (csrc/scan.h) = 1024 threads x 4 = 4096 totals: a volume of more than 4096 * 256 = 1 048 576 samples needs a second tile.
+MC_THREADS = 256
+
+
+def _scan_tile():
+    text = open(os.path.join(ROOT, "lidar-nerf_amd", "csrc", "scan.h")).read()
+    m = re.search(r"kScanThreads = (\d+), kScanPerThread = (\d+), kScanTile = kScanThreads \* kScanPerThread;", text)
+    return int(m.group(1)) * int(m.group(2))
+
+
+MC_SCAN_TILE = _scan_tile()
 
 
 def _bits(a):

@@ -25,14 +25,17 @@ RAY_COUNTS = (1, 63, 64, 65, 257, 4099)
 
 
 def _scan_tile():
-    """kRcScanTile of csrc/raycast.hip: the cells one tile of the one-workgroup scan covers."""
-    text = open(os.path.join(ROOT, "lidar-nerf_amd", "csrc", "raycast.hip")).read()
-    m = re.search(r"kRcScanThreads = (\d+), kRcScanPerThread = (\d+), kRcScanTile = kRcScanThreads \* kRcScanPerThread;", text)
+    """kScanTile of csrc/scan.h: the cells one tile of the one-workgroup scan covers."""
+    text = open(os.path.join(ROOT, "lidar-nerf_amd", "csrc", "scan.h")).read()
+    m = re.search(r"kScanThreads = (\d+), kScanPerThread = (\d+), kScanTile = kScanThreads \* kScanPerThread;", text)
     return int(m.group(1)) * int(m.group(2))
 
 
 PAST_ONE_TILE = (17, 19, 16)  # 5168 cells
-GRIDS = {"all_triangles": (1, 1, 1), "2x3x5": (2, 3, 5), "default": None, "past_one_scan_tile": PAST_ONE_TILE}
+ONE_TILE = (16, 16, 16)  # 4096 cells: exactly one tile of the scan
+ONE_PAST_A_TILE = (1, 17, 241)  # 4097 cells: the second tile holds one cell
+GRIDS = {"all_triangles": (1, 1, 1), "2x3x5": (2, 3, 5), "default": None, "past_one_scan_tile": PAST_ONE_TILE,
+         "one_scan_tile": ONE_TILE, "one_past_a_scan_tile": ONE_PAST_A_TILE}
 
 
 def _bits(a):
@@ -185,6 +188,10 @@ def test_the_whole_output_equals_the_restatement_at_every_grid(name, grid):
     assert 0 < hits < len(o), "the ray set must both hit and miss"
     if grid == "past_one_scan_tile":
         assert np.prod(PAST_ONE_TILE) > _scan_tile() + 1000
+    if grid == "one_scan_tile":
+        assert np.prod(ONE_TILE) == _scan_tile()
+    if grid == "one_past_a_scan_tile":
+        assert np.prod(ONE_PAST_A_TILE) == _scan_tile() + 1
     scene = _scene(v, t, GRIDS[grid])
     got = _cast(scene, o, d)
     print(f"{name} / {grid}: grid {scene.grid}, {scene.entries} entries for {len(t)} triangles, {hits} of {len(o)} rays hit")

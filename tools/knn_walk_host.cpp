@@ -30,14 +30,14 @@ void build(Index &ix, const std::vector<float> &points, uint32_t nx, uint32_t ny
     for (int a = 0; a < 3; a++) ix.box[a] = inf, ix.box[3 + a] = -inf;
     for (uint32_t i = 0; i < ix.N; i++)
         for (int a = 0; a < 3; a++) ix.box[a] = fminf(ix.box[a], points[i * 3 + a]), ix.box[3 + a] = fmaxf(ix.box[3 + a], points[i * 3 + a]);
-    const KnnGrid g = knn_grid(ix.box.data(), nx, ny, nz);
+    const CellGrid g = cell_grid(ix.box.data(), nx, ny, nz);
     const uint32_t cells = nx * ny * nz, S = nx + ny + nz, off[3] = {0, nx, nx + ny};
     std::vector<uint32_t> cell(ix.N), count(cells, 0);
     std::vector<float> lo(S, inf), hi(S, -inf);
     for (uint32_t i = 0; i < ix.N; i++) {
         uint32_t c[3];
         for (int a = 0; a < 3; a++) {
-            c[a] = knn_cell_of(points[i * 3 + a], g.lo[a], g.inv[a], g.n[a]);
+            c[a] = cell_of(points[i * 3 + a], g.lo[a], g.inv[a], g.n[a]);
             lo[off[a] + c[a]] = fminf(lo[off[a] + c[a]], points[i * 3 + a]);
             hi[off[a] + c[a]] = fmaxf(hi[off[a] + c[a]], points[i * 3 + a]);
         }
