@@ -71,6 +71,16 @@ LNH_API int lnh_grid_encode_forward(const float *inputs, const void *embeddings,
                                     void *outputs, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S,
                                     uint32_t H, void *dy_dx, uint32_t gridtype, int align_corners, uint32_t interp,
                                     int dtype, lnh_stream_t stream);
+/* Scheduling knob of the three forward entry points, process-wide; never changes a result.  The forward's workgroups run
+ * level-major (all of level 0, then level 1, ...) except for up to `max_pairs` PAIRS of levels — the finest hashed level
+ * with the coarsest level, the next finest with the next coarsest, ... — whose workgroups alternate in blocks of `block`
+ * consecutive ids (rounded up to a power of two in 8 .. 1024; 0 = the default block, 32).  A pair needs a fine level of the
+ * plain hashed class (power-of-two table, linear interpolation, align_corners off) and a partner that is hashed or dense
+ * in every dimension.  max_pairs = 0: plain level-major order.  max_pairs = 0xffffffff, the default: the default block, and
+ * as many pairs as have a fine level of at least 32 times its partner's resolution (5 pairs for 16 levels from 16 to
+ * 32768).  The environment variable LNH_FWD_SCHEDULE = "max_pairs[,block]", read at the first forward call, sets the same
+ * two numbers unless this function was called before. */
+LNH_API void lnh_grid_forward_set_schedule(uint32_t max_pairs, uint32_t block);
 /*
  * Replaces grid_encode_backward  gridencoder.h:26-41 (gridencoder.cu:639-693).
  * grad [L,B,C] (dtype); grad_embeddings [rows,C] (dtype), ZERO-INITIALISED by the caller (grid.py:106), receives

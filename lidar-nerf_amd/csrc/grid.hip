@@ -5,8 +5,9 @@
 //   * the level geometry (scale, resolution, dense/hash decision, modulo strategy) is resolved ONCE on the host and
 //     handed to the kernel in kernarg SGPRs, so the per-corner index math is a handful of VALU ops with no
 //     per-thread loop-carried stride test and no integer division on the hot levels;
-//   * one 2D launch, blockIdx.y = level (dispatch order is x-fastest, so the chip works level-major and every XCD's
-//     4 MiB L2 holds the ~2 MiB fp16 table of the level in flight);
+//   * one launch whose workgroup ids run through the levels one after the other (FwdSched), so the chip works
+//     level-major and every XCD's 4 MiB L2 holds the ~2 MiB fp16 table of the level in flight; the finest hashed levels
+//     each share their turn with one small coarse level;
 //   * 64 consecutive lanes = 64 consecutive sample points (consecutive samples along a LiDAR ray): coarse-level
 //     corner gathers of a wave hit a few cache lines; the [L,B,C] output store is a fully coalesced 256 B / wave;
 //   * backward: packed `global_atomic_pk_add_f16` (fp16 tables) / `global_atomic_add_f32`, preceded by a
@@ -21,6 +22,8 @@ typedef uint32_t uint2_t __attribute__((ext_vector_type(2)));
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 
 namespace {
 
@@ -37,7 +40,58 @@ struct GridMeta {
 };
 struct RowMap {
     uint32_t T_cur, T_tot, slot_off, B_all;
+    uint32_t kind;  // how b0 / T_cur is taken (make_row_map): ROW_DIV per lane, ROW_UNIFORM on the scalar unit, ROW_SHIFT
+    uint32_t aux;   // ROW_UNIFORM: floor(2^32 / T_cur); ROW_SHIFT: log2(T_cur)
 };
+enum { ROW_DIV = 0, ROW_UNIFORM = 1, ROW_SHIFT = 2 };
+constexpr uint32_t kFwdThreads = 256;  // points (= threads) of a forward workgroup
+
+// floor(2^32 / d) clamped to 32 bits: mul_hi(n, .) is n / d or one less for every 32-bit n (n / d - n * m / 2^32 < 1), so a
+// workgroup-uniform quotient costs one scalar multiply-high and one compare — the scalar unit has no divide.
+inline uint32_t recip32(uint32_t d) { return (uint32_t)std::min<uint64_t>((1ull << 32) / d, 0xffffffffull); }
+__device__ __forceinline__ uint32_t div_recip(uint32_t n, uint32_t d, uint32_t recip, uint32_t &rem) {
+    uint32_t q = (uint32_t)(((uint64_t)n * recip) >> 32);
+    rem = n - q * d;
+    if (rem >= d) {
+        q++;
+        rem -= d;
+    }
+    return q;
+}
+
+// Forward schedule: which (level, chunk) the workgroup with linear id w works on.  The ids are cut into slots of `chunks`
+// workgroups; the first 2 * n_pairs slots are PAIRS (two slots each), the rest single levels in ascending order.  Inside a
+// pair the two levels alternate in blocks of G = 2^g_log2 consecutive ids (a multiple of 8: consecutive workgroups are dealt
+// round-robin to the 8 XCDs, so every XCD sees both levels), the `tail` chunks past the last whole block following as two
+// runs.  A pair joins a level bound by distinct-line requests to L2 (fine hashed) with one that hardly loads L2 (dense or
+// low hashed: it streams positions in and features out): run one after the other, each leaves the other's unit idle;
+// side by side about 60 % of the coarse level's time disappears (profiles/forward_level_pairs.txt).  n_pairs = 0 is the
+// level-major order of a (chunks, L) launch.
+struct FwdSched {
+    uint32_t chunks, chunks_recip;  // workgroups per level, recip32 of it
+    uint32_t n_pairs, g_log2;
+    uint32_t full_end, tail;     // ids of a pair below full_end alternate in whole blocks; tail = chunks % G
+    uint32_t n_blocks;           // full_end / G
+    uint32_t lv[LNH_MAX_LEVELS];  // slot -> level (slots 2p, 2p + 1: the levels of pair p)
+};
+struct FwdSlot {
+    uint32_t level, chunk;
+};
+// scalar arithmetic only: w is workgroup-uniform
+__device__ __forceinline__ FwdSlot fwd_slot(const FwdSched &s, uint32_t w) {
+    // (selects, not branches: every field of the schedule is then fetched by the kernel's first scalar loads)
+    uint32_t rem;
+    const uint32_t q = div_recip(w, s.chunks, s.chunks_recip, rem);
+    const uint32_t r = (q & 1u) * s.chunks + rem;  // id inside the pair, 0 .. 2 * chunks - 1
+    const uint32_t blk = r >> s.g_log2;            // whole blocks: even ones to the first level, odd ones to the second
+    const uint32_t chunk_b = ((blk >> 1) << s.g_log2) + (r & ((1u << s.g_log2) - 1u));
+    const uint32_t rr = r - s.full_end;  // the tail: `tail` chunks of the first level, then of the second (rr < 2 * tail)
+    const uint32_t first = q & ~1u, second = q | 1u, half = s.full_end >> 1;
+    const bool whole = blk < s.n_blocks, pair = q < 2 * s.n_pairs, tail2 = rr >= s.tail;
+    const uint32_t slot_b = (blk & 1u) ? second : first;
+    const uint32_t slot_t = tail2 ? second : first, chunk_t = tail2 ? half + rr - s.tail : half + rr;
+    return FwdSlot{s.lv[pair ? (whole ? slot_b : slot_t) : q], pair ? (whole ? chunk_b : chunk_t) : rem};
+}
 enum { LV_HASH = 16, LV_POW2 = 32, LV_NOWRAP = 64, LV_RSTRIDE = 128, LV_WRAP1 = 256 };
 // gridtype 2: tiny-cuda-nn's lattice (its published GridEncoding: grid_index / pos_fract, restated; parity with a real
 // tiny-cuda-nn build is unpinned).  Same scale, resolution, hash and cell position as gridtype 0, but a dense level has
@@ -215,18 +269,38 @@ __device__ __forceinline__ void store_vec(T *p, const Vec<T, C> &r) {
 
 // ------------------------------------------------------------------------------------------------ forward
 template <typename T, int D, int C, bool DYDX>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(kFwdThreads)
 k_grid_forward(const float *__restrict__ inputs, const T *__restrict__ table, T *__restrict__ outputs,
                T *__restrict__ dy_dx, uint32_t B, uint32_t L, GridMeta meta, uint32_t align_rt, uint32_t interp_rt,
-               RowMap map) {
-    const uint32_t b0 = blockIdx.x * blockDim.x + threadIdx.x;
+               RowMap map, FwdSched sched) {
+    const FwdSlot slot = fwd_slot(sched, blockIdx.x);
+    const uint32_t base = slot.chunk * kFwdThreads;  // workgroup-uniform
+    const uint32_t b0 = base + threadIdx.x;
     if (b0 >= B) return;
     {  // (tools/probe_variants.py "fusion" turns this block into a loop over the levels: the encode -> MLP fusion probe)
-    const uint32_t level = blockIdx.y;
+    const uint32_t level = slot.level;
     const LevelParams lv_rt = meta.lv[level];
     // optional row map: launch index b0 = r*T_cur + j addresses row r*T_tot + slot_off + j of buffers holding
-    // B_all rows (coarse and fine samples of a ray side by side); identity when T_cur == 0
-    const uint32_t b = map.T_cur ? (b0 / map.T_cur) * map.T_tot + map.slot_off + b0 % map.T_cur : b0;
+    // B_all rows (coarse and fine samples of a ray side by side); identity when T_cur == 0.  The division is per lane only
+    // where it has to be: a workgroup inside one ray (T_cur a multiple of its threads) takes r on the scalar unit, a
+    // power-of-two T_cur that divides the workgroup takes it with a shift.
+    uint32_t b = b0;
+    if (map.T_cur) {
+#ifdef LNH_FWD_ONLY_MAP  // tools/isa_sections.py: one row-map path per census
+        const uint32_t kind = LNH_FWD_ONLY_MAP;
+#else
+        const uint32_t kind = map.kind;
+#endif
+        if (kind == ROW_UNIFORM) {
+            uint32_t j0;
+            const uint32_t r = div_recip(base, map.T_cur, map.aux, j0);
+            b = r * map.T_tot + map.slot_off + j0 + threadIdx.x;
+        } else if (kind == ROW_SHIFT) {
+            b = (b0 >> map.aux) * map.T_tot + map.slot_off + (b0 & (map.T_cur - 1u));
+        } else {
+            b = (b0 / map.T_cur) * map.T_tot + map.slot_off + b0 % map.T_cur;
+        }
+    }
     const uint32_t Bs = map.T_cur ? map.B_all : B;
     float x[D];
 #pragma unroll
@@ -411,12 +485,17 @@ k_grid_forward(const float *__restrict__ inputs, const T *__restrict__ table, T 
     }
     };
     const bool plain = align_rt == 0 && interp_rt == 0;
+#ifdef LNH_FWD_ONLY_MODE  // tools/isa_sections.py: one class per census
+    (void)plain;
+    body(std::integral_constant<int, LNH_FWD_ONLY_MODE>{});
+#else
     if (plain && (lv_rt.flags & (LV_HASH | LV_POW2)) == (LV_HASH | LV_POW2)) body(std::integral_constant<int, 1>{});
     else if (plain && !(lv_rt.flags & LV_HASH) && (lv_rt.flags & LV_NOWRAP) && (lv_rt.flags & 15u) == (uint32_t)D)
         body(std::integral_constant<int, 2>{});
     else if (plain && !(lv_rt.flags & LV_HASH) && (lv_rt.flags & LV_WRAP1) && (lv_rt.flags & 15u) == (uint32_t)D)
         body(std::integral_constant<int, 3>{});
     else body(std::integral_constant<int, 0>{});
+#endif
     }  // level
 }
 
@@ -2131,16 +2210,92 @@ int with_dtype(int dtype, F f) {  // dtype has passed check_common
     return dtype == LNH_F32 ? f(float{}) : f(half_t{});
 }
 
+RowMap make_row_map(uint32_t T_cur, uint32_t T_tot, uint32_t slot_off, uint32_t B_all) {
+    RowMap map{T_cur, T_tot, slot_off, B_all, ROW_DIV, 0};
+    if (T_cur && T_cur % kFwdThreads == 0) {
+        map.kind = ROW_UNIFORM;
+        map.aux = recip32(T_cur);
+    } else if (T_cur && (T_cur & (T_cur - 1)) == 0) {
+        map.kind = ROW_SHIFT;
+        while ((1u << map.aux) < T_cur) map.aux++;
+    }
+    return map;
+}
+
+// Forward schedule knobs, process-wide (lnh_grid_forward_set_schedule; first read from LNH_FWD_SCHEDULE = "pairs[,block]").
+// The defaults are what profiles/forward_level_pairs.txt measured on MI355X: blocks of 32 workgroups (8: slower than
+// level-major order, 128: the same), and by default (kFwdAuto) a pair forms only where the fine level's resolution is at
+// least kFwdMinRatio times its partner's — pairs at ratios 2048 .. 35 each take 7 to 10 us off 3.41 M points, the pair at
+// ratio 13 nothing, those at 4.6 and 2.1 (two levels of the same kind) ADD 4 and 2 us.
+constexpr uint32_t kFwdAuto = 0xffffffffu, kFwdBlockDefault = 32, kFwdMinRatio = 32;
+uint32_t g_fwd_pairs = kFwdAuto, g_fwd_block_log2 = 5;
+bool g_fwd_env_read = false;
+
+void set_fwd_schedule(uint32_t max_pairs, uint32_t block) {
+    if (block == 0) block = kFwdBlockDefault;
+    uint32_t lg = 3;  // G: a power of two, 8 .. 1024
+    while (lg < 10 && (1u << lg) < block) lg++;
+    g_fwd_pairs = max_pairs;
+    g_fwd_block_log2 = lg;
+    g_fwd_env_read = true;
+}
+
+// 1 hashed power-of-two level, 2 / 3 dense level (reference / tiny-cuda-nn lattice), 0 generic: k_grid_forward's classes
+int fwd_level_class(const LevelParams &p, uint32_t D, bool plain) {
+    if (!plain) return 0;
+    if ((p.flags & (LV_HASH | LV_POW2)) == (LV_HASH | LV_POW2)) return 1;
+    if (!(p.flags & LV_HASH) && (p.flags & 15u) == D) return (p.flags & LV_NOWRAP) ? 2 : (p.flags & LV_WRAP1) ? 3 : 0;
+    return 0;
+}
+
+// Pairs: the finest hashed level with the coarsest level, the next finest with the next coarsest, ... — at most g_fwd_pairs
+// of them (kFwdAuto: as many as pass the resolution ratio), as long as the fine one is of the plain hashed class and
+// neither is of the generic class.  Everything else runs alone in ascending order; no pair at all = level-major order.
+FwdSched build_fwd_schedule(const GridMeta &m, uint32_t B, uint32_t D, uint32_t L, bool plain) {
+    if (!g_fwd_env_read) {
+        g_fwd_env_read = true;
+        if (const char *e = getenv("LNH_FWD_SCHEDULE")) {
+            unsigned pairs = 0, block = 0;
+            if (sscanf(e, "%u,%u", &pairs, &block) >= 1) set_fwd_schedule(pairs, block);
+        }
+    }
+    FwdSched s{};
+    s.chunks = div_up(B, kFwdThreads);
+    s.chunks_recip = recip32(s.chunks);
+    s.g_log2 = g_fwd_block_log2;
+    s.tail = s.chunks & ((1u << s.g_log2) - 1u);
+    s.full_end = 2u * (s.chunks - s.tail);
+    s.n_blocks = s.full_end >> s.g_log2;
+    bool paired[LNH_MAX_LEVELS] = {};
+    uint32_t n = 0;
+    if (L >= 2) {
+        for (uint32_t lo = 0, hi = L - 1; lo < hi && s.n_pairs < g_fwd_pairs; lo++, hi--) {
+            if (fwd_level_class(m.lv[hi], D, plain) != 1 || fwd_level_class(m.lv[lo], D, plain) == 0) break;
+            if (g_fwd_pairs == kFwdAuto && m.lv[hi].resolution < (uint64_t)kFwdMinRatio * m.lv[lo].resolution) break;
+            s.lv[n++] = hi;
+            s.lv[n++] = lo;
+            paired[hi] = paired[lo] = true;
+            s.n_pairs++;
+        }
+    }
+    for (uint32_t l = 0; l < L; l++)
+        if (!paired[l]) s.lv[n++] = l;
+    return s;
+}
+
 template <typename T, int D>
 int launch_forward_c(const float *inputs, const T *emb, T *out, T *dy_dx, uint32_t B, uint32_t C, uint32_t L,
-                     const GridMeta &m, uint32_t align, uint32_t interp, hipStream_t s, RowMap map = RowMap{0, 0, 0, 0}) {
-    dim3 grid(div_up(B, 256), /* levels */ L), block(256);
+                     const GridMeta &m, uint32_t align, uint32_t interp, hipStream_t s, RowMap map = make_row_map(0, 0, 0, 0)) {
+    const FwdSched sched = build_fwd_schedule(m, B, D, L, align == 0 && interp == 0);
+    dim3 grid(sched.chunks * /* levels */ L), block(kFwdThreads);
     const int rc = with_channels(C, [&](auto c) {
         constexpr int CC = decltype(c)::value;
         if (dy_dx)
-            LNH_LAUNCH((k_grid_forward<T, D, CC, true>), grid, block, 0, s, inputs, emb, out, dy_dx, B, L, m, align, interp, map);
+            LNH_LAUNCH((k_grid_forward<T, D, CC, true>), grid, block, 0, s, inputs, emb, out, dy_dx, B, L, m, align, interp, map,
+                       sched);
         else
-            LNH_LAUNCH((k_grid_forward<T, D, CC, false>), grid, block, 0, s, inputs, emb, out, dy_dx, B, L, m, align, interp, map);
+            LNH_LAUNCH((k_grid_forward<T, D, CC, false>), grid, block, 0, s, inputs, emb, out, dy_dx, B, L, m, align, interp, map,
+                       sched);
         return LNH_OK;
     });
     return rc ? rc : lnh_check_launch("lnh_grid_encode_forward");
@@ -2275,7 +2430,7 @@ int lnh_grid_encode_forward_mapped_ex(const float *inputs_all, const void *embed
                 "grid forward (mapped): gridtype must be 0 (hash) or 2 (tiny-cuda-nn lattice), got %u", gridtype);
     GridMeta m;
     if ((rc = resolve_levels(m, offsets_host, 3, L, S, H, gridtype, 0))) return rc;
-    const RowMap map{T_cur, T_tot, slot_off, B_all};
+    const RowMap map = make_row_map(T_cur, T_tot, slot_off, B_all);
     return with_dtype(dtype, [&](auto t) {
         using T = decltype(t);
         return launch_forward_c<T, 3>(inputs_all, (const T *)embeddings, (T *)outputs_all, nullptr, B, C, L, m, 0, 0,
@@ -2289,6 +2444,10 @@ int lnh_grid_encode_forward_mapped(const float *inputs_all, const void *embeddin
                                    lnh_stream_t stream) {
     return lnh_grid_encode_forward_mapped_ex(inputs_all, embeddings, offsets_host, outputs_all, B, T_cur, T_tot, slot_off,
                                              B_all, C, L, S, H, kGridHash, dtype, stream);
+}
+
+void lnh_grid_forward_set_schedule(uint32_t max_pairs, uint32_t block) {
+    set_fwd_schedule(max_pairs, max_pairs == kFwdAuto ? 0 : block);
 }
 
 int lnh_grid_encode_backward(const void *grad, const float *inputs, const void *embeddings,

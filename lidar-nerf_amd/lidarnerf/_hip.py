@@ -154,7 +154,8 @@ for _n in ("lnh_mlp_forward", "lnh_mlp_backward", "lnh_mlp_backward_data", "lnh_
 EXPORTS = sorted(list(_SIGS) + ["lnh_version", "lnh_last_error", "lnh_arch", "lnh_build_variant",
                                  "lnh_grid_backward_workspace_size", "lnh_grid_backward_workspace_size_min",
                                  "lnh_grid_backward_plan_info", "lnh_grid_backward_workspace_clear_bytes",
-                                 "lnh_grid_backward_set_slice_entries", "lnh_wgrad_workspace_bytes",
+                                 "lnh_grid_backward_set_slice_entries", "lnh_grid_forward_set_schedule",
+                                 "lnh_wgrad_workspace_bytes",
                                  "lnh_lidar_loss_ex_workspace_bytes", "lnh_lidar_eval_workspace_bytes",
                                  "lnh_eval_points_workspace_bytes", "lnh_lidar_to_pano_fpa_workspace_size",
                                  "lnh_marching_cubes_workspace_size", "lnh_raycast_workspace_size",
@@ -193,6 +194,9 @@ def lib():
         L.lnh_grid_backward_plan_info.restype = C.c_int
         L.lnh_grid_backward_set_slice_entries.argtypes = [U32]
         L.lnh_grid_backward_set_slice_entries.restype = None
+        if hasattr(L, "lnh_grid_forward_set_schedule"):
+            L.lnh_grid_forward_set_schedule.argtypes = [U32, U32]
+            L.lnh_grid_forward_set_schedule.restype = None
         L.lnh_wgrad_workspace_bytes.argtypes = []
         L.lnh_wgrad_workspace_bytes.restype = C.c_uint64
         L.lnh_lidar_loss_ex_workspace_bytes.argtypes = [U32]

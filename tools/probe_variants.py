@@ -101,9 +101,11 @@ SLICES = {"s384": _slice(384), "s256": _slice(256), "s192": _slice(192), "s128":
 # gives up: the level-major launch order that keeps ONE level's ~2 MB table in each XCD's L2.
 FUSION = {
     "fwdloop": ("grid.hip", [
-        ('    {  // (tools/probe_variants.py "fusion" turns this block into a loop over the levels: the encode -> MLP fusion probe)\n    const uint32_t level = blockIdx.y;\n',
+        ('    {  // (tools/probe_variants.py "fusion" turns this block into a loop over the levels: the encode -> MLP fusion probe)\n    const uint32_t level = slot.level;\n',
          "    for (uint32_t level = 0; level < L; level++) {\n"),
-        ("    dim3 grid(div_up(B, 256), /* levels */ L), block(256);", "    dim3 grid(div_up(B, 256), 1), block(256);")]),
+        # (a grid of `chunks` workgroups and no pairs: the schedule decodes every id to slot 0, chunk = id)
+        ("    dim3 grid(sched.chunks * /* levels */ L), block(kFwdThreads);", "    dim3 grid(sched.chunks), block(kFwdThreads);"),
+        ("uint32_t g_fwd_pairs = kFwdAuto,", "uint32_t g_fwd_pairs = 0,")]),
     "product": ("grid.hip", []),
 }
 
@@ -161,9 +163,7 @@ NTMEM = {"full": ("grid.hip", []),
          "ntall": ("grid.hip", [_NT_OUT, _NT_IN, _NT_SIN] + _NT_POOL)}
 # ---- workgroup size of the encode forward (256 threads in the product)
 def _fwd_threads(n):
-    return ("grid.hip", [("// ------------------------------------------------------------------------------------------------ forward\ntemplate <typename T, int D, int C, bool DYDX>\n__global__ void __launch_bounds__(256)",
-                          "// ------------------------------------------------------------------------------------------------ forward\ntemplate <typename T, int D, int C, bool DYDX>\n__global__ void __launch_bounds__(%d)" % n),
-                         ("    dim3 grid(div_up(B, 256), /* levels */ L), block(256);", "    dim3 grid(div_up(B, %d), /* levels */ L), block(%d);" % (n, n))])
+    return ("grid.hip", [("constexpr uint32_t kFwdThreads = 256;", "constexpr uint32_t kFwdThreads = %d;" % n)])
 
 
 FWDWG = {"full": ("grid.hip", []), "fw64": _fwd_threads(64), "fw128": _fwd_threads(128), "fw512": _fwd_threads(512), "fw1024": _fwd_threads(1024)}
