@@ -891,6 +891,49 @@ LNH_API int lnh_raydrop_adam(float *params, float *exp_avg, float *exp_avg_sq, c
                              const float *lr_table, uint32_t lr_len, const float *step_in, float *step_out, double beta1,
                              double beta2, double eps, lnh_stream_t stream);
 
+/* ---- the ray-drop U-Net of the mesh baselines (README f11; lidarnvs/unet.py: UNet(10, 1, bilinear=False) in eval mode,
+ * the reference's --amp arithmetic) — csrc/unet.hip.  Inference only.
+ * Activations: fp16, NHWC [N, H, W, C] with C a multiple of 32.  Weights: fp16, rounded to nearest even from fp32.  Every
+ *   product sum of the convolutions is accumulated in fp32 on v_mfma_f32_16x16x32_f16, k in the order (tap row-major, source 0
+ *   channels, source 1 channels); no float atomics, no partial sums in memory: an output is a function of (packed parameters,
+ *   input, tile) alone and two calls are bit-identical.  No call reads the host or allocates; all can be captured in a hipGraph.
+ *   Every pointer must be 16-byte aligned.  N H W of any image at most 2^26.
+ * lnh_unet_workspace_size(N, H, W): bytes of every activation buffer of one forward of the whole net on [N, 10, H, W] (the
+ *   layout is lidarnerf/unet.py: workspace_layout; every buffer 256-byte aligned); 0 for a refused shape (N = 0, H or W < 16,
+ *   N H W > 2^26).
+ * lnh_unet_input: in [N, C, H, W] f32 (1 <= C <= 32) -> out [N, H, W, 32] fp16, channels C .. 31 zero.
+ * lnh_unet_conv3x3: 3 x 3 convolution, padding 1, no bias, of the channel concatenation (src0, src1), then eval-mode BatchNorm
+ *   and ReLU in fp32: out[n, y, x, co] = fp16(max(fmaf(acc, scale[co], shift[co]), 0)), out [N, H, W, Cout].
+ *   src0 [N, H0, W0, C0]: pool = 0: H0 = H, W0 = W.  pool = 1: the 2 x 2 maximum of src0 is taken on read (MaxPool2d(2));
+ *     H = H0 / 2, W = W0 / 2 (floor: an odd last row or column is dropped).
+ *   src1 [N, H1, W1, C1] or NULL (C1 = 0): channels C0 .. C0 + C1 - 1 (torch.cat([skip, upsampled])), placed top-left, reading as
+ *     zero for y >= H1 or x >= W1 (F.pad); H - H1 and W - W1 must be 0 or 1.
+ *   weight [Cout, 9, C0 + C1] fp16 (torch's [Cout, Cin, 3, 3] with the channel last); scale, shift [Cout] f32.
+ *   C0, C1 multiples of 32 up to 1024 (C0 >= 32), Cout a multiple of 64 up to 1024.
+ *   tile: 0 = chosen from the shape; LNH_UNET_TILE_16 / _32 / _64: pixels per wave, four waves of a workgroup on neighbouring
+ *     pixel tiles and the same 64 output channels; LNH_UNET_TILE_KSPLIT: 16 pixels per workgroup, its four waves share the k
+ *     range and add their partial sums through LDS in the fixed order (w0 + w1) + (w2 + w3).  The first three give the same
+ *     bits; the last may differ from them in the last place of the fp32 sum.
+ * lnh_unet_upconv2x2: ConvTranspose2d(kernel 2, stride 2) with bias: in [N, H, W, Cin] -> out [N, 2H, 2W, Cout],
+ *   out[n, 2y+dy, 2x+dx, co] = fp16(bias[co] + sum_ci in[n, y, x, ci] weight[2dy + dx, co, ci]); weight [4, Cout, Cin] fp16 (torch's
+ *   [Cin, Cout, 2, 2] permuted), bias [Cout] f32.  Cin a multiple of 32 up to 1024, Cout a multiple of 64 up to 1024.
+ * lnh_unet_head: the 1 x 1 output convolution: in [N, H, W, 64] fp16, weight [64] fp16, bias [1] f32 (read on the device) ->
+ *   logits [N, 1, H, W] f32 = bias + the fmaf chain over channel 0 .. 63 in fp32; mask (or NULL) [N, 1, H, W] f32 = 1 where
+ *   logit > 0 (sigmoid(logit) > 0.5), else 0 — also for a NaN logit. */
+#define LNH_UNET_TILE_16 1u
+#define LNH_UNET_TILE_32 2u
+#define LNH_UNET_TILE_64 4u
+#define LNH_UNET_TILE_KSPLIT 8u
+LNH_API uint64_t lnh_unet_workspace_size(uint32_t N, uint32_t H, uint32_t W);
+LNH_API int lnh_unet_input(const float *in, uint32_t N, uint32_t C, uint32_t H, uint32_t W, void *out, lnh_stream_t stream);
+LNH_API int lnh_unet_conv3x3(const void *src0, uint32_t C0, uint32_t H0, uint32_t W0, uint32_t pool, const void *src1,
+                             uint32_t C1, uint32_t H1, uint32_t W1, const void *weight, const float *scale,
+                             const float *shift, uint32_t N, uint32_t Cout, uint32_t tile, void *out, lnh_stream_t stream);
+LNH_API int lnh_unet_upconv2x2(const void *in, uint32_t N, uint32_t H, uint32_t W, uint32_t Cin, const void *weight,
+                               const float *bias, uint32_t Cout, void *out, lnh_stream_t stream);
+LNH_API int lnh_unet_head(const void *in, uint32_t N, uint32_t H, uint32_t W, const void *weight, const float *bias,
+                          float *logits, float *mask, lnh_stream_t stream);
+
 /* ---- evaluation: nearest-neighbour pass of the chamfer distance (extern/chamfer3D/chamfer3D.cu:9-138)
  * dist[j] = min_k |xyz1[j] - xyz2[k]|^2 (squared), idx[j] = the first k attaining it; xyz* are [n,3] / [m,3] f32.
  */

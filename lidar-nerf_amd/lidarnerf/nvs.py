@@ -6,7 +6,8 @@ the GPU.
 What is not pinned against the reference: Open3D's order among equidistant neighbours and NumPy's float32 np.mean
 (here: smallest index first, an fp64 rank-order sum rounded once), and its float64 pose matrices (here fp32).  The pose is taken
 as affine (last row 0 0 0 1), which is what homo_project's division by w amounts to for a LiDAR pose.  The ray-drop U-Net of the
-mesh baselines, its training and the meshing itself (MeshNVS has no fit) are not part of this.  No CPU fallback.
+mesh baselines is lidarnerf/unet.py (RayDropUNet, inference); its training and the meshing itself (MeshNVS has no fit)
+are not part of this.  No CPU fallback.
 
 PointCloudNVS is the point-cloud baseline, LidarNVSPCGen of lidarnvs/lidarnvs_pcgen.py:16-248: the training cloud itself is
 projected ("cp": closest point, "fpa": first-peak averaging over a z-buffer), turned back into a cloud, and masked by the
@@ -60,7 +61,10 @@ class MeshNVS:
     """scene: a raycast.RaycastingScene (for instance LidarTrainer.mesh_scene()).  points float [N,3] / point_intensities
     float [N]: the world-frame training cloud LidarNVSMeshing.fit keeps (tensors or NumPy arrays; moved to the scene's GPU).
     intensity_interpolate_k: neighbours averaged per hit point (lidarnvs_poisson.py's default 5; run.py passes 9).
-    grid_resolution: of the cloud's PointCloudIndex."""
+    grid_resolution: of the cloud's PointCloudIndex.  set_raydrop(model) stores the model predict_frame_with_raydrop uses when it
+    is given none (LidarNVSMeshing's ckpt_path: unet.RayDropUNet.from_checkpoint(path), or any callable)."""
+
+    raydrop = None
 
     def __init__(self, scene, points, point_intensities, intensity_interpolate_k=5, grid_resolution=None):
         if not isinstance(scene, RaycastingScene):
@@ -80,6 +84,14 @@ class MeshNVS:
         self.index = PointCloudIndex(points.to(self.device), grid_resolution=grid_resolution)
         self.points = self.index.points
         self.point_intensities = inten.detach().reshape(-1).to(self.device, torch.float32).contiguous()
+
+    def set_raydrop(self, model):
+        """Store the ray-drop model (a unet.RayDropUNet, or any callable from the [1,10,H,W] feature image to [1,1,H,W] logits) that
+        predict_frame_with_raydrop and predict_images_with_raydrop use when none is passed; None removes it.  Returns self."""
+        if model is not None and not callable(model):
+            raise TypeError("MeshNVS.set_raydrop: the model must be callable")
+        self.raydrop = model
+        return self
 
     def predict_frame(self, lidar_K, lidar_pose, lidar_H, lidar_W, compact=True):
         """The reference's predict_dict as device tensors: pano f32 [H,W], intensities f32 [H,W], hit_dict (intersect_lidar's,
@@ -112,10 +124,15 @@ class MeshNVS:
         return self.scene.raydrop_features(lidar_K, pose, lidar_H, lidar_W, intensities=frame["intensities"])
 
     @torch.no_grad()
-    def predict_frame_with_raydrop(self, lidar_K, lidar_pose, lidar_H, lidar_W, model):
-        """lidarnvs_meshing.py:170-291.  model: any callable from the [1,10,H,W] feature image to [1,1,H,W] logits; a pixel
-        is kept where sigmoid(logit) > 0.5.  pano and intensities are multiplied by that mask and turned back into the clouds
-        (convert.pano_to_lidar_with_intensities, then the pose)."""
+    def predict_images_with_raydrop(self, lidar_K, lidar_pose, lidar_H, lidar_W, model=None):
+        """The images of predict_frame_with_raydrop without its clouds: pano, intensities (both multiplied by the mask) and
+        hit_dict.  Nothing reads the host (the clouds' length is the one host read of predict_frame_with_raydrop), so with a
+        unet.RayDropUNet the whole call can be captured."""
+        if model is None:
+            model = self.raydrop
+        if model is None:
+            raise TypeError("MeshNVS.predict_frame_with_raydrop() missing 1 required positional argument: 'model' "
+                            "(pass one, or store one with set_raydrop)")
         H, W = int(lidar_H), int(lidar_W)
         pose = _pose(lidar_pose, self.device)
         frame = self.predict_frame(lidar_K, pose, H, W, compact=False)
@@ -124,14 +141,22 @@ class MeshNVS:
         if not torch.is_tensor(logits) or logits.numel() != H * W:
             raise ValueError(f"MeshNVS.predict_frame_with_raydrop: the model must return [1, 1, {H}, {W}] logits")
         keep = (torch.sigmoid(logits.detach().to(self.device, torch.float32)) > 0.5).to(torch.float32).reshape(H, W)
-        pano = frame["pano"] * keep
-        intensities = frame["intensities"] * keep
-        local4 = convert.pano_to_lidar_with_intensities(pano, intensities, lidar_K)
+        return {"pano": frame["pano"] * keep, "intensities": frame["intensities"] * keep, "hit_dict": frame["hit_dict"]}
+
+    @torch.no_grad()
+    def predict_frame_with_raydrop(self, lidar_K, lidar_pose, lidar_H, lidar_W, model=None):
+        """lidarnvs_meshing.py:170-291.  model: any callable from the [1,10,H,W] feature image to [1,1,H,W] logits (a
+        unet.RayDropUNet is the reference's network); None: the model stored with set_raydrop.  A pixel is kept where
+        sigmoid(logit) > 0.5.  pano and intensities are multiplied by that mask and turned back into the clouds
+        (convert.pano_to_lidar_with_intensities, then the pose)."""
+        pose = _pose(lidar_pose, self.device)
+        out = self.predict_images_with_raydrop(lidar_K, pose, lidar_H, lidar_W, model)
+        local4 = convert.pano_to_lidar_with_intensities(out["pano"], out["intensities"], lidar_K)
         local_points = local4[:, :3].contiguous()
         local_inten = local4[:, 3].contiguous()
-        return {"pano": pano, "intensities": intensities, "points": transform_points(local_points, pose),
+        return {"pano": out["pano"], "intensities": out["intensities"], "points": transform_points(local_points, pose),
                 "point_intensities": local_inten, "local_points": local_points, "local_point_intensities": local_inten,
-                "hit_dict": frame["hit_dict"]}
+                "hit_dict": out["hit_dict"]}
 
 
 PCGEN_KEYS = ("pano", "intensities") + CLOUD_KEYS
