@@ -18,6 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 # Developer hook for A/B experiments (tools/): LNH_VARIANT=name builds lib/liblidarnerf_hip_<name>.so from objects in
 # lib/obj_<name>/ with LNH_EXTRA_FLAGS appended; the product library and its objects are not touched.
 _VARIANT = os.environ.get("LNH_VARIANT", "")
+_GRID_FILES = "grid_forward.hip grid_backward.hip grid_bwd_scatter.hip grid_bwd_reduce.hip"  # LNH_VARIANT_FILES default
 OBJ = os.path.join(HERE, "lib", "obj" + ("_" + _VARIANT if _VARIANT else ""))
 LIB = os.path.join(HERE, "lib", "liblidarnerf_hip" + ("_" + _VARIANT if _VARIANT else "") + ".so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -62,7 +63,7 @@ def _local_includes(src, seen=None):
 
 def _compile(src, force):
     out = os.path.join(OBJ, os.path.basename(src).replace(".hip", ".o"))
-    if _VARIANT and os.path.basename(src) not in os.environ.get("LNH_VARIANT_FILES", "grid.hip").split():
+    if _VARIANT and os.path.basename(src) not in os.environ.get("LNH_VARIANT_FILES", _GRID_FILES).split():
         return os.path.join(HERE, "lib", "obj", os.path.basename(out)), False  # unchanged files: the product's objects
     deps = (glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(HERE, "..", "include", "*.h")) +
             sorted(_local_includes(src)))
@@ -79,7 +80,8 @@ def _compile(src, force):
 def build(force=False, jobs=None, verbose=True):
     os.makedirs(OBJ, exist_ok=True)
     srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
-    jobs = jobs or min(len(srcs), os.cpu_count() or 4)
+    # MAX_JOBS: the share of a machine this build may use (os.cpu_count() reports all of it)
+    jobs = jobs or min(len(srcs), int(os.environ.get("MAX_JOBS") or os.cpu_count() or 4))
     objs, rebuilt = [], False
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:
         for out, did in ex.map(lambda s: _compile(s, force), srcs):

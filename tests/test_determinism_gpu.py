@@ -1,5 +1,5 @@
 """Bit-reproducibility of the training path.  Every sum over samples on it has a fixed order: the hash-table gradient is an
-integer sum per row (csrc/grid.hip, bucketed backward), the weight gradients of the MLP family are per-workgroup partials
+integer sum per row (csrc/grid_pool.h, bucketed backward), the weight gradients of the MLP family are per-workgroup partials
 added up in index order (csrc/wgrad.h — rounds 1-5 used fp32 device atomics there, and two runs of the same seed drifted
 apart within a few hundred steps), the loss is a slot-ordered sum.  So: the same entry point twice gives the same bits, and
 two training runs from the same seed give the same table and the same weights — launch by launch and as a captured step."""

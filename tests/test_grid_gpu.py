@@ -281,7 +281,7 @@ def test_backward_bucketed_overflow_by_a_few(dt):
     cidx = c_oracle.grid_indices(cells, OFF, CH, S, H)[level] // CH        # [2, 8]
 
     def entry_buckets(ix):
-        """Pool entries of points with corner rows ix [n, 8] (grid.hip, "pool entries"): one entry per x-neighbour pair of
+        """Pool entries of points with corner rows ix [n, 8] (grid_pool.h, "pool entries"): one entry per x-neighbour pair of
         corners (2p, 2p + 1) in the bucket of the first row, plus one in the bucket of the second row when the rows differ
         in more than 7 low bits (r0 ^ r1 = 2^(t+1) - 1 with t >= 7: the pair travels as two singles).  -> (point, bucket)."""
         r0, r1 = ix[:, 0::2], ix[:, 1::2]
@@ -438,7 +438,7 @@ def test_backward_ws_ex_with_buffers_the_caller_cleared(dt):
 
 
 def test_dense_levels_are_dealt_to_64_buckets():
-    """Plan of the dense plain levels (grid.hip bucket_of_row): rows go to min(64, ceil(rows / 128)) buckets in groups of
+    """Plan of the dense plain levels (grid_pool.h bucket_of_row): rows go to min(64, ceil(rows / 128)) buckets in groups of
     128, so the few cells around the sensor that every LiDAR ray leaves are reduced by many workgroups, not one."""
     for level, rows in ((0, 17 ** 3), (1, 28 ** 3), (2, 45 ** 3), (3, 75 ** 3)):
         assert int(OFF[level + 1] - OFF[level]) >= rows
@@ -525,6 +525,39 @@ def test_backward_bucketed_generic_level_classes(dt, interp, gridtype, align):
         ge = torch.zeros((rows, CH), dtype=dt, device="cuda")
         call("lnh_grid_encode_backward_ws", dev(g), dev(x), offh, ge, B, 3, CH, L, S, H, gridtype, int(align), interp,
              code, ws, need)
+        outs.append(ge)
+    assert torch.equal(outs[0], outs[1])
+    _check_table(host(outs[0]).astype(np.float64), want, dt)
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.float16])
+def test_backward_bucketed_generic_class_overflow(dt):
+    """The generic scatter kernel's spill branch: a bucket of a generic-class level outgrows its pool share.  Smoothstep
+    interpolation makes every level generic (8 singles per point).  B = 8192: a hashed level has a worst case of 65536
+    entries over 64 buckets, so its pool share (plan_buckets) is 1024 + 1024 / 8 + 12 * sqrt(1024) + 64 = 1600 slots per
+    bucket.  Points 0..4095 alternate between two cells (alternating, so the run-merge cannot collapse them): every corner
+    row of either cell receives 2048 entries, so at least one bucket overflows whatever the hash does.  The spill list holds
+    the level's whole worst case at this size (min(max(65536 / 16, 2^20), 65536)), so no float atomic is reached and the
+    sum is exact: equal to the oracle, and bit-identical run to run."""
+    from gpu_util import call, dev, host
+    from lidarnerf import _hip
+    B, rows = 8192, int(OFF[-1])
+    x = np.random.default_rng(21).random((B, 3), dtype=np.float32)
+    x[0:4096:2] = 0.3
+    x[1:4096:2] = 0.41
+    nd = np.float32 if dt == torch.float32 else np.float16
+    g = (np.random.default_rng(22).standard_normal((L, B, CH)) * 0.1).astype(nd)
+    want = c_oracle.grid_backward(g, x, OFF, rows, S, H, 0, False, 1)
+    code = 0 if dt == torch.float32 else 1
+    offh = torch.from_numpy(OFF)
+    need = _hip.lib().lnh_grid_backward_workspace_size(offh.data_ptr(), B, 3, CH, L, S, H, 0, 0, code)
+    assert need > 0
+    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    gd, xd = dev(g), dev(x)
+    outs = []
+    for _ in range(2):
+        ge = torch.zeros((rows, CH), dtype=dt, device="cuda")
+        call("lnh_grid_encode_backward_ws", gd, xd, offh, ge, B, 3, CH, L, S, H, 0, 0, 1, code, ws, need)
         outs.append(ge)
     assert torch.equal(outs[0], outs[1])
     _check_table(host(outs[0]).astype(np.float64), want, dt)

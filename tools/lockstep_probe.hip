@@ -5,7 +5,7 @@
 // net would run from LDS; here a stand-in reads every feature once and writes 4 bytes per point, which lower-bounds it).
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics -ffp-contract=off tools/lockstep_probe.hip \
-//         lidar-nerf_amd/csrc/core.hip -o tools/bin/lockstep_probe && tools/bin/lockstep_probe
+//         lidar-nerf_amd/csrc/core.hip lidar-nerf_amd/csrc/grid_forward.hip -o tools/bin/lockstep_probe && tools/bin/lockstep_probe
 //
 // Compared, on the same points (4096 LiDAR rays x 832 samples, fp16 tables, 16 levels to resolution 32768) and with the
 // same per-point arithmetic (locate + 8 corner gathers, no wide-load tricks):
@@ -13,7 +13,7 @@
 //   (b) lock-step: features to LDS, grid barrier per level, consume      — the fusion candidate
 //   (c) the same without the barriers (workgroups drift apart)           — what round 3 measured on the product kernel
 // plus the product's own forward for reference.  Results: profiles/r04_fusion_lockstep.txt.
-#include "../lidar-nerf_amd/csrc/grid.hip"
+#include "../lidar-nerf_amd/csrc/grid_geom.h"
 
 #include <cstdlib>
 #include <vector>
