@@ -934,6 +934,53 @@ LNH_API int lnh_unet_upconv2x2(const void *in, uint32_t N, uint32_t H, uint32_t 
 LNH_API int lnh_unet_head(const void *in, uint32_t N, uint32_t H, uint32_t W, const void *weight, const float *bias,
                           float *logits, float *mask, lnh_stream_t stream);
 
+/* ---- U-Net training (README f12) — csrc/unet_train.hip.  So far: the max-pool and head backward, and the transposed
+ * convolution's weight pack, data gradient and weight / bias gradient.
+ * Activations and activation gradients: fp16 NHWC, rounded once per tensor; parameter gradients f32.  No float atomics: a sum that
+ * is split goes to a workspace as partials and is added in a fixed order, so two calls give the same bits.  No call reads the host
+ * or allocates.  N H W of any image at most 2^26.
+ * lnh_unet_pool_backward: the gradient of MaxPool2d(2) at x [N, H0, W0, C] fp16 for dpool [N, H0 / 2, W0 / 2, C] fp16 (floor):
+ *   dx[n, y, x, c] = fp16(route + skip) in fp32, where route = dpool of the element's window if the element is the FIRST maximum of
+ *   that 2 x 2 window in row-major order (strict >, and a NaN takes over from any earlier value: torch's rule), else 0 — also 0 in a last odd row or column, which no window
+ *   covers — and skip = dskip[(n, y, x) skip_stride + c], or 0 with dskip NULL (then skip_stride = 0).  dskip is read in place from
+ *   a tensor with skip_stride >= C channels per pixel (a multiple of 8, up to 2048): channels [0, C) of the data gradient of the
+ *   concatenating convolution.  C a multiple of 32, 32 .. 1024; H0, W0 >= 2.  One owner per element.
+ * lnh_unet_head_backward: the 1 x 1 head.  a [N, H, W, 64] fp16 (the head's input), weight [64] fp16 (as lnh_unet_head reads it),
+ *   dlogits [N, 1, H, W] f32, used as given (loss scaling is the caller's; non-finite values pass through) ->
+ *   dx [N, H, W, 64] fp16 = fp16(dlogit[p] weight[c]) (one fp32 product);
+ *   dweight [64] f32 = sum_p fp32(dlogit[p] a[p, c]); dbias [1] f32 = sum_p dlogit[p].  The sums: the 64 consecutive pixels
+ *   64 k .. 64 k + 63 are added in fp32 by the xor butterfly (lane i with lane i ^ 32, then ^ 16, .. ^ 1), those partials go to
+ *   ws and are added in ascending k in float64, the result rounded to f32.
+ *   ws: lnh_unet_head_backward_workspace_size(N, H, W) = ceil(N H W / 64) x 65 x 4 bytes (0: refused shape), 16-byte aligned.
+ * lnh_unet_pack_upconv: weight f32 [Cin, Cout, 2, 2] (the ConvTranspose2d parameter itself) -> fwd fp16 [4, Cout, Cin], the image
+ *   lnh_unet_upconv2x2 reads (fwd[2dy + dx, co, ci] = fp16(weight[ci, co, dy, dx])), and, unless bwd is NULL, bwd fp16
+ *   [Cin, 4, Cout] with bwd[ci, 2dy + dx, co] the same value: the image of the data gradient.  Cin, Cout multiples of 64 up to 1024.
+ * lnh_unet_upconv2x2_backward_data: dx [N, H, W, Cin] fp16 = fp16(sum_{q, co} dy[n, 2y + (q >> 1), 2x + (q & 1), co] bwd[ci, q, co]),
+ *   fp32 sums on the MFMA, k in the order (q, co).  dy is read in place: channels [dy_offset, dy_offset + Cout) of an fp16 tensor
+ *   [N, Hd, Wd, dy_stride] with Hd - 2H and Wd - 2W each 0 or 1 (the gradient at a padded last row / column is dropped); offset and
+ *   stride multiples of 8, stride up to 2048.  Cin a multiple of 64, Cout a multiple of 32, both up to 1024.
+ * lnh_unet_upconv2x2_backward_weight: dweight f32 [Cin, Cout, 2, 2] (the parameter's layout; overwritten) with dweight[ci, co, q] =
+ *   sum over the M = N H W input pixels p of x[p, ci] dy[2p + q, co], fp32 sums on the MFMA, and dbias f32 [Cout] = the sum of dy
+ *   over the 4 M output pixels.  x [N, H, W, Cin] fp16; dy read in place as in lnh_unet_upconv2x2_backward_data.  Cin, Cout
+ *   multiples of 64 up to 1024.  The pixel range is cut into S = min(ceil(M / 256), max(1, floor(16 MiB / (16 Cin Cout)))) slices
+ *   of L = ceil(M / S) rounded up to 32 pixels (then S = ceil(M / L)); within a slice the sums run over steps of 32 pixels in
+ *   ascending order (dbias: per step q, then pixel, ascending, one fp32 chain); the slices go to ws and are added in ascending order
+ *   in float64.  ws: lnh_unet_upconv2x2_backward_weight_workspace_size(N, H, W, Cin, Cout) = S (4 Cin Cout + Cout) x 4 bytes
+ *   (0: refused shape), 16-byte aligned.  Same shape, same bits. */
+LNH_API int lnh_unet_pool_backward(const void *x, uint32_t N, uint32_t H0, uint32_t W0, uint32_t C, const void *dpool,
+                                   const void *dskip, uint32_t skip_stride, void *dx, lnh_stream_t stream);
+LNH_API int lnh_unet_pack_upconv(const float *weight, uint32_t Cin, uint32_t Cout, void *fwd, void *bwd, lnh_stream_t stream);
+LNH_API int lnh_unet_upconv2x2_backward_data(const void *dy, uint32_t Hd, uint32_t Wd, uint32_t dy_stride, uint32_t dy_offset,
+                                             uint32_t N, uint32_t H, uint32_t W, uint32_t Cin, uint32_t Cout, const void *weight,
+                                             void *dx, lnh_stream_t stream);
+LNH_API uint64_t lnh_unet_upconv2x2_backward_weight_workspace_size(uint32_t N, uint32_t H, uint32_t W, uint32_t Cin, uint32_t Cout);
+LNH_API int lnh_unet_upconv2x2_backward_weight(const void *x, const void *dy, uint32_t Hd, uint32_t Wd, uint32_t dy_stride,
+                                               uint32_t dy_offset, uint32_t N, uint32_t H, uint32_t W, uint32_t Cin, uint32_t Cout,
+                                               void *ws, uint64_t ws_bytes, float *dweight, float *dbias, lnh_stream_t stream);
+LNH_API uint64_t lnh_unet_head_backward_workspace_size(uint32_t N, uint32_t H, uint32_t W);
+LNH_API int lnh_unet_head_backward(const void *a, uint32_t N, uint32_t H, uint32_t W, const void *weight, const float *dlogits,
+                                   void *ws, uint64_t ws_bytes, void *dx, float *dweight, float *dbias, lnh_stream_t stream);
+
 /* ---- evaluation: nearest-neighbour pass of the chamfer distance (extern/chamfer3D/chamfer3D.cu:9-138)
  * dist[j] = min_k |xyz1[j] - xyz2[k]|^2 (squared), idx[j] = the first k attaining it; xyz* are [n,3] / [m,3] f32.
  */
