@@ -106,14 +106,20 @@ struct SpillEntry {
     v2_t<T> a, b;
 };
 
-// value * 2^24 of an fp16 number as an exact 64-bit integer in 5 VALU operations: x = h * 2^24 is an integer with
-// |x| < 2^40, so the double 1.5 * 2^52 + x is exact and its 52 mantissa bits hold 2^51 + x — low word = x mod 2^32, the 20
-// bits above = 2^19 + floor(x / 2^32).  (The bit-twiddling form — (1024 | m) << (e - 1), negate — cost 12 per value and
-// made the reduce pass VALU-bound: 34 VALU operations per pool entry against two ds_add_u64.)
+// value * 2^24 of an fp16 number as an exact 64-bit integer in 4 VALU operations: x = h * 2^24 is an integer with
+// |x| < 2^40, so the double 1.5 * 2^52 + x is exact, its exponent is that of 2^52 and its 52 mantissa bits hold 2^51 + x —
+// low word = x mod 2^32, high word = 0x43380000 + floor(x / 2^32).  (The bit-twiddling form — (1024 | m) << (e - 1),
+// negate — cost 12 per value and made the reduce pass VALU-bound: 34 VALU operations per pool entry against two
+// ds_add_u64.)
+// A NON-FINITE value must not vanish in the integer sum: the training step looks for inf / NaN in this table gradient to
+// skip an overflowed step.  The high word is therefore taken WHOLE (not its 20 mantissa bits, which are zero for inf and
+// cancel for a NaN: a NaN gradient left a finite table): inf / NaN (exponent 0x7ff) give |x| >= 2^61 in multiples of 2^42, so
+// a row's sum that holds any count of them short of an exact multiple of 1024 stays beyond 2^42, and the float step of the
+// reduce pass rounds it to an infinity of the fp16 table.
 __device__ __forceinline__ long long half_to_fixed24(half_t h) {
     const double d = __builtin_fma((double)(float)h, 16777216.0, 6755399441055744.0);
     const unsigned long long bits = __builtin_bit_cast(unsigned long long, d);
-    const int hi = (int)((uint32_t)(bits >> 32) & 0xFFFFFu) - 0x80000;
+    const int hi = (int)(uint32_t)(bits >> 32) - 0x43380000;
     return (long long)(((unsigned long long)(uint32_t)hi << 32) | (bits & 0xFFFFFFFFull));
 }
 // fixed-point images: fp16 contributions are exact multiples of 2^-24; fp32 ones get 2^-40 resolution, +-8e6 of range
