@@ -180,9 +180,8 @@ def test_resample_points_writes_the_coordinates_of_the_new_samples():
 
 
 def test_resample_against_reference_golden(golden_dir):
-    """G1: reference sample_pdf outputs; here the stage-1 weights are fed through sigma so that w == golden weights
-    is not reproducible, so instead check the inverse-cdf stage alone by a degenerate construction: T-2 bins with
-    alpha ~ weights (tiny sigma => w ~ alpha ~ sigma*delta)."""
+    """G1: reference sample_pdf outputs.  First the properties on a random smooth ray (monotone in u, inside the ray); then the
+    golden rows themselves, reproduced through sigma, against the reference's `rnd` and `det`."""
     from gpu_util import call
     g = np.load(os.path.join(golden_dir, "g1_sample_pdf.npz"))
     bins = torch.from_numpy(g["bins"])  # [B, 767] z_mid; rebuild z so that z_mid(z) == bins is not needed: only
@@ -198,3 +197,29 @@ def test_resample_against_reference_golden(golden_dir):
     assert torch.all(nz[:, 1:] >= nz[:, :-1])
     assert torch.all(nz >= z[:, :1]) and torch.all(nz <= z[:, -1:])
     assert bins.shape[1] == 767
+    # The comparison with the reference's own outputs: the golden weights fed through the sigma that reproduces them and a z
+    # whose midpoints are the golden bins (render_exact_cases.g1_inputs: the rows whose weights can be compositing weights),
+    # with G1's u against `rnd` and with the deterministic u against `det`, within the derived bound of the inverse cdf
+    # (render_exact_cases.icdf_reference, float64 on the kernel's inputs) plus the reference's own float32 deviation from
+    # float64 on the golden data and the float64 distance between the two sets of inputs.
+    import render_exact_cases as rc
+    zk, sk, sdk, rows = rc.g1_inputs(g["bins"], g["weights"])
+    assert list(rows) == [3, 5] and g["weights"][3].max() == 0.0 and g["weights"][5].sum() == 1.0
+    zm = zk.astype(np.float64)[:, :-1] + 0.5 * np.diff(zk.astype(np.float64), axis=1)
+    assert np.abs(zm - g["bins"][rows]).max() < 2.0 ** -23                 # midpoints of the float32 z = the golden bins
+    B = len(rows)
+    for name, uk in (("rnd", g["u"][rows]), ("det", u[:B].numpy())):
+        ref = rc.icdf_reference(zk, sk, sdk, 1.0, uk)
+        gold = g[name][rows].astype(np.float64)
+        gold64 = render_ref.sample_pdf(torch.from_numpy(g["bins"][rows]).double(), torch.from_numpy(g["weights"][rows]).double(),
+                                       64, u=torch.from_numpy(uk).double()).numpy()
+        own, moved = np.abs(gold - gold64), np.abs(gold64 - ref["s"])
+        assert own.max() < 1e-6 and moved.max() < 1e-7 and not ref["excluded"].any()
+        nz, zo, pm = (torch.empty((B, 64), device="cuda"), torch.empty((B, T + 64), device="cuda"),
+                      torch.empty((B, T + 64), dtype=torch.int32, device="cuda"))
+        call("lnh_lidar_resample", torch.from_numpy(zk).cuda(), torch.from_numpy(sk).cuda(), torch.from_numpy(sdk).cuda(),
+             torch.from_numpy(np.ascontiguousarray(uk)).cuda(), B, T, 64, 1.0, 0, nz, zo, pm)
+        err = np.abs(nz.cpu().numpy().astype(np.float64) - gold)
+        share = float((err / (ref["bound"] + own + moved)).max())
+        print(f"[bound] G1 {name}: max |new_z - golden| = {err.max():.3e}, {share:.3f} of the bound")
+        assert share <= 1.0, (name, share)
