@@ -934,8 +934,10 @@ LNH_API int lnh_unet_upconv2x2(const void *in, uint32_t N, uint32_t H, uint32_t 
 LNH_API int lnh_unet_head(const void *in, uint32_t N, uint32_t H, uint32_t W, const void *weight, const float *bias,
                           float *logits, float *mask, lnh_stream_t stream);
 
-/* ---- U-Net training (README f12) — csrc/unet_train.hip.  So far: the max-pool and head backward, and the transposed
- * convolution's weight pack, data gradient and weight / bias gradient.
+/* ---- U-Net training (README f12) — csrc/unet_train.hip, csrc/unet_train_conv.hip (and the RAW epilogue of csrc/unet.hip).
+ * The max-pool and head backward, the transposed convolution's weight pack, data gradient and weight / bias gradient, and the
+ * training-mode convolution layer without its weight gradient: weight pack, raw convolution (forward and data gradient), batch
+ * statistics, BatchNorm + ReLU and their backward.
  * Activations and activation gradients: fp16 NHWC, rounded once per tensor; parameter gradients f32.  No float atomics: a sum that
  * is split goes to a workspace as partials and is added in a fixed order, so two calls give the same bits.  No call reads the host
  * or allocates.  N H W of any image at most 2^26.
@@ -980,6 +982,46 @@ LNH_API int lnh_unet_upconv2x2_backward_weight(const void *x, const void *dy, ui
 LNH_API uint64_t lnh_unet_head_backward_workspace_size(uint32_t N, uint32_t H, uint32_t W);
 LNH_API int lnh_unet_head_backward(const void *a, uint32_t N, uint32_t H, uint32_t W, const void *weight, const float *dlogits,
                                    void *ws, uint64_t ws_bytes, void *dx, float *dweight, float *dbias, lnh_stream_t stream);
+/* The training-mode convolution layer, a = relu(bn(z)), z = fp16(conv3x3(x)), BatchNorm on the statistics of the batch.
+ * lnh_unet_pack_conv3x3: weight f32 [Cout, Cin, 3, 3] (the Conv2d parameter itself) -> fwd fp16 [Cout, 9, Cpad], the image
+ *   lnh_unet_conv3x3 reads (fwd[co, t, ci] = fp16(weight[co, ci, t]), channels Cin .. Cpad - 1 zero; Cpad = 32 for Cin <= 32, else
+ *   Cin, which must then be a multiple of 32 up to 1024), and, unless bwd is NULL, bwd fp16 [Cin, 9, Cout] with bwd[ci, t, co] =
+ *   fp16(weight[co, ci, 8 - t]): the flipped and transposed image, on which the same convolution is the data gradient.  bwd needs
+ *   Cin % 64 == 0.  Cout a multiple of 64 up to 1024.
+ * lnh_unet_conv3x3_raw: lnh_unet_conv3x3 without scale / shift: out = fp16(acc), the same main loop, sources, pool on read, padding
+ *   rule, tile argument and tile rule.  As the data gradient: dx = conv3x3_raw(dz, bwd) with C0 = the layer's Cout, no pool, no second
+ *   source and Cout = the layer's C0 + C1; for a pooling layer dx is the gradient of the pooled tensor (lnh_unet_pool_backward's
+ *   dpool), for a concatenating layer [N, H, W, C0 + C1], which lnh_unet_pool_backward (skip channels) and
+ *   lnh_unet_upconv2x2_backward_* (offset C0) read in place.
+ * lnh_unet_bn_stats: z fp16 [M, C] (M = N H W >= 2, C a multiple of 32 up to 1024), gamma, beta f32 [C] -> mean, invstd f32 [C]
+ *   (saved for the backward), scale = gamma invstd, shift = beta - mean scale f32 [C], and in place unless NULL running_mean <-
+ *   (1 - momentum) running_mean + momentum mean, running_var <- (1 - momentum) running_var + momentum var M / (M - 1).  The
+ *   statistics are those of the rounded z.  sum z and sum z^2 in float64 (an fp16 square is exact there), in a fixed order: with
+ *   P = 256 ceil(M / 2^14) pixels per partial (at most 64 partials), row r = 0 .. 31 of partial k chains the pixels k P + r,
+ *   k P + r + 32, ..; the rows of a partial are added in ascending r, the partials go to ws and are added in ascending k.  mean = S1 / M, var =
+ *   max(S2 / M - mean^2, 0) (biased; a NaN stays), invstd = 1 / sqrt(var + eps), scale, shift (from the unrounded scale) and the
+ *   running statistics are formed in float64 and rounded once to f32.  ws: lnh_unet_bn_stats_workspace_size(M, C) =
+ *   ceil(M / P) x 2 C x 8 bytes (0: refused shape), 16-byte aligned.
+ * lnh_unet_bn_relu: a [M, C] fp16 = fp16(max(fmaf(float(z), scale[c], shift[c]), 0)): the epilogue of lnh_unet_conv3x3 on the stored z.
+ * lnh_unet_bn_relu_backward: with g = da [a > 0] and xhat = (float(z) - mean) invstd in fp32: dbeta f32 [C] = sum g, dgamma f32 [C] =
+ *   sum fp32(g xhat), both added in float64 in the order of lnh_unet_bn_stats and rounded once; then dz [M, C] fp16 =
+ *   fp16(scale ((g - dbeta / M) - xhat (dgamma / M))) in fp32 from those rounded sums.  dz may be da (one owner per element, read
+ *   before written).  Linear in da: loss scaling is the caller's; non-finite values pass through.  ws:
+ *   lnh_unet_bn_relu_backward_workspace_size(M, C), the same figure. */
+LNH_API int lnh_unet_pack_conv3x3(const float *weight, uint32_t Cout, uint32_t Cin, void *fwd, void *bwd, lnh_stream_t stream);
+LNH_API int lnh_unet_conv3x3_raw(const void *src0, uint32_t C0, uint32_t H0, uint32_t W0, uint32_t pool, const void *src1,
+                                 uint32_t C1, uint32_t H1, uint32_t W1, const void *weight, uint32_t N, uint32_t Cout,
+                                 uint32_t tile, void *out, lnh_stream_t stream);
+LNH_API uint64_t lnh_unet_bn_stats_workspace_size(uint64_t M, uint32_t C);
+LNH_API int lnh_unet_bn_stats(const void *z, uint64_t M, uint32_t C, const float *gamma, const float *beta, double eps,
+                              double momentum, void *ws, uint64_t ws_bytes, float *mean, float *invstd, float *scale,
+                              float *shift, float *running_mean, float *running_var, lnh_stream_t stream);
+LNH_API int lnh_unet_bn_relu(const void *z, uint64_t M, uint32_t C, const float *scale, const float *shift, void *a,
+                             lnh_stream_t stream);
+LNH_API uint64_t lnh_unet_bn_relu_backward_workspace_size(uint64_t M, uint32_t C);
+LNH_API int lnh_unet_bn_relu_backward(const void *z, const void *a, const void *da, uint64_t M, uint32_t C, const float *mean,
+                                      const float *invstd, const float *scale, void *ws, uint64_t ws_bytes, void *dz,
+                                      float *dgamma, float *dbeta, lnh_stream_t stream);
 
 /* ---- evaluation: nearest-neighbour pass of the chamfer distance (extern/chamfer3D/chamfer3D.cu:9-138)
  * dist[j] = min_k |xyz1[j] - xyz2[k]|^2 (squared), idx[j] = the first k attaining it; xyz* are [n,3] / [m,3] f32.

@@ -63,7 +63,9 @@ struct ConvArgs {
     uint64_t M;  // N H W
 };
 
-template <int MT, bool KS>
+// RAW: the epilogue of the training step, out = fp16(acc) — the convolution in front of batch-statistics BatchNorm and, on the
+// flipped and transposed weight image, its data gradient; scale / shift are not read.
+template <int MT, bool KS, bool RAW>
 __global__ void __launch_bounds__(256)
 k_unet_conv3x3(ConvArgs a) {
     static_assert(!KS || MT == 1, "the k-split variant owns one 16-pixel tile");
@@ -166,10 +168,15 @@ k_unet_conv3x3(ConvArgs a) {
 #pragma unroll
         for (int t = 0; t < 4; t++) {
             const uint32_t co = co0 + 16 * t + 4 * g;
-            const f32x4 s = *reinterpret_cast<const f32x4 *>(a.scale + co), sh = *reinterpret_cast<const f32x4 *>(a.shift + co);
             half4_t o;
+            if constexpr (RAW) {
 #pragma unroll
-            for (int r = 0; r < 4; r++) o[r] = (half_t)fmaxf(fmaf(acc[m][t][r], s[r], sh[r]), 0.0f);
+                for (int r = 0; r < 4; r++) o[r] = (half_t)acc[m][t][r];
+            } else {
+                const f32x4 s = *reinterpret_cast<const f32x4 *>(a.scale + co), sh = *reinterpret_cast<const f32x4 *>(a.shift + co);
+#pragma unroll
+                for (int r = 0; r < 4; r++) o[r] = (half_t)fmaxf(fmaf(acc[m][t][r], s[r], sh[r]), 0.0f);
+            }
             *reinterpret_cast<half4_t *>(a.out + p * a.Cout + co) = o;
         }
     }
@@ -252,6 +259,54 @@ bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 uint64_t pad256(uint64_t b) { return (b + 255) / 256 * 256; }
 
+// lnh_unet_conv3x3 and lnh_unet_conv3x3_raw: one set of checks, one tile rule, one main loop; RAW picks the epilogue.
+template <bool RAW>
+int conv3x3_launch(const char *what, const void *src0, uint32_t C0, uint32_t H0, uint32_t W0, uint32_t pool, const void *src1,
+                   uint32_t C1, uint32_t H1, uint32_t W1, const void *weight, const float *scale, const float *shift, uint32_t N,
+                   uint32_t Cout, uint32_t tile, void *out, lnh_stream_t stream) {
+    LNH_REQUIRE(src0 && weight && (RAW || (scale && shift)) && out, LNH_ERR_INVALID_ARG, "%s: null pointer", what);
+    LNH_REQUIRE(pool <= 1, LNH_ERR_INVALID_ARG, "%s: pool %u (0 or 1)", what, pool);
+    LNH_REQUIRE(C0 >= 32 && C0 <= 1024 && C0 % 32 == 0, LNH_ERR_INVALID_ARG, "%s: C0 %u (a multiple of 32, 32 .. 1024)", what, C0);
+    LNH_REQUIRE(C1 <= 1024 && C1 % 32 == 0, LNH_ERR_INVALID_ARG, "%s: C1 %u (a multiple of 32 up to 1024)", what, C1);
+    LNH_REQUIRE((C1 != 0) == (src1 != nullptr), LNH_ERR_INVALID_ARG, "%s: src1 and C1 must be given together", what);
+    LNH_REQUIRE(Cout >= 64 && Cout <= 1024 && Cout % 64 == 0, LNH_ERR_INVALID_ARG, "%s: Cout %u (a multiple of 64, 64 .. 1024)", what,
+                Cout);
+    const uint32_t H = pool ? H0 / 2 : H0, W = pool ? W0 / 2 : W0;
+    LNH_REQUIRE(N && H && W && (uint64_t)N * H0 * W0 <= kMaxPixels, LNH_ERR_INVALID_ARG,
+                "%s: source [%u, %u, %u], pool %u (output of 1 .. 2^26 pixels)", what, N, H0, W0, pool);
+    if (C1) {
+        LNH_REQUIRE(H1 <= H && H - H1 <= 1 && W1 <= W && W - W1 <= 1 && H1 && W1, LNH_ERR_INVALID_ARG,
+                    "%s: second source %u x %u under an output of %u x %u (each 0 or 1 smaller)", what, H1, W1, H, W);
+    }
+    LNH_REQUIRE(aligned16(src0) && aligned16(src1) && aligned16(weight) && aligned16(scale) && aligned16(shift) && aligned16(out),
+                LNH_ERR_INVALID_ARG, "%s: every pointer must be 16-byte aligned", what);
+    LNH_REQUIRE(tile == 0 || tile == LNH_UNET_TILE_16 || tile == LNH_UNET_TILE_32 || tile == LNH_UNET_TILE_64 ||
+                    tile == LNH_UNET_TILE_KSPLIT,
+                LNH_ERR_INVALID_ARG, "%s: tile %u (0, 1, 2, 4 or 8)", what, tile);
+    ConvArgs a{};
+    a.s0 = (const half_t *)src0; a.s1 = (const half_t *)src1; a.w = (const half_t *)weight;
+    a.scale = scale; a.shift = shift; a.out = (half_t *)out;
+    a.H = H; a.W = W; a.H0 = H0; a.W0 = W0; a.C0 = C0; a.H1 = H1; a.W1 = W1; a.C1 = C1; a.Cout = Cout; a.pool = pool;
+    a.M = (uint64_t)N * H * W;
+    const uint32_t cols = Cout / 64;
+    if (tile == 0) {
+        // From the timings of every layer of a 66 x 1030 frame with every tile (DESIGN §18): the operand reads are hidden by waves
+        // in flight, so a large tile pays only where it leaves two waves per SIMD (2048), or one wave per two SIMDs with a long k
+        // loop; everything smaller — 17 k pixels and fewer — runs fastest with the k range split over a workgroup's waves.
+        auto waves = [&](uint32_t mt) { return (a.M + 16 * mt - 1) / (16 * mt) * cols; };
+        const uint32_t K = 9 * (C0 + C1);
+        if (waves(2) >= 2048) tile = K >= 1024 ? LNH_UNET_TILE_64 : LNH_UNET_TILE_32;
+        else if (waves(4) >= 512 && K >= 2048) tile = LNH_UNET_TILE_64;
+        else tile = LNH_UNET_TILE_KSPLIT;
+    }
+    const hipStream_t s = (hipStream_t)stream;
+    if (tile == LNH_UNET_TILE_KSPLIT) LNH_LAUNCH((k_unet_conv3x3<1, true, RAW>), dim3(div_up(a.M, 16), cols), dim3(256), 0, s, a);
+    else if (tile == LNH_UNET_TILE_16) LNH_LAUNCH((k_unet_conv3x3<1, false, RAW>), dim3(div_up(a.M, 64), cols), dim3(256), 0, s, a);
+    else if (tile == LNH_UNET_TILE_32) LNH_LAUNCH((k_unet_conv3x3<2, false, RAW>), dim3(div_up(a.M, 128), cols), dim3(256), 0, s, a);
+    else LNH_LAUNCH((k_unet_conv3x3<4, false, RAW>), dim3(div_up(a.M, 256), cols), dim3(256), 0, s, a);
+    return lnh_check_launch(RAW ? "lnh_unet_conv3x3_raw" : "lnh_unet_conv3x3");
+}
+
 }  // namespace
 
 extern "C" {
@@ -281,48 +336,15 @@ int lnh_unet_input(const float *in, uint32_t N, uint32_t C, uint32_t H, uint32_t
 int lnh_unet_conv3x3(const void *src0, uint32_t C0, uint32_t H0, uint32_t W0, uint32_t pool, const void *src1, uint32_t C1,
                      uint32_t H1, uint32_t W1, const void *weight, const float *scale, const float *shift, uint32_t N,
                      uint32_t Cout, uint32_t tile, void *out, lnh_stream_t stream) {
-    LNH_REQUIRE(src0 && weight && scale && shift && out, LNH_ERR_INVALID_ARG, "unet_conv3x3: null pointer");
-    LNH_REQUIRE(pool <= 1, LNH_ERR_INVALID_ARG, "unet_conv3x3: pool %u (0 or 1)", pool);
-    LNH_REQUIRE(C0 >= 32 && C0 <= 1024 && C0 % 32 == 0, LNH_ERR_INVALID_ARG,
-                "unet_conv3x3: C0 %u (a multiple of 32, 32 .. 1024)", C0);
-    LNH_REQUIRE(C1 <= 1024 && C1 % 32 == 0, LNH_ERR_INVALID_ARG, "unet_conv3x3: C1 %u (a multiple of 32 up to 1024)", C1);
-    LNH_REQUIRE((C1 != 0) == (src1 != nullptr), LNH_ERR_INVALID_ARG, "unet_conv3x3: src1 and C1 must be given together");
-    LNH_REQUIRE(Cout >= 64 && Cout <= 1024 && Cout % 64 == 0, LNH_ERR_INVALID_ARG,
-                "unet_conv3x3: Cout %u (a multiple of 64, 64 .. 1024)", Cout);
-    const uint32_t H = pool ? H0 / 2 : H0, W = pool ? W0 / 2 : W0;
-    LNH_REQUIRE(N && H && W && (uint64_t)N * H0 * W0 <= kMaxPixels, LNH_ERR_INVALID_ARG,
-                "unet_conv3x3: source [%u, %u, %u], pool %u (output of 1 .. 2^26 pixels)", N, H0, W0, pool);
-    if (C1) {
-        LNH_REQUIRE(H1 <= H && H - H1 <= 1 && W1 <= W && W - W1 <= 1 && H1 && W1, LNH_ERR_INVALID_ARG,
-                    "unet_conv3x3: second source %u x %u under an output of %u x %u (each 0 or 1 smaller)", H1, W1, H, W);
-    }
-    LNH_REQUIRE(aligned16(src0) && aligned16(src1) && aligned16(weight) && aligned16(scale) && aligned16(shift) && aligned16(out),
-                LNH_ERR_INVALID_ARG, "unet_conv3x3: every pointer must be 16-byte aligned");
-    LNH_REQUIRE(tile == 0 || tile == LNH_UNET_TILE_16 || tile == LNH_UNET_TILE_32 || tile == LNH_UNET_TILE_64 ||
-                    tile == LNH_UNET_TILE_KSPLIT,
-                LNH_ERR_INVALID_ARG, "unet_conv3x3: tile %u (0, 1, 2, 4 or 8)", tile);
-    ConvArgs a{};
-    a.s0 = (const half_t *)src0; a.s1 = (const half_t *)src1; a.w = (const half_t *)weight;
-    a.scale = scale; a.shift = shift; a.out = (half_t *)out;
-    a.H = H; a.W = W; a.H0 = H0; a.W0 = W0; a.C0 = C0; a.H1 = H1; a.W1 = W1; a.C1 = C1; a.Cout = Cout; a.pool = pool;
-    a.M = (uint64_t)N * H * W;
-    const uint32_t cols = Cout / 64;
-    if (tile == 0) {
-        // From the timings of every layer of a 66 x 1030 frame with every tile (DESIGN §18): the operand reads are hidden by waves
-        // in flight, so a large tile pays only where it leaves two waves per SIMD (2048), or one wave per two SIMDs with a long k
-        // loop; everything smaller — 17 k pixels and fewer — runs fastest with the k range split over a workgroup's waves.
-        auto waves = [&](uint32_t mt) { return (a.M + 16 * mt - 1) / (16 * mt) * cols; };
-        const uint32_t K = 9 * (C0 + C1);
-        if (waves(2) >= 2048) tile = K >= 1024 ? LNH_UNET_TILE_64 : LNH_UNET_TILE_32;
-        else if (waves(4) >= 512 && K >= 2048) tile = LNH_UNET_TILE_64;
-        else tile = LNH_UNET_TILE_KSPLIT;
-    }
-    const hipStream_t s = (hipStream_t)stream;
-    if (tile == LNH_UNET_TILE_KSPLIT) LNH_LAUNCH((k_unet_conv3x3<1, true>), dim3(div_up(a.M, 16), cols), dim3(256), 0, s, a);
-    else if (tile == LNH_UNET_TILE_16) LNH_LAUNCH((k_unet_conv3x3<1, false>), dim3(div_up(a.M, 64), cols), dim3(256), 0, s, a);
-    else if (tile == LNH_UNET_TILE_32) LNH_LAUNCH((k_unet_conv3x3<2, false>), dim3(div_up(a.M, 128), cols), dim3(256), 0, s, a);
-    else LNH_LAUNCH((k_unet_conv3x3<4, false>), dim3(div_up(a.M, 256), cols), dim3(256), 0, s, a);
-    return lnh_check_launch("lnh_unet_conv3x3");
+    return conv3x3_launch<false>("unet_conv3x3", src0, C0, H0, W0, pool, src1, C1, H1, W1, weight, scale, shift, N, Cout, tile, out,
+                                 stream);
+}
+
+int lnh_unet_conv3x3_raw(const void *src0, uint32_t C0, uint32_t H0, uint32_t W0, uint32_t pool, const void *src1, uint32_t C1,
+                         uint32_t H1, uint32_t W1, const void *weight, uint32_t N, uint32_t Cout, uint32_t tile, void *out,
+                         lnh_stream_t stream) {
+    return conv3x3_launch<true>("unet_conv3x3_raw", src0, C0, H0, W0, pool, src1, C1, H1, W1, weight, nullptr, nullptr, N, Cout, tile,
+                                out, stream);
 }
 
 int lnh_unet_upconv2x2(const void *in, uint32_t N, uint32_t H, uint32_t W, uint32_t Cin, const void *weight, const float *bias,

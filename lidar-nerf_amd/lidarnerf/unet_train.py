@@ -5,16 +5,26 @@
   backward with the skip add, the backward of the 1 x 1 head, the transposed convolution's weight pack, data gradient and weight / bias
   gradient.  One entry point each; they read no host memory and allocate nothing — the caller owns every buffer.  No CPU fallback.
 
-The convolution and BatchNorm kernels of the training step, and with them the module that chains everything, are not in the package
-yet: RayDropUNet keeps refusing training mode."""
+* The training-mode convolution layer without its weight gradient (csrc/unet_train_conv.hip and the RAW epilogue of csrc/unet.hip):
+  pack_conv3x3, conv3x3_raw (the forward convolution and, on the flipped and transposed image, the data gradient), bn_stats, bn_relu,
+  bn_relu_backward.
+* train_forward / train_backward: the whole net in training mode on a RayDropUNet's live parameters, and the gradient of the loss with
+  respect to every activation, every BatchNorm weight / bias, the four transposed convolutions and the head (46 of the 64 parameter
+  tensors), in one workspace that is allocated once per shape.
+
+Still missing: the 3 x 3 convolution's weight gradient, the optimizer step and the module around them; RayDropUNet keeps refusing
+training mode."""
 import torch
 import torch.nn.functional as F
 
 from . import _hip
-from .unet import _nhwc
+from . import unet as _unet
+from .unet import CHANNELS, _nhwc
 
 _SYMBOLS = ("lnh_unet_pool_backward", "lnh_unet_head_backward", "lnh_unet_head_backward_workspace_size", "lnh_unet_pack_upconv",
-            "lnh_unet_upconv2x2_backward_data", "lnh_unet_upconv2x2_backward_weight", "lnh_unet_upconv2x2_backward_weight_workspace_size")
+            "lnh_unet_upconv2x2_backward_data", "lnh_unet_upconv2x2_backward_weight", "lnh_unet_upconv2x2_backward_weight_workspace_size",
+            "lnh_unet_pack_conv3x3", "lnh_unet_conv3x3_raw", "lnh_unet_bn_stats", "lnh_unet_bn_stats_workspace_size", "lnh_unet_bn_relu",
+            "lnh_unet_bn_relu_backward", "lnh_unet_bn_relu_backward_workspace_size")
 
 
 # ---- loss and validation score ------------------------------------------------------------------------------------------------------
@@ -166,3 +176,309 @@ def upconv2x2_backward_weight(x, dy, ws, dweight, dbias, offset=0):
     _hip.call("lnh_unet_upconv2x2_backward_weight", _hip.ptr(x), _hip.ptr(dy), Hd, Wd, Cs, int(offset), N, H, W, Cin, Cout, _hip.ptr(ws),
               have, _hip.ptr(dweight), _hip.ptr(dbias))
     return dweight, dbias
+
+
+# ---- the training-mode convolution layer -------------------------------------------------------------------------------------------
+def pack_conv3x3(weight, fwd, bwd=None):
+    """lnh_unet_pack_conv3x3: weight f32 [Cout, Cin, 3, 3] (the parameter) -> fwd fp16 [Cout, 9, Cpad] (what conv3x3 / conv3x3_raw read;
+    Cpad = 32 for Cin <= 32, else Cin) and, if given, bwd fp16 [Cin, 9, Cout] with bwd[ci, t, co] = weight[co, ci, 8 - t] (what
+    conv3x3_raw reads as the data gradient; Cin a multiple of 64)."""
+    if not (torch.is_tensor(weight) and weight.is_cuda and weight.dtype == torch.float32 and weight.dim() == 4 and
+            weight.is_contiguous() and tuple(weight.shape[2:]) == (3, 3)):
+        raise RuntimeError("lidarnerf.unet_train.pack_conv3x3: weight must be a contiguous f32 [Cout, Cin, 3, 3] GPU tensor")
+    Cout, Cin = weight.shape[:2]
+    cpad = 32 if Cin <= 32 else Cin
+    for t, shape, what in ((fwd, (Cout, 9, cpad), "fwd"), (bwd, (Cin, 9, Cout), "bwd")):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float16 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise RuntimeError(f"lidarnerf.unet_train.pack_conv3x3: {what} must be contiguous fp16 {shape} on the GPU")
+    _hip.require_symbols(_SYMBOLS, "U-Net training")
+    _hip.call("lnh_unet_pack_conv3x3", _hip.ptr(weight.detach()), Cout, Cin, _hip.ptr(fwd), _hip.ptr(bwd))
+    return fwd, bwd
+
+
+def conv3x3_raw(src0, weight, out, src1=None, pool=False, tile=0):
+    """lnh_unet_conv3x3_raw: lidarnerf.unet.conv3x3 without scale / shift, out = fp16(acc).  With pack_conv3x3's bwd image as weight and
+    dz as src0 it is the data gradient of the layer: out [N, H, W, C0 + C1]."""
+    _nhwc(src0, "src0"), _nhwc(out, "out")
+    N, H0, W0, C0 = src0.shape
+    H1 = W1 = C1 = 0
+    if src1 is not None:
+        _, H1, W1, C1 = _nhwc(src1, "src1").shape
+    Cout = out.shape[3]
+    H, W = (H0 // 2, W0 // 2) if pool else (H0, W0)
+    if tuple(out.shape) != (N, H, W, Cout) or not torch.is_tensor(weight) or tuple(weight.shape) != (Cout, 9, C0 + C1) or \
+            weight.dtype != torch.float16 or (src1 is not None and src1.shape[0] != N):
+        raise RuntimeError("lidarnerf.unet_train.conv3x3_raw: shapes of out / weight do not fit the sources")
+    _hip.require_cuda(weight)
+    _hip.require_symbols(_SYMBOLS, "U-Net training")
+    _hip.call("lnh_unet_conv3x3_raw", _hip.ptr(src0), C0, H0, W0, int(bool(pool)), _hip.ptr(src1), C1, H1, W1, _hip.ptr(weight), N, Cout,
+              int(tile), _hip.ptr(out))
+    return out
+
+
+def bn_partials(M):
+    """(P, parts): the pixels per partial of bn_stats / bn_relu_backward and their number, from the shape alone."""
+    P = 256 * ((M + (1 << 14) - 1) >> 14)
+    return P, (M + P - 1) // P
+
+
+def bn_stats_workspace_bytes(M, C):
+    """Bytes of bn_stats' (and bn_relu_backward's) workspace: 2 C float64 per partial.  Equals the C size functions."""
+    return bn_partials(M)[1] * 2 * C * 8
+
+
+bn_relu_backward_workspace_bytes = bn_stats_workspace_bytes
+
+
+def _vec(t, C, what, where):
+    if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.numel() == C and t.is_contiguous()):
+        raise RuntimeError(f"lidarnerf.unet_train.{where}: {what} must be contiguous f32 [{C}]")
+    return t
+
+
+def _ws_bytes(ws, need, where):
+    _hip.require_cuda(ws)
+    have = ws.numel() * ws.element_size()
+    if have < need:
+        raise RuntimeError(f"lidarnerf.unet_train.{where}: the workspace holds {have} bytes, {need} needed")
+    return have
+
+
+def bn_stats(z, gamma, beta, eps, momentum, ws, mean, invstd, scale, shift, running_mean=None, running_var=None):
+    """lnh_unet_bn_stats: z fp16 [N, H, W, C] (M = N H W >= 2 values per channel) -> mean, invstd, scale = gamma invstd, shift = beta -
+    mean scale, all f32 [C], and the in-place update of running_mean / running_var (f32 [C]) where given."""
+    N, H, W, C = _nhwc(z, "z").shape
+    M = N * H * W
+    if M < 2:
+        raise ValueError("lidarnerf.unet_train.bn_stats: expected more than 1 value per channel when training")
+    for t, what in ((gamma, "gamma"), (beta, "beta"), (mean, "mean"), (invstd, "invstd"), (scale, "scale"), (shift, "shift")):
+        _vec(t, C, what, "bn_stats")
+    for t, what in ((running_mean, "running_mean"), (running_var, "running_var")):
+        if t is not None:
+            _vec(t, C, what, "bn_stats")
+    _hip.require_cuda(gamma, beta, mean, invstd, scale, shift, running_mean, running_var)
+    have = _ws_bytes(ws, bn_stats_workspace_bytes(M, C), "bn_stats")
+    _hip.require_symbols(_SYMBOLS, "U-Net training")
+    _hip.call("lnh_unet_bn_stats", _hip.ptr(z), M, C, _hip.ptr(gamma), _hip.ptr(beta), float(eps), float(momentum), _hip.ptr(ws), have,
+              _hip.ptr(mean), _hip.ptr(invstd), _hip.ptr(scale), _hip.ptr(shift), _hip.ptr(running_mean), _hip.ptr(running_var))
+    return mean, invstd, scale, shift
+
+
+def bn_relu(z, scale, shift, a):
+    """lnh_unet_bn_relu: a = fp16(max(fmaf(float(z), scale, shift), 0)), z / a fp16 [N, H, W, C], scale / shift f32 [C]."""
+    N, H, W, C = _nhwc(z, "z").shape
+    if tuple(_nhwc(a, "a").shape) != (N, H, W, C):
+        raise RuntimeError("lidarnerf.unet_train.bn_relu: z and a must have one shape")
+    _hip.require_cuda(_vec(scale, C, "scale", "bn_relu"), _vec(shift, C, "shift", "bn_relu"))
+    _hip.require_symbols(_SYMBOLS, "U-Net training")
+    _hip.call("lnh_unet_bn_relu", _hip.ptr(z), N * H * W, C, _hip.ptr(scale), _hip.ptr(shift), _hip.ptr(a))
+    return a
+
+
+def bn_relu_backward(z, a, da, mean, invstd, scale, ws, dz, dgamma, dbeta):
+    """lnh_unet_bn_relu_backward: from the layer's stored z and a, bn_stats' mean / invstd / scale and the cotangent da -> dgamma, dbeta
+    f32 [C] and dz fp16 [N, H, W, C] (dz may be da)."""
+    N, H, W, C = _nhwc(z, "z").shape
+    M = N * H * W
+    if M < 2:
+        raise ValueError("lidarnerf.unet_train.bn_relu_backward: expected more than 1 value per channel")
+    for t, what in ((a, "a"), (da, "da"), (dz, "dz")):
+        if tuple(_nhwc(t, what).shape) != (N, H, W, C):
+            raise RuntimeError("lidarnerf.unet_train.bn_relu_backward: z, a, da and dz must have one shape")
+    for t, what in ((mean, "mean"), (invstd, "invstd"), (scale, "scale"), (dgamma, "dgamma"), (dbeta, "dbeta")):
+        _vec(t, C, what, "bn_relu_backward")
+    _hip.require_cuda(mean, invstd, scale, dgamma, dbeta)
+    have = _ws_bytes(ws, bn_relu_backward_workspace_bytes(M, C), "bn_relu_backward")
+    _hip.require_symbols(_SYMBOLS, "U-Net training")
+    _hip.call("lnh_unet_bn_relu_backward", _hip.ptr(z), _hip.ptr(a), _hip.ptr(da), M, C, _hip.ptr(mean), _hip.ptr(invstd), _hip.ptr(scale),
+              _hip.ptr(ws), have, _hip.ptr(dz), _hip.ptr(dgamma), _hip.ptr(dbeta))
+    return dz, dgamma, dbeta
+
+
+# ---- the whole net in training mode ---------------------------------------------------------------------------------------------------
+def train_layers(n_channels=10):
+    """The 18 convolution layers in execution order, one dict each: `conv` / `bn` (state-dict prefixes), `src0`, `src1` (buffer names;
+    src1 None but for the concatenating layers), `pool`, `out` (the activation buffer), `level`, `cin` (C0 + C1 of the parameter) and
+    `cout`."""
+    def pair(prefix, src0, src1, pool, mid, out, level, cin):
+        c = CHANNELS[level]
+        return [dict(conv=f"{prefix}.0", bn=f"{prefix}.1", src0=src0, src1=src1, pool=pool, out=mid, level=level, cin=cin, cout=c),
+                dict(conv=f"{prefix}.3", bn=f"{prefix}.4", src0=mid, src1=None, pool=False, out=out, level=level, cin=c, cout=c)]
+    layers = pair("inc.double_conv", "input", None, False, "mid0", "x0", 0, n_channels)
+    for l in range(1, 5):
+        layers += pair(f"down{l}.maxpool_conv.1.double_conv", f"x{l - 1}", None, True, f"mid{l}", f"x{l}", l, CHANNELS[l - 1])
+    for i, l in enumerate((3, 2, 1, 0)):
+        layers += pair(f"up{i + 1}.conv.double_conv", f"x{l}", f"up{l}", False, f"dmid{l}", f"d{l}", l, 2 * CHANNELS[l])
+    return layers
+
+
+def train_workspace_layout(N, H, W, n_channels=10):
+    """([(name, byte offset, shape, dtype)], total bytes) of everything train_forward / train_backward touch, every buffer 256-byte
+    aligned: the inference layout of lidarnerf.unet.workspace_layout at its offsets, then
+      dmid{l}            the decoder's first activation, l = 0 .. 3 (inference reuses mid{l}; the backward needs both)
+      z{k}, g{k}         the raw convolution output of layer k = 0 .. 17 and the gradient buffer of its shape: da, then in place dz
+      dcat{l}, dpool{l}  the data gradient of a concatenating layer [N, h, w, 2 C] and of a pooling layer (the pooled tensor's)
+      stat{k}            f32 [6, C]: mean, invstd, scale, shift, dgamma, dbeta
+      wf{k}, wb{k}       the packed forward and (k >= 1) data-gradient weight images; uf{i}, ub{i}, hw: the transposed convolutions', the head's
+      dupw{i}, dupb{i}, dhw, dhb   f32 parameter gradients of the transposed convolutions and the head
+      ws_bn, ws_head, ws_up        the partials workspaces (each the largest any layer needs)
+      logits             f32 [N, 1, H, W]."""
+    sizes = _unet.level_sizes(H, W)
+    f16, f32, u8 = torch.float16, torch.float32, torch.uint8
+    bufs = [(name, shape, f16) for name, _, shape in _unet.workspace_layout(N, H, W)[0]]
+    bufs += [(f"dmid{l}", (N,) + sizes[l] + (CHANNELS[l],), f16) for l in range(4)]
+    layers = train_layers(n_channels)
+    for k, lay in enumerate(layers):
+        shape = (N,) + sizes[lay["level"]] + (lay["cout"],)
+        bufs += [(f"z{k}", shape, f16), (f"g{k}", shape, f16)]
+    for l in range(4):
+        bufs.append((f"dcat{l}", (N,) + sizes[l] + (2 * CHANNELS[l],), f16))
+    for l in range(1, 5):
+        bufs.append((f"dpool{l}", (N,) + sizes[l] + (CHANNELS[l - 1],), f16))
+    for k, lay in enumerate(layers):
+        bufs.append((f"stat{k}", (6, lay["cout"]), f32))
+    for k, lay in enumerate(layers):
+        cin = lay["cin"]
+        bufs.append((f"wf{k}", (lay["cout"], 9, 32 if cin <= 32 else cin), f16))
+        if k:
+            bufs.append((f"wb{k}", (cin, 9, lay["cout"]), f16))
+    for i in range(4):
+        cin = CHANNELS[4 - i]
+        bufs += [(f"uf{i}", (4, cin // 2, cin), f16), (f"ub{i}", (cin, 4, cin // 2), f16), (f"dupw{i}", (cin, cin // 2, 2, 2), f32),
+                 (f"dupb{i}", (cin // 2,), f32)]
+    bufs += [("hw", (64,), f16), ("dhw", (1, 64, 1, 1), f32), ("dhb", (1,), f32)]
+    ws_bn = max(bn_stats_workspace_bytes(N * sizes[lay["level"]][0] * sizes[lay["level"]][1], lay["cout"]) for lay in layers)
+    ws_up = max(upconv2x2_backward_weight_workspace_bytes(N, sizes[l + 1][0], sizes[l + 1][1], CHANNELS[l + 1], CHANNELS[l]) for l in range(4))
+    bufs += [("ws_bn", (ws_bn,), u8), ("ws_head", (head_backward_workspace_bytes(N, H, W),), u8), ("ws_up", (ws_up,), u8),
+             ("logits", (N, 1, H, W), f32)]
+    out, off = [], 0
+    for name, shape, dtype in bufs:
+        n = 1
+        for d in shape:
+            n *= d
+        out.append((name, off, shape, dtype))
+        off += (n * torch.empty(0, dtype=dtype).element_size() + 255) // 256 * 256
+    return out, off
+
+
+def _train_state(net, N, H, W, device):
+    key = (N, H, W, device.index, net.n_channels)
+    cache = net.__dict__.setdefault("_train_states", {})
+    st = cache.get(key)
+    if st is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("lidarnerf.unet_train: the workspace of a shape must exist before a call is captured (run it eagerly once)")
+        layout, total = train_workspace_layout(N, H, W, net.n_channels)
+        raw = torch.empty(total, dtype=torch.uint8, device=device)
+        views = {}
+        for name, off, shape, dtype in layout:
+            n = 1
+            for d in shape:
+                n *= d
+            views[name] = raw[off:off + n * torch.empty(0, dtype=dtype).element_size()].view(dtype).view(shape)
+        layers = train_layers(net.n_channels)
+        grads = {"outc.conv.weight": views["dhw"], "outc.conv.bias": views["dhb"]}
+        for k, lay in enumerate(layers):
+            s = views[f"stat{k}"]
+            lay.update(index=k, operand=(views[lay["src0"]], None if lay["src1"] is None else views[lay["src1"]]), z=views[f"z{k}"],
+                       a=views[lay["out"]], dz=views[f"g{k}"], mean=s[0], invstd=s[1], scale=s[2], shift=s[3], dgamma=s[4], dbeta=s[5])
+            grads[lay["bn"] + ".weight"], grads[lay["bn"] + ".bias"] = s[4], s[5]
+        for i in range(4):
+            grads[f"up{i + 1}.up.weight"], grads[f"up{i + 1}.up.bias"] = views[f"dupw{i}"], views[f"dupb{i}"]
+        st = cache[key] = {"key": key, "raw": raw, "views": views, "layers": layers, "grads": grads, "logits": views["logits"]}
+    return st
+
+
+def _live(t, what):
+    t = t.detach()
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+        raise RuntimeError(f"lidarnerf.unet_train: {what} must be a contiguous f32 GPU tensor (the live parameter is read on the device)")
+    return t
+
+
+def train_forward(net, images, state=None):
+    """The forward of the net in training mode (BatchNorm on the batch's statistics), whatever mode `net` is in: images f32
+    [N, n_channels, H, W] on the GPU -> (logits f32 [N, 1, H, W], state).  `net` is a lidarnerf.unet.RayDropUNet; its fp32 parameters
+    are read live and packed on the device, its running_mean / running_var / num_batches_tracked are updated in place as torch's
+    BatchNorm2d does, and its cached inference pack is dropped (the next inference call packs again, from the new statistics).
+    The chain: input pack; per layer pack_conv3x3 -> conv3x3_raw -> bn_stats -> bn_relu; lidarnerf.unet's upconv2x2 and head.
+
+    `state` (None: the net's cached state of this shape, made at the first call) owns every buffer — train_workspace_layout — and
+    the returned logits: the next call of the shape overwrites them.  After the first call of a shape nothing is allocated and
+    nothing waits for the device; a call can be captured in a graph."""
+    if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] != net.n_channels:
+        raise ValueError(f"lidarnerf.unet_train.train_forward: images must be [N, {net.n_channels}, H, W]")
+    N, _, H, W = images.shape
+    if H < _unet.MIN_SIZE or W < _unet.MIN_SIZE or N < 1:
+        raise ValueError(f"lidarnerf.unet_train.train_forward: images of {H} x {W}; H and W must be at least {_unet.MIN_SIZE}")
+    if not images.is_cuda:
+        raise RuntimeError("lidarnerf.unet_train.train_forward: images must live on the GPU (no CPU fallback)")
+    _hip.require_symbols(_unet._SYMBOLS + _SYMBOLS, "U-Net training")
+    if state is None:
+        state = _train_state(net, N, H, W, images.device)
+    elif state["key"] != (N, H, W, images.device.index, net.n_channels):
+        raise RuntimeError(f"lidarnerf.unet_train.train_forward: the state belongs to {state['key']}, not to these images")
+    v = state["views"]
+    _unet.unet_input(images.detach().to(torch.float32).contiguous(), v["input"])
+    counters = []
+    cur = None
+    for k, lay in enumerate(state["layers"]):
+        if lay["src1"] is not None:  # a decoder block begins: the transposed convolution of what came before
+            i = (k - 10) // 2
+            up = net.get_submodule(f"up{i + 1}.up")
+            pack_upconv(_live(up.weight, "up.weight"), v[f"uf{i}"], v[f"ub{i}"])
+            _unet.upconv2x2(cur, v[f"uf{i}"], _live(up.bias, "up.bias"), v[lay["src1"]])
+        conv, bn = net.get_submodule(lay["conv"]), net.get_submodule(lay["bn"])
+        if bn.momentum is None:
+            raise NotImplementedError("lidarnerf.unet_train.train_forward: BatchNorm with momentum=None (cumulative average)")
+        pack_conv3x3(_live(conv.weight, "conv.weight"), v[f"wf{k}"], v.get(f"wb{k}"))
+        src0, src1 = lay["operand"]
+        conv3x3_raw(src0, v[f"wf{k}"], lay["z"], src1=src1, pool=lay["pool"])
+        bn_stats(lay["z"], _live(bn.weight, "bn.weight"), _live(bn.bias, "bn.bias"), bn.eps, bn.momentum, v["ws_bn"], lay["mean"],
+                 lay["invstd"], lay["scale"], lay["shift"], bn.running_mean, bn.running_var)
+        cur = bn_relu(lay["z"], lay["scale"], lay["shift"], lay["a"])
+        counters.append(bn.num_batches_tracked)
+    v["hw"].copy_(net.outc.conv.weight.detach().reshape(64))
+    _unet.head(cur, v["hw"], _live(net.outc.conv.bias, "outc.conv.bias"), state["logits"])
+    torch._foreach_add_(counters, 1)
+    net._packed = None  # (as load_state_dict: the inference images no longer match the buffers)
+    return state["logits"], state
+
+
+def train_backward(net, state, dlogits):
+    """The backward of train_forward's last call on `state` for the cotangent dlogits f32 [N, 1, H, W], used as given (loss scaling is
+    the caller's; everything here is linear in it): {state-dict name: f32 gradient} for the 36 BatchNorm weights / biases, the 8
+    transposed-convolution tensors and the 2 head tensors.  The weights of the 18 3 x 3 convolutions are ABSENT from the dict: their
+    gradient kernel does not exist yet; state["layers"][k] keeps what it will need — `operand` (src0, src1; `pool` says whether src0
+    is pooled on read) and `dz`.  The chain, in the order of the float64 restatement: head_backward; per layer bn_relu_backward and
+    the raw convolution on the flipped image; pool_backward with the skip gradient; upconv2x2_backward_weight / _data reading the
+    concatenating layer's gradient in place.  The returned tensors belong to `state`; nothing is allocated, nothing waits."""
+    v, layers = state["views"], state["layers"]
+    N, H, W = state["key"][:3]
+    if not (torch.is_tensor(dlogits) and dlogits.is_cuda and dlogits.dtype == torch.float32 and dlogits.is_contiguous() and
+            tuple(dlogits.shape) == (N, 1, H, W)):
+        raise RuntimeError(f"lidarnerf.unet_train.train_backward: dlogits must be a contiguous f32 [{N}, 1, {H}, {W}] GPU tensor")
+    grads = state["grads"]
+    head_backward(v["d0"], v["hw"], dlogits.detach(), v["ws_head"], v["g17"], grads["outc.conv.weight"], grads["outc.conv.bias"])
+
+    def layer_backward(k, dx):
+        lay = layers[k]
+        bn_relu_backward(lay["z"], lay["a"], lay["dz"], lay["mean"], lay["invstd"], lay["scale"], v["ws_bn"], lay["dz"], lay["dgamma"],
+                         lay["dbeta"])
+        if dx is not None:
+            conv3x3_raw(lay["dz"], v[f"wb{k}"], dx)
+
+    for i in (3, 2, 1, 0):  # up4 .. up1: level l = 3 - i
+        l, k = 3 - i, 10 + 2 * i
+        layer_backward(k + 1, v[f"g{k}"])
+        layer_backward(k, v[f"dcat{l}"])
+        x, dx = (v["x4"], v["g9"]) if i == 0 else (v[f"d{l + 1}"], v[f"g{k - 1}"])
+        upconv2x2_backward_weight(x, v[f"dcat{l}"], v["ws_up"], v[f"dupw{i}"], v[f"dupb{i}"], offset=CHANNELS[l])
+        upconv2x2_backward_data(v[f"dcat{l}"], v[f"ub{i}"], dx, offset=CHANNELS[l])
+    for l in (4, 3, 2, 1):  # down4 .. down1
+        layer_backward(2 * l + 1, v[f"g{2 * l}"])
+        layer_backward(2 * l, v[f"dpool{l}"])
+        pool_backward(v[f"x{l - 1}"], v[f"dpool{l}"], v[f"g{2 * l - 1}"], dskip=v[f"dcat{l - 1}"])
+    layer_backward(1, v["g0"])
+    layer_backward(0, None)
+    return grads

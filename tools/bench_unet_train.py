@@ -1,0 +1,136 @@
+#!/usr/bin/env python3
+"""Time of the ray-drop U-Net's training-mode forward (lidarnerf/unet_train.py: train_forward — weight pack, raw convolution, batch
+statistics, BatchNorm + ReLU per layer) on one 66 x 1030 frame at N = 1 against the same network from stock torch modules
+in train() mode, channels_last, under torch.autocast(fp16), autograd recording what its backward would need (as train_forward keeps
+z).  The method is tools/bench_unet.py's: the sides alternate window by window in one process, median and range over --rounds windows;
+device activities counted with torch.profiler in a pass of their own; per-launch times of the five new entry points from HIP events.
+
+train_backward is timed alone and has NO stock counterpart: it stops short of the 3 x 3 convolutions' weight gradient, which a stock
+backward cannot leave out, so a ratio would compare different work.
+
+    python tools/bench_unet_train.py [--rounds 7] [--window 0.3] [--out profiles/unet_train_bench.txt]
+
+The stock side's BatchNorm2d layers run torch's own batch-norm kernels (the MIOpen switch is off around them, and only them; the
+convolutions stay on MIOpen): with it on, this torch hands a channels_last training-mode batch norm to MIOpen, and the first such
+call ended the process with a segmentation fault on an MI355X under torch 2.10 / ROCm 7.0.  Progress is printed stage by stage.
+
+No GPU, no numbers: the tool refuses to run without one."""
+import argparse
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "lidar-nerf_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+import torch  # noqa: E402
+
+import bench_unet as B  # noqa: E402
+
+NEW = ("lnh_unet_pack_conv3x3", "lnh_unet_conv3x3_raw", "lnh_unet_bn_stats", "lnh_unet_bn_relu", "lnh_unet_bn_relu_backward")
+
+
+def say(what):
+    print(f"[bench_unet_train] {what}", flush=True)
+
+
+def native_batch_norm(stock):
+    """BatchNorm2d.forward of every layer of `stock` with the MIOpen switch off (see the module docstring)."""
+    for m in stock.modules():
+        if isinstance(m, torch.nn.BatchNorm2d):
+            inner = m.forward
+
+            def forward(x, inner=inner):
+                with torch.backends.cudnn.flags(enabled=False):
+                    return inner(x)
+            m.forward = forward
+    return stock
+
+
+def per_launch(fn, lines, title, frames=10):
+    from lidarnerf import _hip
+    fn()
+    torch.cuda.synchronize()
+    _hip.enable_timers(list(NEW))
+    for _ in range(frames):
+        fn()
+    torch.cuda.synchronize()
+    t = _hip.disable_timers()
+    lines.append(f"  {title}, us per call (HIP events around each entry point, mean of {frames} frames; calls per frame; sum per frame):")
+    for name in NEW:
+        ev = t.get(name, [])
+        if not ev:
+            continue
+        per = len(ev) // frames
+        us = [e0.elapsed_time(e1) * 1e3 for e0, e1, _ in ev]
+        by_call = [statistics.mean(us[i::per]) for i in range(per)]
+        lines.append(f"      {name:<28s} {statistics.mean(us):8.1f}   x {per:2d}   = {sum(by_call):8.1f}   (per call: "
+                     + " ".join(f"{v:.0f}" for v in by_call) + ")")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--window", type=float, default=0.3)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_unet_train: no GPU — nothing is measured without one")
+    from lidarnerf import unet_train as ut
+    from lidarnerf.unet import RayDropUNet
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    stock = B.Stock().train()
+    net = RayDropUNet()
+    net.load_state_dict(stock.state_dict())
+    net = net.to(dev)
+    stock = native_batch_norm(stock.to(dev).to(memory_format=torch.channels_last)).prepare()
+    g = torch.Generator(device=dev).manual_seed(1)
+    x = torch.rand(1, 10, B.H, B.W, generator=g, device=dev) * 2 - 1
+    x[:, 1] = (x[:, 1] + 1) * 40
+    d = (torch.rand(1, 1, B.H, B.W, generator=g, device=dev) - 0.5) * 1024
+    lines = [f"ray-drop U-Net training: one {B.H} x {B.W} frame, N = 1 ({torch.cuda.get_device_name(0)})",
+             f"train_forward: live fp32 parameters packed on the device, raw convolution -> batch statistics -> BatchNorm + ReLU per layer; "
+             f"stock: torch modules in train() mode, channels_last, fp16 autocast, autograd recording, BatchNorm on torch's own kernels; us per frame, windows of >= "
+             f"{args.window} s ending in a synchronise, alternating, median of {args.rounds} rounds"]
+    say("first train_forward")
+    logits, state = ut.train_forward(net, x)
+    torch.cuda.synchronize()
+    say("first train_backward")
+    ut.train_backward(net, state, d)
+    torch.cuda.synchronize()
+    say("first stock forward")
+    ref = stock(x).detach().float()
+    torch.cuda.synchronize()
+    say("timing")
+    lines.append(f"same parameters: logits differ by at most {float((logits - ref).abs().max()):.3g} (standard deviation "
+                 f"of the logits {float(logits.std()):.3g})")
+    sides = {"train_forward": lambda: ut.train_forward(net, x), "stock modules, train(), autocast": lambda: stock(x)}
+    times, counts = B.alternate(sides, args)
+    for k, v in times.items():
+        lines.append(f"  {k:<44s} {statistics.median(v):9.1f} us   (min {min(v):.1f} ... max {max(v):.1f}; ~{counts[k]} calls per window)")
+    fa, st = times["train_forward"], times["stock modules, train(), autocast"]
+    wins = sum(p < q for p, q in zip(fa, st))
+    lines.append(f"  train_forward faster in {wins} of {len(fa)} windows; medians {statistics.median(st) / statistics.median(fa):.2f} x apart")
+    times, counts = B.alternate({"train_backward (no 3 x 3 weight gradient)": lambda: ut.train_backward(net, state, d)}, args)
+    for k, v in times.items():
+        lines.append(f"  {k:<44s} {statistics.median(v):9.1f} us   (min {min(v):.1f} ... max {max(v):.1f}; ~{counts[k]} calls per window)"
+                     "   — alone: no fair stock counterpart without the weight gradient")
+    say("device activities")
+    B.activities(lambda: ut.train_forward(net, x), 10, lines, "train_forward")
+    B.activities(lambda: stock(x), 10, lines, "stock")
+    B.activities(lambda: ut.train_backward(net, state, d), 10, lines, "train_backward")
+    say("per-launch times")
+    per_launch(lambda: ut.train_forward(net, x), lines, "train_forward")
+    per_launch(lambda: ut.train_backward(net, state, d), lines, "train_backward")
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
