@@ -934,10 +934,11 @@ LNH_API int lnh_unet_upconv2x2(const void *in, uint32_t N, uint32_t H, uint32_t 
 LNH_API int lnh_unet_head(const void *in, uint32_t N, uint32_t H, uint32_t W, const void *weight, const float *bias,
                           float *logits, float *mask, lnh_stream_t stream);
 
-/* ---- U-Net training (README f12) — csrc/unet_train.hip, csrc/unet_train_conv.hip (and the RAW epilogue of csrc/unet.hip).
+/* ---- U-Net training (README f12) — csrc/unet_train.hip, csrc/unet_train_conv.hip, csrc/unet_train_wgrad.hip (and
+ * the RAW epilogue of csrc/unet.hip).
  * The max-pool and head backward, the transposed convolution's weight pack, data gradient and weight / bias gradient, and the
- * training-mode convolution layer without its weight gradient: weight pack, raw convolution (forward and data gradient), batch
- * statistics, BatchNorm + ReLU and their backward.
+ * training-mode convolution layer: weight pack, raw convolution (forward and data gradient), batch statistics, BatchNorm + ReLU
+ * and their backward, the weight gradient.
  * Activations and activation gradients: fp16 NHWC, rounded once per tensor; parameter gradients f32.  No float atomics: a sum that
  * is split goes to a workspace as partials and is added in a fixed order, so two calls give the same bits.  No call reads the host
  * or allocates.  N H W of any image at most 2^26.
@@ -1022,6 +1023,28 @@ LNH_API uint64_t lnh_unet_bn_relu_backward_workspace_size(uint64_t M, uint32_t C
 LNH_API int lnh_unet_bn_relu_backward(const void *z, const void *a, const void *da, uint64_t M, uint32_t C, const float *mean,
                                       const float *invstd, const float *scale, void *ws, uint64_t ws_bytes, void *dz,
                                       float *dgamma, float *dbeta, lnh_stream_t stream);
+/* The 3 x 3 convolution's weight gradient — csrc/unet_train_wgrad.hip.
+ * lnh_unet_conv3x3_backward_weight: dweight f32 [Cout, Cin, 3, 3] (the parameter's layout; overwritten) with dweight[co, ci, t] =
+ *   sum over the M = N H W output pixels p of dz[p, co] X[p + off(t), ci], t the forward tap (fwd[co, t, ci]).  X is the operand
+ *   lnh_unet_conv3x3 read, formed on read and never stored: src0 [N, H0, W0, C0] fp16, max-pooled 2 x 2 with pool = 1 (floor), then
+ *   the channels of src1 [N, H1, W1, C1] fp16 (zero for y >= H1 or x >= W1; H - H1, W - W1 each 0 or 1); a tap outside the image is
+ *   zero.  dz [N, H, W, Cout] fp16.  C1 = 0 or C1 = C0; C0 = 32 (the padded first layer, C1 = 0, Cin = 1 .. 32 real channels: channels
+ *   Cin .. 31 are not written) or a multiple of 64 up to 1024 (Cin = C0 + C1); Cout a multiple of 64 up to 1024; every pointer
+ *   16-byte aligned.  fp32 sums on the MFMA, no float atomics.  The pixel range is cut into
+ *   S = min(ceil(M / 256), max(1, floor(32 MiB / (36 (C0 + C1) Cout)))) slices of L = ceil(M / S) rounded up to 32 pixels (then
+ *   S = ceil(M / L)); within a slice the sums run over steps of 32 pixels in ascending order; the slices go to ws as
+ *   [S][9][Cout][C0 + C1] f32 and are added in ascending order in float64, rounded once.  variant: how the MFMA operands leave the
+ *   LDS — 0 = the default (LNH_UNET_WGRAD_TR), LNH_UNET_WGRAD_GATHER = 16-bit reads, LNH_UNET_WGRAD_TR = ds_read_b64_tr_b16; the
+ *   two give the same bits.  ws: lnh_unet_conv3x3_backward_weight_workspace_size(N, H0, W0, pool, C0, C1, Cout) = S x 36 (C0 + C1)
+ *   Cout bytes (0: refused shape).  Same shape, same bits; a non-finite dz makes the 9 Cin entries of its co non-finite, no others. */
+#define LNH_UNET_WGRAD_GATHER 1u
+#define LNH_UNET_WGRAD_TR 2u
+LNH_API uint64_t lnh_unet_conv3x3_backward_weight_workspace_size(uint32_t N, uint32_t H0, uint32_t W0, uint32_t pool, uint32_t C0,
+                                                                 uint32_t C1, uint32_t Cout);
+LNH_API int lnh_unet_conv3x3_backward_weight(const void *src0, uint32_t C0, uint32_t H0, uint32_t W0, uint32_t pool,
+                                             const void *src1, uint32_t C1, uint32_t H1, uint32_t W1, const void *dz, uint32_t N,
+                                             uint32_t Cout, uint32_t Cin, uint32_t variant, void *ws, uint64_t ws_bytes,
+                                             float *dweight, lnh_stream_t stream);
 
 /* ---- evaluation: nearest-neighbour pass of the chamfer distance (extern/chamfer3D/chamfer3D.cu:9-138)
  * dist[j] = min_k |xyz1[j] - xyz2[k]|^2 (squared), idx[j] = the first k attaining it; xyz* are [n,3] / [m,3] f32.

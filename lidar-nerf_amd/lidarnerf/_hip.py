@@ -103,6 +103,7 @@ _SIGS = {
     "lnh_unet_bn_stats": [P, C.c_uint64, U32, P, P, C.c_double, C.c_double, P, C.c_uint64, P, P, P, P, P, P],
     "lnh_unet_bn_relu": [P, C.c_uint64, U32, P, P, P],
     "lnh_unet_bn_relu_backward": [P, P, P, C.c_uint64, U32, P, P, P, P, C.c_uint64, P, P, P],
+    "lnh_unet_conv3x3_backward_weight": [P, U32, U32, U32, U32, P, U32, U32, U32, P, U32, U32, U32, U32, P, C.c_uint64, P],
     "lnh_chamfer_nn": [P, U32, P, U32, P, P],
     "lnh_grad_check_f16": [P, C.c_uint64, P],
     "lnh_adam_table_step": [P, P, P, P, P, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double, P, P, P, P],
@@ -168,7 +169,9 @@ _OPTIONAL = {"lnh_lidar_eval_frame": "frame evaluation", "lnh_lidar_eval_ssim": 
              "lnh_unet_upconv2x2_backward_weight_workspace_size": "U-Net training",
              "lnh_unet_pack_conv3x3": "U-Net training", "lnh_unet_conv3x3_raw": "U-Net training", "lnh_unet_bn_stats": "U-Net training",
              "lnh_unet_bn_relu": "U-Net training", "lnh_unet_bn_relu_backward": "U-Net training",
-             "lnh_unet_bn_stats_workspace_size": "U-Net training", "lnh_unet_bn_relu_backward_workspace_size": "U-Net training"}
+             "lnh_unet_bn_stats_workspace_size": "U-Net training", "lnh_unet_bn_relu_backward_workspace_size": "U-Net training",
+             "lnh_unet_conv3x3_backward_weight": "U-Net training",
+             "lnh_unet_conv3x3_backward_weight_workspace_size": "U-Net training"}
 for _n in ("lnh_mlp_forward", "lnh_mlp_backward", "lnh_mlp_backward_data", "lnh_mlp_wgrad", "lnh_density_mlp_forward", "lnh_density_mlp_backward",
            "lnh_lidar_dir_term", "lnh_lidar_pack_weights", "lnh_lidar_step_prologue", "lnh_lidar_color_forward", "lnh_lidar_color_backward",
            "lnh_lidar_color_composite_forward", "lnh_lidar_color_backward_image", "lnh_lidar_dir_term_freq",
@@ -186,12 +189,15 @@ EXPORTS = sorted(list(_SIGS) + ["lnh_version", "lnh_last_error", "lnh_arch", "ln
                                  "lnh_knn_workspace_size", "lnh_raydrop_workspace_size", "lnh_raydrop_param_count",
                                  "lnh_unet_workspace_size", "lnh_unet_head_backward_workspace_size",
                                  "lnh_unet_upconv2x2_backward_weight_workspace_size", "lnh_unet_bn_stats_workspace_size",
-                                 "lnh_unet_bn_relu_backward_workspace_size"])
+                                 "lnh_unet_bn_relu_backward_workspace_size",
+                                 "lnh_unet_conv3x3_backward_weight_workspace_size"])
 
 LNH_F32, LNH_F16 = 0, 1
 LNH_BWD_WS_CLEARED, LNH_BWD_TABLE_ZERO = 1, 2
 # lnh_unet_conv3x3's tile argument (include/lidarnerf_hip.h, LNH_UNET_TILE_*); 0 = chosen from the shape
 UNET_TILE_16, UNET_TILE_32, UNET_TILE_64, UNET_TILE_KSPLIT = 1, 2, 4, 8
+# lnh_unet_conv3x3_backward_weight's variant argument (LNH_UNET_WGRAD_*); 0 = the default
+UNET_WGRAD_GATHER, UNET_WGRAD_TR = 1, 2
 
 _lib = None
 
@@ -265,6 +271,9 @@ def lib():
         for name in ("lnh_unet_bn_stats_workspace_size", "lnh_unet_bn_relu_backward_workspace_size"):
             if hasattr(L, name):
                 getattr(L, name).argtypes, getattr(L, name).restype = [C.c_uint64, U32], C.c_uint64
+        if hasattr(L, "lnh_unet_conv3x3_backward_weight_workspace_size"):
+            L.lnh_unet_conv3x3_backward_weight_workspace_size.argtypes = [U32] * 7
+            L.lnh_unet_conv3x3_backward_weight_workspace_size.restype = C.c_uint64
         L.lnh_last_error.restype = C.c_char_p
         L.lnh_arch.restype = C.c_char_p
         L.lnh_build_variant.restype = C.c_char_p

@@ -5,15 +5,14 @@
   backward with the skip add, the backward of the 1 x 1 head, the transposed convolution's weight pack, data gradient and weight / bias
   gradient.  One entry point each; they read no host memory and allocate nothing — the caller owns every buffer.  No CPU fallback.
 
-* The training-mode convolution layer without its weight gradient (csrc/unet_train_conv.hip and the RAW epilogue of csrc/unet.hip):
+* The training-mode convolution layer (csrc/unet_train_conv.hip, csrc/unet_train_wgrad.hip and the RAW epilogue of csrc/unet.hip):
   pack_conv3x3, conv3x3_raw (the forward convolution and, on the flipped and transposed image, the data gradient), bn_stats, bn_relu,
-  bn_relu_backward.
+  bn_relu_backward, conv3x3_backward_weight.
 * train_forward / train_backward: the whole net in training mode on a RayDropUNet's live parameters, and the gradient of the loss with
-  respect to every activation, every BatchNorm weight / bias, the four transposed convolutions and the head (46 of the 64 parameter
-  tensors), in one workspace that is allocated once per shape.
+  respect to every activation and — with conv_weights=True — all 64 parameter tensors (without it the 46 that are no 3 x 3
+  convolution weight), in one workspace that is allocated once per shape.
 
-Still missing: the 3 x 3 convolution's weight gradient, the optimizer step and the module around them; RayDropUNet keeps refusing
-training mode."""
+Still missing: the optimizer step and the module around them; RayDropUNet keeps refusing training mode."""
 import torch
 import torch.nn.functional as F
 
@@ -24,7 +23,8 @@ from .unet import CHANNELS, _nhwc
 _SYMBOLS = ("lnh_unet_pool_backward", "lnh_unet_head_backward", "lnh_unet_head_backward_workspace_size", "lnh_unet_pack_upconv",
             "lnh_unet_upconv2x2_backward_data", "lnh_unet_upconv2x2_backward_weight", "lnh_unet_upconv2x2_backward_weight_workspace_size",
             "lnh_unet_pack_conv3x3", "lnh_unet_conv3x3_raw", "lnh_unet_bn_stats", "lnh_unet_bn_stats_workspace_size", "lnh_unet_bn_relu",
-            "lnh_unet_bn_relu_backward", "lnh_unet_bn_relu_backward_workspace_size")
+            "lnh_unet_bn_relu_backward", "lnh_unet_bn_relu_backward_workspace_size", "lnh_unet_conv3x3_backward_weight",
+            "lnh_unet_conv3x3_backward_weight_workspace_size")
 
 
 # ---- loss and validation score ------------------------------------------------------------------------------------------------------
@@ -295,6 +295,52 @@ def bn_relu_backward(z, a, da, mean, invstd, scale, ws, dz, dgamma, dbeta):
     return dz, dgamma, dbeta
 
 
+def conv_wgrad_slices(M, Cp, Cout):
+    """(S, L): the slices conv3x3_backward_weight cuts M output pixels into and the pixels per slice, from the shape alone (Cp = C0 +
+    C1 as stored: 32 for the first layer)."""
+    S = min((M + 255) // 256, max(1, (32 << 20) // (36 * Cp * Cout)))
+    L = ((M + S - 1) // S + 31) // 32 * 32
+    return (M + L - 1) // L, L
+
+
+def conv3x3_backward_weight_workspace_bytes(N, H0, W0, pool, C0, C1, Cout):
+    """Bytes of conv3x3_backward_weight's workspace: S slices of [9, Cout, C0 + C1] f32; 0 for a shape the kernel refuses.  Equals
+    lnh_unet_conv3x3_backward_weight_workspace_size."""
+    H, W = (H0 // 2, W0 // 2) if pool else (H0, W0)
+    c_ok = (C0 == 32 and C1 == 0) or (64 <= C0 <= 1024 and C0 % 64 == 0 and C1 in (0, C0))
+    if not (pool in (0, 1, False, True) and N >= 1 and H >= 1 and W >= 1 and N * H0 * W0 <= 1 << 26 and c_ok and
+            64 <= Cout <= 1024 and Cout % 64 == 0):
+        return 0
+    return conv_wgrad_slices(N * H * W, C0 + C1, Cout)[0] * 36 * (C0 + C1) * Cout
+
+
+def conv3x3_backward_weight(src0, dz, ws, dweight, src1=None, pool=False, variant=0):
+    """lnh_unet_conv3x3_backward_weight: dweight f32 [Cout, Cin, 3, 3] (the parameter's layout, overwritten) = the gradient of the
+    layer's weight for dz fp16 [N, H, W, Cout], from the operand the forward convolution read: src0 fp16 [N, H0, W0, C0] (pooled 2 x 2
+    on read with pool), then the channels of src1 fp16 [N, H1, W1, C1].  Cin = C0 + C1, or the real channel count (up to 32) of the
+    padded first layer.  variant: 0, _hip.UNET_WGRAD_GATHER or _hip.UNET_WGRAD_TR (the same bits)."""
+    N, H0, W0, C0 = _nhwc(src0, "src0").shape
+    H1 = W1 = C1 = 0
+    if src1 is not None:
+        _, H1, W1, C1 = _nhwc(src1, "src1").shape
+    H, W = (H0 // 2, W0 // 2) if pool else (H0, W0)
+    Cout = _nhwc(dz, "dz").shape[3]
+    if not (torch.is_tensor(dweight) and dweight.dtype == torch.float32 and dweight.dim() == 4 and dweight.is_contiguous() and
+            dweight.shape[0] == Cout and tuple(dweight.shape[2:]) == (3, 3)) or tuple(dz.shape[:3]) != (N, H, W) or \
+            (src1 is not None and src1.shape[0] != N):
+        raise RuntimeError("lidarnerf.unet_train.conv3x3_backward_weight: dweight contiguous f32 [Cout, Cin, 3, 3], dz [N, H, W, Cout] "
+                           "over the sources' batch and output size")
+    _hip.require_cuda(ws, dweight)
+    have = ws.numel() * ws.element_size()
+    need = conv3x3_backward_weight_workspace_bytes(N, H0, W0, pool, C0, C1, Cout)
+    if need and have < need:
+        raise RuntimeError(f"lidarnerf.unet_train.conv3x3_backward_weight: the workspace holds {have} bytes, {need} needed")
+    _hip.require_symbols(_SYMBOLS, "U-Net training")
+    _hip.call("lnh_unet_conv3x3_backward_weight", _hip.ptr(src0), C0, H0, W0, int(bool(pool)), _hip.ptr(src1), C1, H1, W1, _hip.ptr(dz), N,
+              Cout, dweight.shape[1], int(variant), _hip.ptr(ws), have, _hip.ptr(dweight))
+    return dweight
+
+
 # ---- the whole net in training mode ---------------------------------------------------------------------------------------------------
 def train_layers(n_channels=10):
     """The 18 convolution layers in execution order, one dict each: `conv` / `bn` (state-dict prefixes), `src0`, `src1` (buffer names;
@@ -322,7 +368,9 @@ def train_workspace_layout(N, H, W, n_channels=10):
       wf{k}, wb{k}       the packed forward and (k >= 1) data-gradient weight images; uf{i}, ub{i}, hw: the transposed convolutions', the head's
       dupw{i}, dupb{i}, dhw, dhb   f32 parameter gradients of the transposed convolutions and the head
       ws_bn, ws_head, ws_up        the partials workspaces (each the largest any layer needs)
-      logits             f32 [N, 1, H, W]."""
+      logits             f32 [N, 1, H, W]
+      dcw{k}             f32 [Cout, Cin, 3, 3]: the weight gradient of convolution k, the parameter's shape
+      ws_cw              conv3x3_backward_weight's partials, as large as the largest layer needs."""
     sizes = _unet.level_sizes(H, W)
     f16, f32, u8 = torch.float16, torch.float32, torch.uint8
     bufs = [(name, shape, f16) for name, _, shape in _unet.workspace_layout(N, H, W)[0]]
@@ -351,6 +399,8 @@ def train_workspace_layout(N, H, W, n_channels=10):
     ws_up = max(upconv2x2_backward_weight_workspace_bytes(N, sizes[l + 1][0], sizes[l + 1][1], CHANNELS[l + 1], CHANNELS[l]) for l in range(4))
     bufs += [("ws_bn", (ws_bn,), u8), ("ws_head", (head_backward_workspace_bytes(N, H, W),), u8), ("ws_up", (ws_up,), u8),
              ("logits", (N, 1, H, W), f32)]
+    bufs += [(f"dcw{k}", (lay["cout"], lay["cin"], 3, 3), f32) for k, lay in enumerate(layers)]
+    bufs.append(("ws_cw", (max(_conv_wgrad_bytes(N, sizes, lay) for lay in layers),), u8))
     out, off = [], 0
     for name, shape, dtype in bufs:
         n = 1
@@ -359,6 +409,14 @@ def train_workspace_layout(N, H, W, n_channels=10):
         out.append((name, off, shape, dtype))
         off += (n * torch.empty(0, dtype=dtype).element_size() + 255) // 256 * 256
     return out, off
+
+
+def _conv_wgrad_bytes(N, sizes, lay):
+    """The weight-gradient workspace of one entry of train_layers at level sizes `sizes`."""
+    l = lay["level"]
+    h0, w0 = sizes[l - 1] if lay["pool"] else sizes[l]
+    c0 = max(32, lay["cin"]) if lay["src1"] is None else lay["cin"] // 2
+    return conv3x3_backward_weight_workspace_bytes(N, h0, w0, lay["pool"], c0, lay["cin"] - c0 if lay["src1"] is not None else 0, lay["cout"])
 
 
 def _train_state(net, N, H, W, device):
@@ -378,14 +436,18 @@ def _train_state(net, N, H, W, device):
             views[name] = raw[off:off + n * torch.empty(0, dtype=dtype).element_size()].view(dtype).view(shape)
         layers = train_layers(net.n_channels)
         grads = {"outc.conv.weight": views["dhw"], "outc.conv.bias": views["dhb"]}
+        conv_grads = {}
         for k, lay in enumerate(layers):
+            conv_grads[lay["conv"] + ".weight"] = views[f"dcw{k}"]
             s = views[f"stat{k}"]
             lay.update(index=k, operand=(views[lay["src0"]], None if lay["src1"] is None else views[lay["src1"]]), z=views[f"z{k}"],
-                       a=views[lay["out"]], dz=views[f"g{k}"], mean=s[0], invstd=s[1], scale=s[2], shift=s[3], dgamma=s[4], dbeta=s[5])
+                       a=views[lay["out"]], dz=views[f"g{k}"], dweight=views[f"dcw{k}"], mean=s[0], invstd=s[1], scale=s[2], shift=s[3], dgamma=s[4], dbeta=s[5])
             grads[lay["bn"] + ".weight"], grads[lay["bn"] + ".bias"] = s[4], s[5]
         for i in range(4):
             grads[f"up{i + 1}.up.weight"], grads[f"up{i + 1}.up.bias"] = views[f"dupw{i}"], views[f"dupb{i}"]
-        st = cache[key] = {"key": key, "raw": raw, "views": views, "layers": layers, "grads": grads, "logits": views["logits"]}
+        # "grads": all 64 names; "grads_no_conv": the 46 a train_backward without the convolution weights fills and returns
+        st = cache[key] = {"key": key, "raw": raw, "views": views, "layers": layers, "grads": {**grads, **conv_grads},
+                           "grads_no_conv": grads, "logits": views["logits"]}
     return st
 
 
@@ -445,26 +507,30 @@ def train_forward(net, images, state=None):
     return state["logits"], state
 
 
-def train_backward(net, state, dlogits):
+def train_backward(net, state, dlogits, conv_weights=False):
     """The backward of train_forward's last call on `state` for the cotangent dlogits f32 [N, 1, H, W], used as given (loss scaling is
     the caller's; everything here is linear in it): {state-dict name: f32 gradient} for the 36 BatchNorm weights / biases, the 8
-    transposed-convolution tensors and the 2 head tensors.  The weights of the 18 3 x 3 convolutions are ABSENT from the dict: their
-    gradient kernel does not exist yet; state["layers"][k] keeps what it will need — `operand` (src0, src1; `pool` says whether src0
-    is pooled on read) and `dz`.  The chain, in the order of the float64 restatement: head_backward; per layer bn_relu_backward and
-    the raw convolution on the flipped image; pool_backward with the skip gradient; upconv2x2_backward_weight / _data reading the
-    concatenating layer's gradient in place.  The returned tensors belong to `state`; nothing is allocated, nothing waits."""
+    transposed-convolution tensors and the 2 head tensors.  Without conv_weights the weights of the 18 3 x 3 convolutions are ABSENT
+    from the dict and their kernel is not launched; with conv_weights=True each layer's conv3x3_backward_weight is launched once its
+    dz exists — from state["layers"][k]'s `operand` (src0, src1; `pool` says whether src0 is pooled on read) and `dz` — and the dict
+    holds all 64 names, the other 46 with the same bits.  The chain, in the order of the float64 restatement: head_backward; per
+    layer bn_relu_backward, the weight gradient and the raw convolution on the flipped image; pool_backward with the skip gradient;
+    upconv2x2_backward_weight / _data reading the concatenating layer's gradient in place.  The returned tensors belong to `state`;
+    nothing is allocated, nothing waits."""
     v, layers = state["views"], state["layers"]
     N, H, W = state["key"][:3]
     if not (torch.is_tensor(dlogits) and dlogits.is_cuda and dlogits.dtype == torch.float32 and dlogits.is_contiguous() and
             tuple(dlogits.shape) == (N, 1, H, W)):
         raise RuntimeError(f"lidarnerf.unet_train.train_backward: dlogits must be a contiguous f32 [{N}, 1, {H}, {W}] GPU tensor")
-    grads = state["grads"]
+    grads = state["grads"] if conv_weights else state["grads_no_conv"]
     head_backward(v["d0"], v["hw"], dlogits.detach(), v["ws_head"], v["g17"], grads["outc.conv.weight"], grads["outc.conv.bias"])
 
     def layer_backward(k, dx):
         lay = layers[k]
         bn_relu_backward(lay["z"], lay["a"], lay["dz"], lay["mean"], lay["invstd"], lay["scale"], v["ws_bn"], lay["dz"], lay["dgamma"],
                          lay["dbeta"])
+        if conv_weights:
+            conv3x3_backward_weight(lay["operand"][0], lay["dz"], v["ws_cw"], lay["dweight"], src1=lay["operand"][1], pool=lay["pool"])
         if dx is not None:
             conv3x3_raw(lay["dz"], v[f"wb{k}"], dx)
 

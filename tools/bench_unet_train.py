@@ -8,6 +8,11 @@ device activities counted with torch.profiler in a pass of their own; per-launch
 train_backward is timed alone and has NO stock counterpart: it stops short of the 3 x 3 convolutions' weight gradient, which a stock
 backward cannot leave out, so a ratio would compare different work.
 
+Since the 3 x 3 weight gradient (csrc/unet_train_wgrad.hip) the full backward — train_backward(conv_weights=True), all 64 gradients —
+has that counterpart: train_forward + full backward is timed against the stock modules' forward + backward() (same mode, static loss
+scale folded into the cotangent, gradients set to None between steps), and every layer's weight gradient is timed alone for each
+variant of the kernel (HIP events around the entry point, variants alternating, median of --rounds).
+
     python tools/bench_unet_train.py [--rounds 7] [--window 0.3] [--out profiles/unet_train_bench.txt]
 
 The stock side's BatchNorm2d layers run torch's own batch-norm kernels (the MIOpen switch is off around them, and only them; the
@@ -69,6 +74,35 @@ def per_launch(fn, lines, title, frames=10):
                      + " ".join(f"{v:.0f}" for v in by_call) + ")")
 
 
+def wgrad_per_layer(state, lines, rounds):
+    """us per call of conv3x3_backward_weight (both launches) for every layer and variant, on the operands the backward left behind."""
+    from lidarnerf import _hip, unet_train as ut
+    variants = (("16-bit gathers", _hip.UNET_WGRAD_GATHER), ("ds_read_b64_tr_b16", _hip.UNET_WGRAD_TR))
+    ws = state["views"]["ws_cw"]
+    lines.append(f"  conv3x3_backward_weight per layer, us (HIP events around the entry point, variants alternating, median of {rounds}):")
+    lines.append(f"      {'layer':<34s} {'pixels':>7s} " + " ".join(f"{name:>20s}" for name, _ in variants))
+    total = [0.0] * len(variants)
+    for lay in state["layers"]:
+        def run(variant):
+            ut.conv3x3_backward_weight(lay["operand"][0], lay["dz"], ws, lay["dweight"], src1=lay["operand"][1], pool=lay["pool"],
+                                       variant=variant)
+        us = [[] for _ in variants]
+        for r in range(rounds + 1):
+            for i, (_, variant) in enumerate(variants):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                run(variant)
+                e1.record()
+                torch.cuda.synchronize()
+                if r:  # (the first round warms up)
+                    us[i].append(e0.elapsed_time(e1) * 1e3)
+        med = [statistics.median(v) for v in us]
+        total = [a + b for a, b in zip(total, med)]
+        shape = f"{'pool ' if lay['pool'] else ''}{lay['cin']} -> {lay['cout']}" + (" (cat)" if lay["operand"][1] is not None else "")
+        lines.append(f"      L{lay['level']} {shape:<31s} {lay['dz'].numel() // lay['cout']:7d} " + " ".join(f"{m:20.1f}" for m in med))
+    lines.append(f"      {'sum of the 18 layers':<34s} {'':>7s} " + " ".join(f"{m:20.1f}" for m in total))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
@@ -124,6 +158,34 @@ def main():
     say("per-launch times")
     per_launch(lambda: ut.train_forward(net, x), lines, "train_forward")
     per_launch(lambda: ut.train_backward(net, state, d), lines, "train_backward")
+    say("full backward")
+    ut.train_backward(net, state, d, conv_weights=True)
+    torch.cuda.synchronize()
+    params = [p for p in stock.parameters()]
+
+    def stock_step():
+        for p in params:
+            p.grad = None
+        out = stock(x)
+        out.backward(d.to(out.dtype))
+
+    def device_step():
+        ut.train_backward(net, ut.train_forward(net, x)[1], d, conv_weights=True)
+
+    lines.append("full backward (all 64 gradients; the stock side: forward + backward() of the same modules, no optimizer on either side):")
+    times, counts = B.alternate({"train_backward, all 64 gradients": lambda: ut.train_backward(net, state, d, conv_weights=True),
+                                 "train_forward + full train_backward": device_step,
+                                 "stock forward + backward()": stock_step}, args)
+    for k, v in times.items():
+        lines.append(f"  {k:<44s} {statistics.median(v):9.1f} us   (min {min(v):.1f} ... max {max(v):.1f}; ~{counts[k]} calls per window)")
+    fa, st = times["train_forward + full train_backward"], times["stock forward + backward()"]
+    wins = sum(p < q for p, q in zip(fa, st))
+    lines.append(f"  device forward + full backward faster in {wins} of {len(fa)} windows; medians "
+                 f"{statistics.median(st) / statistics.median(fa):.2f} x apart (stock / device)")
+    B.activities(lambda: ut.train_backward(net, state, d, conv_weights=True), 10, lines, "train_backward, all 64 gradients")
+    B.activities(stock_step, 10, lines, "stock forward + backward()")
+    say("weight gradient per layer")
+    wgrad_per_layer(state, lines, args.rounds)
     text = "\n".join(lines)
     print(text)
     if args.out:
