@@ -1045,6 +1045,63 @@ LNH_API int lnh_unet_conv3x3_backward_weight(const void *src0, uint32_t C0, uint
                                              const void *src1, uint32_t C1, uint32_t H1, uint32_t W1, const void *dz, uint32_t N,
                                              uint32_t Cout, uint32_t Cin, uint32_t variant, void *ws, uint64_t ws_bytes,
                                              float *dweight, lnh_stream_t stream);
+/* The training step around forward and backward — csrc/unet_train_step.hip.  No float atomics, no host read, no allocation; every
+ * sum is taken in an order that depends on the sizes alone, so two calls give the same bits; capturable.
+ * lnh_unet_loss_grad: the loss of raydrop_train_poisson.py for the one-class net and its cotangent in closed form.  logits f32 [M]
+ *   (M = N H W, 1 .. 2^26), masks [M] holding 0 / 1 as f32 (LNH_UNET_MASK_F32) or uint8 (LNH_UNET_MASK_U8) ->
+ *   loss[0] f32 = mean BCE-with-logits + 1 - dice(sigmoid(x), t) over the whole batch (reduce_batch_first, epsilon e = 1e-6) and
+ *   dlogits f32 [M] = loss_scale dL/dx.  With s = sigmoid(x), I = sum s t, S = sum (s + t):
+ *   dL/dx_i = (s_i - t_i) / M - s_i (1 - s_i) (2 t_i (S + e) - (2 I + e)) / (S + e)^2, the dice part exactly 0 when S == 0 (then
+ *   dice = 1: dice_coeff's masked_fill).  BCE_i = max(x, 0) - x t + log1p(exp(-|x|)); s (1 - s) = exp(-|x|) / (1 + exp(-|x|))^2.
+ *   Every element is formed in float64 and rounded to f32 once.  Two launches: workgroup b owns elements [b E, (b + 1) E),
+ *   E = 256 ceil(M / 2^16), thread t adding the elements b E + t, + 256, .. in ascending order and the 256 threads by
+ *   block_sum's order, into float64 partials (BCE, I, S) in ws; then every workgroup re-sums the partials in ascending order and
+ *   writes its elements, workgroup 0 the loss.  ws: lnh_unet_loss_grad_workspace_size(M) = ceil(M / E) x 24 bytes (0: refused M).
+ * lnh_urs_tensor / the table: n_tensors (1 .. LNH_URS_MAX_TENSORS) records IN DEVICE MEMORY, one per parameter tensor.  The entry
+ *   points cannot read it, so its contents are the caller's to guarantee: valid 4-byte aligned pointers to numel f32 each
+ *   (momentum_buffer may be NULL only for momentum == 0), numel at most 2^40 per tensor (0 is allowed: the record is passed over)
+ *   and fewer than 2^32 chunks of 4096 elements in the whole table — chunk counts are kept in 32 bits and wrap beyond that.
+ * state: LNH_URS_SLOTS doubles in device memory (the slots below).
+ * lnh_unet_grad_sumsq: state[LNH_URS_SUMSQ] = the sum of grad^2 over all elements of all tensors of the table in float64, and
+ *   state[LNH_URS_NONFINITE] = 1 if that sum is not finite — i.e. if any element is inf or NaN: squares cannot cancel and cannot
+ *   overflow a float64 — else 0.  A tensor is cut into chunks of 4096 elements; workgroup b of 1024 takes chunks b, b + 1024, .. of
+ *   the table's chunk list in ascending order; within a chunk thread t owns elements 4 q .. 4 q + 3 for q = t, t + 256, t + 512,
+ *   t + 768, ascending (read as float4 where the tensor starts on 16 bytes, as scalars otherwise: the same order); the threads are
+ *   added by block_sum's order and the 1024 partials in ascending order.  ws: lnh_unet_grad_sumsq_workspace_size() = 8192 bytes.
+ * lnh_unet_rmsprop_step: clip_grad_norm_(max_norm) on the unscaled gradients + torch.optim.RMSprop(foreach=True) for every
+ *   tensor of the table in ONE launch, from state[LNH_URS_SUMSQ] / [LNH_URS_NONFINITE] (lnh_unet_grad_sumsq's) and the learning
+ *   rate state[LNH_URS_LR], read on the device.  norm = sqrt(sumsq) / loss_scale and coef = min(1, max_norm / (norm + 1e-6)) in
+ *   float64; then per element in fp32, every operation rounded on its own: g = grad (1 / loss_scale); g = g coef; g = g + wd p
+ *   (if wd != 0); sq = sq alpha; sq = sq + ((1 - alpha) g) g; avg = sqrt(sq) + eps; buf = buf momentum; buf = buf + g / avg;
+ *   p = p + (-lr) buf (momentum == 0: p = p + (-lr) (g / avg), momentum_buffer not touched).  Writes state[LNH_URS_NORM],
+ *   [LNH_URS_COEF] and adds 1 to [LNH_URS_STEP].  With state[LNH_URS_NONFINITE] != 0 the step is skipped as GradScaler.step skips
+ *   it: no tensor is written, [LNH_URS_SKIPPED] goes up by 1 and [LNH_URS_STEP] stays.  The gradients are never written. */
+#define LNH_UNET_MASK_F32 0u
+#define LNH_UNET_MASK_U8 1u
+#define LNH_URS_MAX_TENSORS 64
+#define LNH_URS_LR 0        /* learning rate: written by the caller (a scheduler), read by every step */
+#define LNH_URS_STEP 1      /* steps taken */
+#define LNH_URS_SKIPPED 2   /* steps skipped for a non-finite gradient */
+#define LNH_URS_SUMSQ 3     /* the last sum of squares of the (scaled) gradients */
+#define LNH_URS_NORM 4      /* the last total norm of the unscaled gradients */
+#define LNH_URS_COEF 5      /* the last clip coefficient, as the f32 every element was multiplied by */
+#define LNH_URS_NONFINITE 6 /* 1 if the last sum of squares was not finite */
+#define LNH_URS_SLOTS 8
+typedef struct lnh_urs_tensor {
+    float *param;
+    const float *grad;
+    float *square_avg;
+    float *momentum_buffer;
+    uint64_t numel;
+} lnh_urs_tensor;
+LNH_API uint64_t lnh_unet_loss_grad_workspace_size(uint64_t M);
+LNH_API int lnh_unet_loss_grad(const float *logits, const void *masks, uint32_t mask_dtype, uint64_t M, double loss_scale, void *ws,
+                               uint64_t ws_bytes, float *loss, float *dlogits, lnh_stream_t stream);
+LNH_API uint64_t lnh_unet_grad_sumsq_workspace_size(void);
+LNH_API int lnh_unet_grad_sumsq(const lnh_urs_tensor *table, uint32_t n_tensors, void *ws, uint64_t ws_bytes, double *state,
+                                lnh_stream_t stream);
+LNH_API int lnh_unet_rmsprop_step(const lnh_urs_tensor *table, uint32_t n_tensors, double *state, double loss_scale, double max_norm,
+                                  double alpha, double eps, double weight_decay, double momentum, lnh_stream_t stream);
 
 /* ---- evaluation: nearest-neighbour pass of the chamfer distance (extern/chamfer3D/chamfer3D.cu:9-138)
  * dist[j] = min_k |xyz1[j] - xyz2[k]|^2 (squared), idx[j] = the first k attaining it; xyz* are [n,3] / [m,3] f32.

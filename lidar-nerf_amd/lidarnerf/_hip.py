@@ -104,6 +104,9 @@ _SIGS = {
     "lnh_unet_bn_relu": [P, C.c_uint64, U32, P, P, P],
     "lnh_unet_bn_relu_backward": [P, P, P, C.c_uint64, U32, P, P, P, P, C.c_uint64, P, P, P],
     "lnh_unet_conv3x3_backward_weight": [P, U32, U32, U32, U32, P, U32, U32, U32, P, U32, U32, U32, U32, P, C.c_uint64, P],
+    "lnh_unet_loss_grad": [P, P, U32, C.c_uint64, C.c_double, P, C.c_uint64, P, P],
+    "lnh_unet_grad_sumsq": [P, U32, P, C.c_uint64, P],
+    "lnh_unet_rmsprop_step": [P, U32, P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double],
     "lnh_chamfer_nn": [P, U32, P, U32, P, P],
     "lnh_grad_check_f16": [P, C.c_uint64, P],
     "lnh_adam_table_step": [P, P, P, P, P, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double, P, P, P, P],
@@ -171,7 +174,10 @@ _OPTIONAL = {"lnh_lidar_eval_frame": "frame evaluation", "lnh_lidar_eval_ssim": 
              "lnh_unet_bn_relu": "U-Net training", "lnh_unet_bn_relu_backward": "U-Net training",
              "lnh_unet_bn_stats_workspace_size": "U-Net training", "lnh_unet_bn_relu_backward_workspace_size": "U-Net training",
              "lnh_unet_conv3x3_backward_weight": "U-Net training",
-             "lnh_unet_conv3x3_backward_weight_workspace_size": "U-Net training"}
+             "lnh_unet_conv3x3_backward_weight_workspace_size": "U-Net training",
+             "lnh_unet_loss_grad": "U-Net training", "lnh_unet_loss_grad_workspace_size": "U-Net training",
+             "lnh_unet_grad_sumsq": "U-Net training", "lnh_unet_grad_sumsq_workspace_size": "U-Net training",
+             "lnh_unet_rmsprop_step": "U-Net training"}
 for _n in ("lnh_mlp_forward", "lnh_mlp_backward", "lnh_mlp_backward_data", "lnh_mlp_wgrad", "lnh_density_mlp_forward", "lnh_density_mlp_backward",
            "lnh_lidar_dir_term", "lnh_lidar_pack_weights", "lnh_lidar_step_prologue", "lnh_lidar_color_forward", "lnh_lidar_color_backward",
            "lnh_lidar_color_composite_forward", "lnh_lidar_color_backward_image", "lnh_lidar_dir_term_freq",
@@ -190,7 +196,8 @@ EXPORTS = sorted(list(_SIGS) + ["lnh_version", "lnh_last_error", "lnh_arch", "ln
                                  "lnh_unet_workspace_size", "lnh_unet_head_backward_workspace_size",
                                  "lnh_unet_upconv2x2_backward_weight_workspace_size", "lnh_unet_bn_stats_workspace_size",
                                  "lnh_unet_bn_relu_backward_workspace_size",
-                                 "lnh_unet_conv3x3_backward_weight_workspace_size"])
+                                 "lnh_unet_conv3x3_backward_weight_workspace_size",
+                                 "lnh_unet_loss_grad_workspace_size", "lnh_unet_grad_sumsq_workspace_size"])
 
 LNH_F32, LNH_F16 = 0, 1
 LNH_BWD_WS_CLEARED, LNH_BWD_TABLE_ZERO = 1, 2
@@ -198,6 +205,10 @@ LNH_BWD_WS_CLEARED, LNH_BWD_TABLE_ZERO = 1, 2
 UNET_TILE_16, UNET_TILE_32, UNET_TILE_64, UNET_TILE_KSPLIT = 1, 2, 4, 8
 # lnh_unet_conv3x3_backward_weight's variant argument (LNH_UNET_WGRAD_*); 0 = the default
 UNET_WGRAD_GATHER, UNET_WGRAD_TR = 1, 2
+# lnh_unet_loss_grad's mask_dtype (LNH_UNET_MASK_*); the table and state of lnh_unet_grad_sumsq / lnh_unet_rmsprop_step (LNH_URS_*)
+UNET_MASK_F32, UNET_MASK_U8 = 0, 1
+URS_MAX_TENSORS, URS_TENSOR_WORDS, URS_SLOTS = 64, 5, 8  # a table record: param, grad, square_avg, momentum_buffer, numel (int64 each)
+URS_LR, URS_STEP, URS_SKIPPED, URS_SUMSQ, URS_NORM, URS_COEF, URS_NONFINITE = range(7)
 
 _lib = None
 
@@ -274,6 +285,10 @@ def lib():
         if hasattr(L, "lnh_unet_conv3x3_backward_weight_workspace_size"):
             L.lnh_unet_conv3x3_backward_weight_workspace_size.argtypes = [U32] * 7
             L.lnh_unet_conv3x3_backward_weight_workspace_size.restype = C.c_uint64
+        if hasattr(L, "lnh_unet_loss_grad_workspace_size"):
+            L.lnh_unet_loss_grad_workspace_size.argtypes, L.lnh_unet_loss_grad_workspace_size.restype = [C.c_uint64], C.c_uint64
+        if hasattr(L, "lnh_unet_grad_sumsq_workspace_size"):
+            L.lnh_unet_grad_sumsq_workspace_size.argtypes, L.lnh_unet_grad_sumsq_workspace_size.restype = [], C.c_uint64
         L.lnh_last_error.restype = C.c_char_p
         L.lnh_arch.restype = C.c_char_p
         L.lnh_build_variant.restype = C.c_char_p

@@ -12,7 +12,9 @@
   respect to every activation and — with conv_weights=True — all 64 parameter tensors (without it the 46 that are no 3 x 3
   convolution weight), in one workspace that is allocated once per shape.
 
-Still missing: the optimizer step and the module around them; RayDropUNet keeps refusing training mode."""
+* The step around them (csrc/unet_train_step.hip): raydrop_unet_loss_and_grad (the loss and its cotangent in closed form),
+  grad_sumsq and rmsprop_step over a device-resident table of tensors.  lidarnerf.unet_trainer.RayDropUNetTrainer owns a step;
+  RayDropUNet itself keeps refusing training mode."""
 import torch
 import torch.nn.functional as F
 
@@ -548,3 +550,98 @@ def train_backward(net, state, dlogits, conv_weights=False):
     layer_backward(1, v["g0"])
     layer_backward(0, None)
     return grads
+
+
+# ---- the step around forward and backward: loss cotangent, sum of squares, clip + RMSprop (csrc/unet_train_step.hip) -------------------
+def loss_grad_partials(M):
+    """(E, parts): the elements per workgroup of raydrop_unet_loss_and_grad and the number of float64 partials, from M alone."""
+    E = 256 * ((M + (1 << 16) - 1) >> 16)
+    return E, (M + E - 1) // E
+
+
+def loss_grad_workspace_bytes(M):
+    """Bytes of raydrop_unet_loss_and_grad's workspace: three float64 per partial; 0 for an M the kernel refuses.  Equals
+    lnh_unet_loss_grad_workspace_size."""
+    return loss_grad_partials(M)[1] * 24 if 1 <= M <= 1 << 26 else 0
+
+
+def raydrop_unet_loss_and_grad(logits, masks, dlogits, loss, ws, loss_scale=1.0):
+    """lnh_unet_loss_grad: raydrop_unet_loss and its gradient in closed form, no autograd.  logits f32 [N, 1, H, W] (any shape of M
+    elements), masks of M elements holding 0 / 1 as f32, uint8 or bool -> loss f32 [1] and dlogits f32 (M elements) = loss_scale
+    dL/dlogits.  Every element is formed in float64 from fixed-order float64 sums and rounded once."""
+    for t, what in ((logits, "logits"), (dlogits, "dlogits"), (loss, "loss")):
+        if not (torch.is_tensor(t) and t.dtype == torch.float32):
+            raise RuntimeError(f"lidarnerf.unet_train.raydrop_unet_loss_and_grad: {what} must be an f32 tensor")
+    M = logits.numel()
+    if not torch.is_tensor(masks) or masks.dtype not in (torch.float32, torch.uint8, torch.bool):
+        raise RuntimeError("lidarnerf.unet_train.raydrop_unet_loss_and_grad: masks must be f32, uint8 or bool")
+    if masks.numel() != M or dlogits.numel() != M or loss.numel() != 1:
+        raise RuntimeError(f"lidarnerf.unet_train.raydrop_unet_loss_and_grad: masks and dlogits must have the logits' {M} elements, loss one")
+    _hip.require_cuda(logits, masks, dlogits, loss, ws)
+    have = ws.numel() * ws.element_size()
+    _hip.require_symbols(_STEP_SYMBOLS, "U-Net training")
+    _hip.call("lnh_unet_loss_grad", _hip.ptr(logits.detach()), _hip.ptr(masks), _hip.UNET_MASK_F32 if masks.dtype == torch.float32 else
+              _hip.UNET_MASK_U8, M, float(loss_scale), _hip.ptr(ws), have, _hip.ptr(loss), _hip.ptr(dlogits))
+    return loss, dlogits
+
+
+_STEP_SYMBOLS = ("lnh_unet_loss_grad", "lnh_unet_loss_grad_workspace_size", "lnh_unet_grad_sumsq", "lnh_unet_grad_sumsq_workspace_size",
+                 "lnh_unet_rmsprop_step")
+GRAD_SUMSQ_BLOCKS = 1024
+
+
+def grad_sumsq_workspace_bytes():
+    """Bytes of grad_sumsq's workspace: one float64 per workgroup.  Equals lnh_unet_grad_sumsq_workspace_size."""
+    return GRAD_SUMSQ_BLOCKS * 8
+
+
+def step_table(params, grads, square_avgs, momentum_buffers=None):
+    """The device-resident table grad_sumsq and rmsprop_step read: int64 [n, 5] of (param, grad, square_avg, momentum_buffer
+    pointers, element count), one row per tensor (lnh_urs_tensor).  Contiguous f32 GPU tensors of equal sizes; the table holds
+    addresses only, the caller keeps the tensors alive.  momentum_buffers None: NULL pointers, for momentum = 0; the returned tensor
+    carries `has_momentum_buffers`, the host-side note by which rmsprop_step refuses momentum > 0 on such a table (the entry point
+    cannot see into a device-resident table)."""
+    n = len(params)
+    if not 1 <= n <= _hip.URS_MAX_TENSORS or len(grads) != n or len(square_avgs) != n or (momentum_buffers is not None and len(momentum_buffers) != n):
+        raise RuntimeError(f"lidarnerf.unet_train.step_table: 1 .. {_hip.URS_MAX_TENSORS} tensors, as many of each kind")
+    rows = []
+    for k in range(n):
+        group = [params[k], grads[k], square_avgs[k]] + ([] if momentum_buffers is None else [momentum_buffers[k]])
+        for t in group:
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == params[k].numel()):
+                raise RuntimeError(f"lidarnerf.unet_train.step_table: tensor {k}: contiguous f32 GPU tensors of one size")
+        rows.append([t.data_ptr() for t in group] + ([0] if momentum_buffers is None else []) + [params[k].numel()])
+    table = torch.tensor(rows, dtype=torch.int64, device=params[0].device)
+    table.has_momentum_buffers = momentum_buffers is not None
+    return table
+
+
+def _table_state(table, n_tensors, state, where):
+    if not (torch.is_tensor(table) and table.dtype == torch.int64 and table.is_contiguous() and table.numel() >= _hip.URS_TENSOR_WORDS * max(int(n_tensors), 0)):
+        raise RuntimeError(f"lidarnerf.unet_train.{where}: the table must be a contiguous int64 [n_tensors, {_hip.URS_TENSOR_WORDS}] tensor")
+    if not (torch.is_tensor(state) and state.dtype == torch.float64 and state.is_contiguous() and state.numel() >= _hip.URS_SLOTS):
+        raise RuntimeError(f"lidarnerf.unet_train.{where}: the state must be a contiguous float64 tensor of {_hip.URS_SLOTS} slots")
+    _hip.require_cuda(table, state)
+    _hip.require_symbols(_STEP_SYMBOLS, "U-Net training")
+
+
+def grad_sumsq(table, n_tensors, ws, state):
+    """lnh_unet_grad_sumsq: state[URS_SUMSQ] = the float64 sum of grad^2 over the table's tensors, state[URS_NONFINITE] = 1 if any
+    element is inf / NaN, else 0.  Fixed order, no float atomics."""
+    _table_state(table, n_tensors, state, "grad_sumsq")
+    _hip.require_cuda(ws)
+    _hip.call("lnh_unet_grad_sumsq", _hip.ptr(table), int(n_tensors), _hip.ptr(ws), ws.numel() * ws.element_size(), _hip.ptr(state))
+    return state
+
+
+def rmsprop_step(table, n_tensors, state, loss_scale=1.0, max_norm=float("inf"), alpha=0.99, eps=1e-8, weight_decay=0.0, momentum=0.0):
+    """lnh_unet_rmsprop_step: one launch for clip_grad_norm_(max_norm) on the gradients divided by loss_scale +
+    torch.optim.RMSprop(foreach=True) over every tensor of the table, from grad_sumsq's state; the learning rate is
+    state[URS_LR], read on the device.  A non-finite sum of squares skips the step: no tensor is written, state[URS_SKIPPED] += 1."""
+    if float(momentum) > 0 and not getattr(table, "has_momentum_buffers", False):
+        raise RuntimeError("lidarnerf.unet_train.rmsprop_step: momentum > 0 needs a table that step_table built with momentum_buffers "
+                           "(this one has none, or is not step_table's: the kernel would follow a NULL pointer)")
+    _table_state(table, n_tensors, state, "rmsprop_step")
+    _hip.call("lnh_unet_rmsprop_step", _hip.ptr(table), int(n_tensors), _hip.ptr(state), float(loss_scale), float(max_norm), float(alpha),
+              float(eps), float(weight_decay), float(momentum))
+    return state

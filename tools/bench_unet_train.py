@@ -13,6 +13,9 @@ has that counterpart: train_forward + full backward is timed against the stock m
 scale folded into the cotangent, gradients set to None between steps), and every layer's weight gradient is timed alone for each
 variant of the kernel (HIP events around the entry point, variants alternating, median of --rounds).
 
+The whole training step — RayDropUNetTrainer.train_step (lidarnerf/unet_trainer.py), eager and captured — is timed against the stock
+loop (whole_step below), with device activities, synchronising calls and per-launch times of the three kernels of csrc/unet_train_step.hip.
+
     python tools/bench_unet_train.py [--rounds 7] [--window 0.3] [--out profiles/unet_train_bench.txt]
 
 The stock side's BatchNorm2d layers run torch's own batch-norm kernels (the MIOpen switch is off around them, and only them; the
@@ -34,6 +37,8 @@ import torch  # noqa: E402
 import bench_unet as B  # noqa: E402
 
 NEW = ("lnh_unet_pack_conv3x3", "lnh_unet_conv3x3_raw", "lnh_unet_bn_stats", "lnh_unet_bn_relu", "lnh_unet_bn_relu_backward")
+STEP = ("lnh_unet_loss_grad", "lnh_unet_grad_sumsq", "lnh_unet_rmsprop_step")
+COPY_TBS = 6.29  # TB/s this card's copy kernels reach (MI355X): the yardstick of the optimizer pass
 
 
 def say(what):
@@ -53,17 +58,17 @@ def native_batch_norm(stock):
     return stock
 
 
-def per_launch(fn, lines, title, frames=10):
+def per_launch(fn, lines, title, frames=10, names=NEW):
     from lidarnerf import _hip
     fn()
     torch.cuda.synchronize()
-    _hip.enable_timers(list(NEW))
+    _hip.enable_timers(list(names))
     for _ in range(frames):
         fn()
     torch.cuda.synchronize()
     t = _hip.disable_timers()
     lines.append(f"  {title}, us per call (HIP events around each entry point, mean of {frames} frames; calls per frame; sum per frame):")
-    for name in NEW:
+    for name in names:
         ev = t.get(name, [])
         if not ev:
             continue
@@ -101,6 +106,68 @@ def wgrad_per_layer(state, lines, rounds):
         shape = f"{'pool ' if lay['pool'] else ''}{lay['cin']} -> {lay['cout']}" + (" (cat)" if lay["operand"][1] is not None else "")
         lines.append(f"      L{lay['level']} {shape:<31s} {lay['dz'].numel() // lay['cout']:7d} " + " ".join(f"{m:20.1f}" for m in med))
     lines.append(f"      {'sum of the 18 layers':<34s} {'':>7s} " + " ".join(f"{m:20.1f}" for m in total))
+
+
+def whole_step(net, stock, x, lines, args):
+    """RayDropUNetTrainer.train_step, eager and captured, against the stock loop: the stock modules in train() mode, channels_last,
+    fp16 autocast, the loss of lidarnerf.unet_train in torch ops, a static loss scale, clip_grad_norm_ and RMSprop(foreach=True), no
+    .item() anywhere.  Both sides run with lr = 0: the same kernels and the same traffic, and thousands of timed steps on one
+    random frame cannot drive either net into non-finite values (which the device side would answer with cheaper, skipped steps).
+    The eager and the captured trainer share one net, hence one cached training state and one set of gradient buffers (each has its
+    own optimizer state): harmless at lr = 0, where no parameter moves, and wrong for anything but timing.  The stock side unscales
+    with a _foreach_mul_ pass of its own, which GradScaler.unscale_ would fuse with its inf check; the comparison does not hang on
+    it (the stock forward + backward() alone take longer than the whole device step)."""
+    from lidarnerf import unet_train as ut
+    from lidarnerf.unet_trainer import RayDropUNetTrainer
+    masks = ((x[:, 1] < 50) & (x[:, 0] > -0.5)).float()
+    eager = RayDropUNetTrainer(net, lr=0.0, graph=False)
+    captured = RayDropUNetTrainer(net, lr=0.0, graph=True)
+    params = [p for p in stock.parameters()]
+    opt = torch.optim.RMSprop(params, lr=0.0, weight_decay=1e-8, momentum=0.999, foreach=True)
+
+    def stock_step():
+        opt.zero_grad(set_to_none=True)
+        loss = ut.raydrop_unet_loss(stock(x).float(), masks)
+        (loss * 1024.0).backward()
+        torch._foreach_mul_([p.grad for p in params], 1.0 / 1024.0)
+        torch.nn.utils.clip_grad_norm_(params, 1.0, foreach=True)
+        opt.step()
+        return loss
+
+    say("first whole steps")
+    for _ in range(2):  # the second call of the captured trainer captures
+        eager.train_step(x, masks)
+        captured.train_step(x, masks)
+    stock_step()
+    torch.cuda.synchronize()
+    say("timing whole steps")
+    lines.append("whole training step (forward, loss, full backward, unscale, clip, RMSprop; lr = 0 on every side; static scale 1024):")
+    sides = {"RayDropUNetTrainer.train_step, eager": lambda: eager.train_step(x, masks),
+             "RayDropUNetTrainer.train_step, captured": lambda: captured.train_step(x, masks),
+             "stock loop": stock_step}
+    times, counts = B.alternate(sides, args)
+    for k, v in times.items():
+        lines.append(f"  {k:<44s} {statistics.median(v):9.1f} us   (min {min(v):.1f} ... max {max(v):.1f}; ~{counts[k]} calls per window)")
+    st = times["stock loop"]
+    for k in list(sides)[:2]:
+        wins = sum(p < q for p, q in zip(times[k], st))
+        lines.append(f"  {k}: faster than the stock loop in {wins} of {len(st)} windows; medians "
+                     f"{statistics.median(st) / statistics.median(times[k]):.2f} x apart (stock / device)")
+    for k, fn in sides.items():
+        B.activities(fn, 10, lines, k)
+    per_launch(lambda: eager.train_step(x, masks), lines, "train_step", names=STEP)
+    n = sum(p.numel() for p in params)
+    ideal = 28 * n / (COPY_TBS * 1e12) * 1e6
+    from lidarnerf import _hip
+    _hip.enable_timers(["lnh_unet_rmsprop_step"])
+    for _ in range(10):
+        eager.train_step(x, masks)
+    torch.cuda.synchronize()
+    us = statistics.median(e0.elapsed_time(e1) * 1e3 for e0, e1, _ in _hip.disable_timers()["lnh_unet_rmsprop_step"])
+    lines.append(f"  rmsprop_step: 28 bytes x {n} parameters = {28 * n / 1e9:.3f} GB, {ideal:.0f} us at {COPY_TBS} TB/s; measured {us:.0f} us "
+                 f"(median of 10) = {ideal / us:.2f} of that rate")
+    steps = eager.steps, captured.steps
+    lines.append(f"  steps taken / skipped: eager {steps[0]}, captured {steps[1]}")
 
 
 def main():
@@ -186,6 +253,8 @@ def main():
     B.activities(stock_step, 10, lines, "stock forward + backward()")
     say("weight gradient per layer")
     wgrad_per_layer(state, lines, args.rounds)
+    say("whole step")
+    whole_step(net, stock, x, lines, args)
     text = "\n".join(lines)
     print(text)
     if args.out:
