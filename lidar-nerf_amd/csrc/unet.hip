@@ -7,30 +7,19 @@
 //                   consecutive channels of one NHWC pixel per lane) — both are one 16-byte global read per lane, so nothing is
 //                   staged in LDS and no im2col, pooled or concatenated tensor exists: the 2 x 2 maximum is taken over four such
 //                   reads, the second source is a second pointer, a tap outside the image (or the second source) is a zero
-//                   fragment.  A wave owns MT x 16 pixels (flat over N H W) x 64 output channels; a lane ends with 4 consecutive
+//                   fragment — the operand rule, written once in unet_common.h (UnetConvGeom) and read there by the weight
+//                   gradient too (unet_train_wgrad.hip); this kernel hoists the tap pointers out of its channel loop.  A wave owns MT x 16 pixels (flat over N H W) x 64 output channels; a lane ends with 4 consecutive
 //                   channels of one pixel per accumulator: one 8-byte store.  KS: the four waves of a workgroup take the channel
 //                   chunks c = w (mod 4) of every tap of ONE 16-pixel tile and add through LDS in a fixed order — the deep levels
 //                   (256 pixels, K = 9216) would otherwise fill a quarter of the machine.
 //   k_unet_upconv   the same product with k = Cin and rows (2dy + dx, co); every output pixel has one owner.
 //   k_unet_head     64 -> 1 per pixel, an fp32 fmaf chain, logits and the mask logit > 0.
-#include "common.h"
+// unet_common.h: ld8 / zero8 / max8, aligned16, the pixel bound and decomposition, the sources' geometry check, the channel-range message.
+#include "unet_common.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define UNET_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
-
-constexpr uint64_t kMaxPixels = 1ull << 26;
 constexpr uint32_t kLevels = 5;
-
-__device__ __forceinline__ half8_t ld8(const half_t *p) { return *reinterpret_cast<const half8_t *>(p); }
-__device__ __forceinline__ half8_t zero8() { return half8_t{0, 0, 0, 0, 0, 0, 0, 0}; }
-__device__ __forceinline__ half8_t max8(half8_t a, half8_t b) {
-    half8_t r;
-#pragma unroll
-    for (int i = 0; i < 8; i++) r[i] = a[i] > b[i] ? a[i] : b[i];
-    return r;
-}
 
 struct InputArgs {
     const float *in;
@@ -56,10 +45,11 @@ k_unet_input(InputArgs a) {
 }
 
 struct ConvArgs {
-    const half_t *s0, *s1, *w;
+    UnetConvGeom g;
+    const half_t *w;
     const float *scale, *shift;
     half_t *out;
-    uint32_t H, W, H0, W0, C0, H1, W1, C1, Cout, pool;
+    uint32_t Cout;
     uint64_t M;  // N H W
 };
 
@@ -74,8 +64,8 @@ k_unet_conv3x3(ConvArgs a) {
     const int c = lane & 15, g = lane >> 4;
     const uint64_t base = KS ? (uint64_t)blockIdx.x * 16 : ((uint64_t)blockIdx.x * 4 + wave) * (16 * MT);
     if (!KS && base >= a.M) return;  // (no barrier in this variant)
-    const uint32_t co0 = blockIdx.y * 64, Ct = a.C0 + a.C1;
-    const uint64_t HW = (uint64_t)a.H * a.W;
+    const UnetConvGeom &G = a.g;
+    const uint32_t co0 = blockIdx.y * 64, Ct = G.C0 + G.C1;
     bool valid[MT];
     uint32_t pn[MT];
     int py[MT], px[MT];
@@ -83,11 +73,8 @@ k_unet_conv3x3(ConvArgs a) {
     for (int m = 0; m < MT; m++) {
         const uint64_t p = base + m * 16 + c;
         valid[m] = p < a.M;
-        const uint64_t q = valid[m] ? p : 0;
-        pn[m] = (uint32_t)(q / HW);
-        const uint32_t yx = (uint32_t)(q % HW);
-        py[m] = (int)(yx / a.W);
-        px[m] = (int)(yx % a.W);
+        const UnetPixel q = unet_pixel(valid[m] ? p : 0, G.H, G.W);
+        pn[m] = q.n, py[m] = (int)q.y, px[m] = (int)q.x;
     }
     const half_t *wrow[4];
 #pragma unroll
@@ -98,7 +85,6 @@ k_unet_conv3x3(ConvArgs a) {
 #pragma unroll
         for (int t = 0; t < 4; t++) acc[m][t] = f32x4{0, 0, 0, 0};
     const uint32_t ch_first = KS ? wave * 32 : 0, ch_step = KS ? 128 : 32;
-    const uint64_t row0 = (uint64_t)a.W0 * a.C0;  // one source-0 row, in elements
 
     for (int tap = 0; tap < 9; tap++) {
         const int dy = tap / 3 - 1, dx = tap % 3 - 1;
@@ -107,41 +93,31 @@ k_unet_conv3x3(ConvArgs a) {
 #pragma unroll
         for (int m = 0; m < MT; m++) {
             const int yy = py[m] + dy, xx = px[m] + dx;
-            in0[m] = valid[m] && yy >= 0 && yy < (int)a.H && xx >= 0 && xx < (int)a.W;
-            in1[m] = in0[m] && a.C1 != 0 && yy < (int)a.H1 && xx < (int)a.W1;
-            const uint32_t sy = a.pool ? 2 * yy : yy, sx = a.pool ? 2 * xx : xx;  // (2 yy + 1 <= 2 H - 1 <= H0 - 1)
-            p0[m] = in0[m] ? a.s0 + (((uint64_t)pn[m] * a.H0 + sy) * a.W0 + sx) * a.C0 + 8 * g : a.s0;
-            p1[m] = in1[m] ? a.s1 + (((uint64_t)pn[m] * a.H1 + yy) * a.W1 + xx) * a.C1 + 8 * g : a.s0;
+            in0[m] = unet_tap_in0(G, valid[m], yy, xx);
+            in1[m] = unet_tap_in1(G, in0[m], yy, xx);
+            p0[m] = in0[m] ? unet_tap_src0(G, pn[m], yy, xx) + 8 * g : G.s0;
+            p1[m] = in1[m] ? unet_tap_src1(G, pn[m], yy, xx) + 8 * g : G.s0;
         }
         const uint32_t k0 = tap * Ct;
 #pragma unroll 2
-        for (uint32_t ch = ch_first; ch < a.C0; ch += ch_step) {
+        for (uint32_t ch = ch_first; ch < G.C0; ch += ch_step) {
             half8_t wf[4], xf[MT];
 #pragma unroll
             for (int t = 0; t < 4; t++) wf[t] = ld8(wrow[t] + k0 + ch);
 #pragma unroll
-            for (int m = 0; m < MT; m++) {
-                xf[m] = zero8();
-                if (in0[m]) {
-                    xf[m] = ld8(p0[m] + ch);
-                    if (a.pool) {
-                        xf[m] = max8(xf[m], ld8(p0[m] + ch + a.C0));
-                        xf[m] = max8(xf[m], max8(ld8(p0[m] + ch + row0), ld8(p0[m] + ch + row0 + a.C0)));
-                    }
-                }
-            }
+            for (int m = 0; m < MT; m++) xf[m] = in0[m] ? unet_ld8_src0(G, p0[m] + ch) : zero8();
 #pragma unroll
             for (int m = 0; m < MT; m++)
 #pragma unroll
                 for (int t = 0; t < 4; t++) acc[m][t] = UNET_MFMA(wf[t], xf[m], acc[m][t]);
         }
         // the second source continues the chunk count of the first, so the k-split stays balanced when C0 / 32 is no multiple of 4
-        const uint32_t first1 = KS ? ((wave + 4 - (a.C0 / 32) % 4) % 4) * 32 : 0;
+        const uint32_t first1 = KS ? ((wave + 4 - (G.C0 / 32) % 4) % 4) * 32 : 0;
 #pragma unroll 2
-        for (uint32_t ch = first1; ch < a.C1; ch += ch_step) {
+        for (uint32_t ch = first1; ch < G.C1; ch += ch_step) {
             half8_t wf[4], xf[MT];
 #pragma unroll
-            for (int t = 0; t < 4; t++) wf[t] = ld8(wrow[t] + k0 + a.C0 + ch);
+            for (int t = 0; t < 4; t++) wf[t] = ld8(wrow[t] + k0 + G.C0 + ch);
 #pragma unroll
             for (int m = 0; m < MT; m++) xf[m] = in1[m] ? ld8(p1[m] + ch) : zero8();
 #pragma unroll
@@ -217,10 +193,8 @@ k_unet_upconv(UpArgs a) {
         for (int t = 0; t < 4; t++) acc[t] = UNET_MFMA(wf[t], xf, acc[t]);
     }
     if (!valid) return;
-    const uint64_t HW = (uint64_t)a.H * a.W;
-    const uint64_t n = p / HW;
-    const uint32_t yx = (uint32_t)(p % HW), y = yx / a.W, xx = yx % a.W;
-    const uint64_t op = (n * (2 * a.H) + (2 * y + (q >> 1))) * (2 * (uint64_t)a.W) + (2 * xx + (q & 1));
+    const UnetPixel px = unet_pixel(p, a.H, a.W);
+    const uint64_t op = ((uint64_t)px.n * (2 * a.H) + (2 * px.y + (q >> 1))) * (2 * (uint64_t)a.W) + (2 * px.x + (q & 1));
 #pragma unroll
     for (int t = 0; t < 4; t++) {
         const uint32_t co = co0 + 16 * t + 4 * g;
@@ -255,8 +229,6 @@ k_unet_head(HeadArgs a) {
     if (a.mask) a.mask[p] = o > 0.0f ? 1.0f : 0.0f;  // false for NaN
 }
 
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 uint64_t pad256(uint64_t b) { return (b + 255) / 256 * 256; }
 
 // lnh_unet_conv3x3 and lnh_unet_conv3x3_raw: one set of checks, one tile rule, one main loop; RAW picks the epilogue.
@@ -266,28 +238,21 @@ int conv3x3_launch(const char *what, const void *src0, uint32_t C0, uint32_t H0,
                    uint32_t Cout, uint32_t tile, void *out, lnh_stream_t stream) {
     LNH_REQUIRE(src0 && weight && (RAW || (scale && shift)) && out, LNH_ERR_INVALID_ARG, "%s: null pointer", what);
     LNH_REQUIRE(pool <= 1, LNH_ERR_INVALID_ARG, "%s: pool %u (0 or 1)", what, pool);
-    LNH_REQUIRE(C0 >= 32 && C0 <= 1024 && C0 % 32 == 0, LNH_ERR_INVALID_ARG, "%s: C0 %u (a multiple of 32, 32 .. 1024)", what, C0);
+    UNET_REQUIRE_CHANNELS(what, "C0", C0, 32);
     LNH_REQUIRE(C1 <= 1024 && C1 % 32 == 0, LNH_ERR_INVALID_ARG, "%s: C1 %u (a multiple of 32 up to 1024)", what, C1);
     LNH_REQUIRE((C1 != 0) == (src1 != nullptr), LNH_ERR_INVALID_ARG, "%s: src1 and C1 must be given together", what);
-    LNH_REQUIRE(Cout >= 64 && Cout <= 1024 && Cout % 64 == 0, LNH_ERR_INVALID_ARG, "%s: Cout %u (a multiple of 64, 64 .. 1024)", what,
-                Cout);
-    const uint32_t H = pool ? H0 / 2 : H0, W = pool ? W0 / 2 : W0;
-    LNH_REQUIRE(N && H && W && (uint64_t)N * H0 * W0 <= kMaxPixels, LNH_ERR_INVALID_ARG,
-                "%s: source [%u, %u, %u], pool %u (output of 1 .. 2^26 pixels)", what, N, H0, W0, pool);
-    if (C1) {
-        LNH_REQUIRE(H1 <= H && H - H1 <= 1 && W1 <= W && W - W1 <= 1 && H1 && W1, LNH_ERR_INVALID_ARG,
-                    "%s: second source %u x %u under an output of %u x %u (each 0 or 1 smaller)", what, H1, W1, H, W);
-    }
+    UNET_REQUIRE_CHANNELS(what, "Cout", Cout, 64);
+    ConvArgs a{};
+    a.g = UnetConvGeom{(const half_t *)src0, (const half_t *)src1, 0, 0, H0, W0, C0, H1, W1, C1, pool};
+    if (int rc = unet_conv_geometry(what, N, a.g)) return rc;
     LNH_REQUIRE(aligned16(src0) && aligned16(src1) && aligned16(weight) && aligned16(scale) && aligned16(shift) && aligned16(out),
                 LNH_ERR_INVALID_ARG, "%s: every pointer must be 16-byte aligned", what);
     LNH_REQUIRE(tile == 0 || tile == LNH_UNET_TILE_16 || tile == LNH_UNET_TILE_32 || tile == LNH_UNET_TILE_64 ||
                     tile == LNH_UNET_TILE_KSPLIT,
                 LNH_ERR_INVALID_ARG, "%s: tile %u (0, 1, 2, 4 or 8)", what, tile);
-    ConvArgs a{};
-    a.s0 = (const half_t *)src0; a.s1 = (const half_t *)src1; a.w = (const half_t *)weight;
-    a.scale = scale; a.shift = shift; a.out = (half_t *)out;
-    a.H = H; a.W = W; a.H0 = H0; a.W0 = W0; a.C0 = C0; a.H1 = H1; a.W1 = W1; a.C1 = C1; a.Cout = Cout; a.pool = pool;
-    a.M = (uint64_t)N * H * W;
+    a.w = (const half_t *)weight; a.scale = scale; a.shift = shift; a.out = (half_t *)out;
+    a.Cout = Cout;
+    a.M = (uint64_t)N * a.g.H * a.g.W;
     const uint32_t cols = Cout / 64;
     if (tile == 0) {
         // From the timings of every layer of a 66 x 1030 frame with every tile: the operand reads are hidden by waves
@@ -312,7 +277,7 @@ int conv3x3_launch(const char *what, const void *src0, uint32_t C0, uint32_t H0,
 extern "C" {
 
 uint64_t lnh_unet_workspace_size(uint32_t N, uint32_t H, uint32_t W) {
-    if (N == 0 || H < 16 || W < 16 || (uint64_t)N * H * W > kMaxPixels) return 0;
+    if (N == 0 || H < 16 || W < 16 || (uint64_t)N * H * W > kUnetMaxPixels) return 0;
     uint64_t total = pad256((uint64_t)N * H * W * 32 * 2);
     for (uint32_t l = 0; l < kLevels; l++)  // DoubleConv: mid and output of every encoder level
         total += 2 * pad256((uint64_t)N * (H >> l) * (W >> l) * (64u << l) * 2);
@@ -325,7 +290,7 @@ uint64_t lnh_unet_workspace_size(uint32_t N, uint32_t H, uint32_t W) {
 int lnh_unet_input(const float *in, uint32_t N, uint32_t C, uint32_t H, uint32_t W, void *out, lnh_stream_t stream) {
     LNH_REQUIRE(in && out, LNH_ERR_INVALID_ARG, "unet_input: null pointer");
     LNH_REQUIRE(C >= 1 && C <= 32, LNH_ERR_INVALID_ARG, "unet_input: %u channels (1 .. 32)", C);
-    LNH_REQUIRE(N && H && W && (uint64_t)N * H * W <= kMaxPixels, LNH_ERR_INVALID_ARG,
+    LNH_REQUIRE(N && H && W && (uint64_t)N * H * W <= kUnetMaxPixels, LNH_ERR_INVALID_ARG,
                 "unet_input: image [%u, %u, %u] (1 .. 2^26 pixels)", N, H, W);
     LNH_REQUIRE(aligned16(out), LNH_ERR_INVALID_ARG, "unet_input: out must be 16-byte aligned");
     InputArgs a{in, (half_t *)out, N, C, H, W};
@@ -350,11 +315,9 @@ int lnh_unet_conv3x3_raw(const void *src0, uint32_t C0, uint32_t H0, uint32_t W0
 int lnh_unet_upconv2x2(const void *in, uint32_t N, uint32_t H, uint32_t W, uint32_t Cin, const void *weight, const float *bias,
                        uint32_t Cout, void *out, lnh_stream_t stream) {
     LNH_REQUIRE(in && weight && bias && out, LNH_ERR_INVALID_ARG, "unet_upconv2x2: null pointer");
-    LNH_REQUIRE(Cin >= 32 && Cin <= 1024 && Cin % 32 == 0, LNH_ERR_INVALID_ARG,
-                "unet_upconv2x2: Cin %u (a multiple of 32, 32 .. 1024)", Cin);
-    LNH_REQUIRE(Cout >= 64 && Cout <= 1024 && Cout % 64 == 0, LNH_ERR_INVALID_ARG,
-                "unet_upconv2x2: Cout %u (a multiple of 64, 64 .. 1024)", Cout);
-    LNH_REQUIRE(N && H && W && (uint64_t)N * H * W * 4 <= kMaxPixels, LNH_ERR_INVALID_ARG,
+    UNET_REQUIRE_CHANNELS("unet_upconv2x2", "Cin", Cin, 32);
+    UNET_REQUIRE_CHANNELS("unet_upconv2x2", "Cout", Cout, 64);
+    LNH_REQUIRE(N && H && W && (uint64_t)N * H * W * 4 <= kUnetMaxPixels, LNH_ERR_INVALID_ARG,
                 "unet_upconv2x2: image [%u, %u, %u] (output of 1 .. 2^26 pixels)", N, H, W);
     LNH_REQUIRE(aligned16(in) && aligned16(weight) && aligned16(bias) && aligned16(out), LNH_ERR_INVALID_ARG,
                 "unet_upconv2x2: every pointer must be 16-byte aligned");
@@ -366,7 +329,7 @@ int lnh_unet_upconv2x2(const void *in, uint32_t N, uint32_t H, uint32_t W, uint3
 int lnh_unet_head(const void *in, uint32_t N, uint32_t H, uint32_t W, const void *weight, const float *bias, float *logits,
                   float *mask, lnh_stream_t stream) {
     LNH_REQUIRE(in && weight && bias && logits, LNH_ERR_INVALID_ARG, "unet_head: null pointer");
-    LNH_REQUIRE(N && H && W && (uint64_t)N * H * W <= kMaxPixels, LNH_ERR_INVALID_ARG,
+    LNH_REQUIRE(N && H && W && (uint64_t)N * H * W <= kUnetMaxPixels, LNH_ERR_INVALID_ARG,
                 "unet_head: image [%u, %u, %u] (1 .. 2^26 pixels)", N, H, W);
     LNH_REQUIRE(aligned16(in) && aligned16(weight), LNH_ERR_INVALID_ARG, "unet_head: in and weight must be 16-byte aligned");
     HeadArgs a{(const half_t *)in, (const half_t *)weight, bias, logits, mask, (uint64_t)N * H * W};

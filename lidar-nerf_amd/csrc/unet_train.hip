@@ -1,6 +1,7 @@
 // unet_train.hip — backward kernels of the ray-drop U-Net's training step: the max-pool backward with the skip add, the
 // backward of the 1 x 1 head, the transposed convolution's weight pack and data gradient.  Contract: include/lidarnerf_hip.h,
-// "U-Net training".
+// "U-Net training".  unet_common.h: the small helpers, the dy window both transposed-convolution entry points require
+// (unet_upconv_dy_window), the channel-range message and the slice split of the weight gradient (unet_pixel_split).
 //   k_unet_pool_backward  one thread owns 8 channels of one source pixel: it re-reads its 2 x 2 window, finds the first maximum in
 //                         row-major order (strict >, and a NaN takes over: torch's rule) and takes the pooled gradient if that is its own position; the
 //                         skip gradient — channels [0, C) of a wider tensor, read in place through a pixel stride — is added in fp32
@@ -25,14 +26,11 @@
 //                         the pixels of its slice in steps of 32 and writes its partial to the workspace in the parameter's
 //                         [Cin, Cout, 2, 2] layout; the workgroups of ci block 0 also add the dy tiles per co (q, then tile row,
 //                         ascending, one fp32 chain).  k_unet_upconv_bwd_reduce adds the slices in ascending order in float64.
-#include "common.h"
+#include "unet_common.h"
 
 namespace {
 
-constexpr uint64_t kTrainMaxPixels = 1ull << 26;
 constexpr uint32_t kHeadC = 64, kHeadCols = kHeadC + 1;  // the head's input channels; + 1 column for the bias
-
-__device__ __forceinline__ half8_t load8(const half_t *p) { return *reinterpret_cast<const half8_t *>(p); }
 
 struct PoolBwdArgs {
     const half_t *x, *dpool, *dskip;
@@ -48,17 +46,16 @@ k_unet_pool_backward(PoolBwdArgs a) {
     if (i >= a.M0 * groups) return;
     const uint64_t p = i / groups;
     const uint32_t c0 = (uint32_t)(i % groups) * 8;
-    const uint64_t HW0 = (uint64_t)a.H0 * a.W0;
-    const uint32_t n = (uint32_t)(p / HW0), yx = (uint32_t)(p % HW0), y = yx / a.W0, x = yx % a.W0;
-    const uint32_t H = a.H0 / 2, W = a.W0 / 2, py = y / 2, px = x / 2;
+    const UnetPixel s = unet_pixel(p, a.H0, a.W0);
+    const uint32_t n = s.n, y = s.y, x = s.x, H = a.H0 / 2, W = a.W0 / 2, py = y / 2, px = x / 2;
     float out[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) out[j] = 0.0f;
     if (py < H && px < W) {  // (a last odd row or column belongs to no window)
         const half_t *win = a.x + (((uint64_t)n * a.H0 + 2 * py) * a.W0 + 2 * px) * a.C + c0;
         const uint64_t row = (uint64_t)a.W0 * a.C;
-        const half8_t v[4] = {load8(win), load8(win + a.C), load8(win + row), load8(win + row + a.C)};
-        const half8_t d = load8(a.dpool + (((uint64_t)n * H + py) * W + px) * a.C + c0);
+        const half8_t v[4] = {ld8(win), ld8(win + a.C), ld8(win + row), ld8(win + row + a.C)};
+        const half8_t d = ld8(a.dpool + (((uint64_t)n * H + py) * W + px) * a.C + c0);
         const int mine = (int)((y & 1) * 2 + (x & 1));
 #pragma unroll
         for (int j = 0; j < 8; j++) {
@@ -71,7 +68,7 @@ k_unet_pool_backward(PoolBwdArgs a) {
         }
     }
     if (a.dskip) {
-        const half8_t s = load8(a.dskip + p * a.skip_stride + c0);
+        const half8_t s = ld8(a.dskip + p * a.skip_stride + c0);
 #pragma unroll
         for (int j = 0; j < 8; j++) out[j] += (float)s[j];
     }
@@ -98,9 +95,9 @@ k_unet_head_backward(HeadBwdArgs a) {
     const bool writer = (threadIdx.x & 63) == 0 && valid;  // (lane 0 is valid whenever any lane of its wave is)
 #pragma unroll
     for (uint32_t k = 0; k < kHeadC / 8; k++) {
-        const half8_t w = load8(a.w + 8 * k);
-        half8_t x = half8_t{0, 0, 0, 0, 0, 0, 0, 0}, o;
-        if (valid) x = load8(a.a + p * kHeadC + 8 * k);
+        const half8_t w = ld8(a.w + 8 * k);
+        half8_t x = zero8(), o;
+        if (valid) x = ld8(a.a + p * kHeadC + 8 * k);
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             o[j] = (half_t)(d * (float)w[j]);
@@ -144,8 +141,6 @@ k_unet_pack_upconv(PackUpArgs a) {
     a.bwd[i] = (half_t)a.w[((uint64_t)ci * a.Cout + co) * 4 + q];
 }
 
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
 struct UpBwdArgs {
     const half_t *dy, *w;
     half_t *dx;
@@ -162,24 +157,24 @@ k_unet_upconv_bwd_data(UpBwdArgs a) {
     const uint32_t ci0 = blockIdx.y * 64;
     const uint64_t p = base + c;
     const bool valid = p < a.M;
-    const uint64_t HW = (uint64_t)a.H * a.W, pq = valid ? p : 0;
-    const uint32_t n = (uint32_t)(pq / HW), yx = (uint32_t)(pq % HW), y = yx / a.W, x = yx % a.W;
+    const UnetPixel s = unet_pixel(valid ? p : 0, a.H, a.W);
+    const uint32_t n = s.n, y = s.y, x = s.x;
     const half_t *wrow[4];
 #pragma unroll
     for (int t = 0; t < 4; t++) wrow[t] = a.w + (uint64_t)(ci0 + 16 * t + c) * 4 * a.Cout + 8 * g;
-    f32x4_t acc[4];
+    f32x4 acc[4];
 #pragma unroll
-    for (int t = 0; t < 4; t++) acc[t] = f32x4_t{0, 0, 0, 0};
+    for (int t = 0; t < 4; t++) acc[t] = f32x4{0, 0, 0, 0};
     for (uint32_t q = 0; q < 4; q++) {
         const half_t *src = a.dy + (((uint64_t)n * a.Hd + 2 * y + (q >> 1)) * a.Wd + 2 * x + (q & 1)) * a.stride + a.off + 8 * g;
 #pragma unroll 2
         for (uint32_t ch = 0; ch < a.Cout; ch += 32) {
             half8_t wf[4];
 #pragma unroll
-            for (int t = 0; t < 4; t++) wf[t] = load8(wrow[t] + q * a.Cout + ch);
-            const half8_t df = valid ? load8(src + ch) : half8_t{0, 0, 0, 0, 0, 0, 0, 0};
+            for (int t = 0; t < 4; t++) wf[t] = ld8(wrow[t] + q * a.Cout + ch);
+            const half8_t df = valid ? ld8(src + ch) : zero8();
 #pragma unroll
-            for (int t = 0; t < 4; t++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[t], df, acc[t], 0, 0, 0);
+            for (int t = 0; t < 4; t++) acc[t] = UNET_MFMA(wf[t], df, acc[t]);
         }
     }
     if (!valid) return;
@@ -210,26 +205,24 @@ k_unet_upconv_bwd_weight(UpWgtArgs a) {
     const uint32_t spix = t >> 3, chunk = t & 7;  // this thread's tile row and 8-channel chunk when staging
     const uint32_t ci0 = blockIdx.y * 64, co0 = blockIdx.z * 64;
     const uint64_t begin = (uint64_t)blockIdx.x * a.L, end = begin + a.L < a.M ? begin + a.L : a.M;
-    const uint64_t HW = (uint64_t)a.H * a.W;
     const bool bias_owner = blockIdx.y == 0 && t < 64;
     float bias = 0.0f;
-    f32x4_t acc[4][4];
+    f32x4 acc[4][4];
 #pragma unroll
     for (int q = 0; q < 4; q++)
 #pragma unroll
-        for (int i = 0; i < 4; i++) acc[q][i] = f32x4_t{0, 0, 0, 0};
-    const half8_t zero = half8_t{0, 0, 0, 0, 0, 0, 0, 0};
+        for (int i = 0; i < 4; i++) acc[q][i] = f32x4{0, 0, 0, 0};
 
     for (uint64_t base = begin; base < end; base += 32) {
         const uint64_t p = base + spix;
         const bool valid = p < end;
-        const uint64_t pq = valid ? p : 0;
-        const uint32_t n = (uint32_t)(pq / HW), yx = (uint32_t)(pq % HW), y = yx / a.W, x = yx % a.W;
-        *reinterpret_cast<half8_t *>(&xs[spix][8 * chunk]) = valid ? load8(a.x + p * a.Cin + ci0 + 8 * chunk) : zero;
+        const UnetPixel s = unet_pixel(valid ? p : 0, a.H, a.W);
+        const uint32_t n = s.n, y = s.y, x = s.x;
+        *reinterpret_cast<half8_t *>(&xs[spix][8 * chunk]) = valid ? ld8(a.x + p * a.Cin + ci0 + 8 * chunk) : zero8();
 #pragma unroll
         for (uint32_t q = 0; q < 4; q++) {
             const half_t *src = a.dy + (((uint64_t)n * a.Hd + 2 * y + (q >> 1)) * a.Wd + 2 * x + (q & 1)) * a.stride + a.off + co0 + 8 * chunk;
-            *reinterpret_cast<half8_t *>(&ds[q][spix][8 * chunk]) = valid ? load8(src) : zero;
+            *reinterpret_cast<half8_t *>(&ds[q][spix][8 * chunk]) = valid ? ld8(src) : zero8();
         }
         __syncthreads();
         half8_t af[4];
@@ -243,7 +236,7 @@ k_unet_upconv_bwd_weight(UpWgtArgs a) {
 #pragma unroll
             for (int j = 0; j < 8; j++) bf[j] = ds[q][4 * j + g][16 * wave + c];
 #pragma unroll
-            for (int i = 0; i < 4; i++) acc[q][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i], bf, acc[q][i], 0, 0, 0);
+            for (int i = 0; i < 4; i++) acc[q][i] = UNET_MFMA(af[i], bf, acc[q][i]);
         }
         if (bias_owner) {
             for (int q = 0; q < 4; q++)
@@ -274,26 +267,12 @@ k_unet_upconv_bwd_reduce(const float *__restrict__ part, uint32_t S, uint64_t nw
     else dbias[i - nw] = (float)s;
 }
 
-struct UpSplit {
-    uint32_t S;
-    uint64_t L;
-};
-
-// The slices of the pixel range, from the shape alone: as many as 256-pixel pieces, as long as all slices fit 16 MiB; the slice length
-// is then rounded up to the 32-pixel step and the count taken again.
-UpSplit upconv_wgrad_split(uint64_t M, uint32_t Cin, uint32_t Cout) {
-    const uint64_t budget = kUpSliceBudget / (16ull * Cin * Cout), pieces = (M + 255) / 256;
-    const uint64_t S = pieces < budget ? pieces : (budget ? budget : 1);
-    const uint64_t L = ((M + S - 1) / S + 31) / 32 * 32;
-    return UpSplit{(uint32_t)((M + L - 1) / L), L};
-}
+// (the bias row of a slice is not counted against the 16 MiB)
+UnetSplit upconv_wgrad_split(uint64_t M, uint32_t Cin, uint32_t Cout) { return unet_pixel_split(M, 16ull * Cin * Cout, kUpSliceBudget); }
 
 bool upconv_wgrad_shape_ok(uint32_t N, uint32_t H, uint32_t W, uint32_t Cin, uint32_t Cout) {
-    return N && H && W && (uint64_t)N * H * W * 4 <= kTrainMaxPixels && Cin >= 64 && Cin <= 1024 && Cin % 64 == 0 && Cout >= 64 &&
-           Cout <= 1024 && Cout % 64 == 0;
+    return N && H && W && (uint64_t)N * H * W * 4 <= kUnetMaxPixels && unet_channels_ok(Cin, 64) && unet_channels_ok(Cout, 64);
 }
-
-bool is_aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -302,12 +281,12 @@ extern "C" {
 int lnh_unet_pool_backward(const void *x, uint32_t N, uint32_t H0, uint32_t W0, uint32_t C, const void *dpool, const void *dskip,
                            uint32_t skip_stride, void *dx, lnh_stream_t stream) {
     LNH_REQUIRE(x && dpool && dx, LNH_ERR_INVALID_ARG, "unet_pool_backward: null pointer");
-    LNH_REQUIRE(C >= 32 && C <= 1024 && C % 32 == 0, LNH_ERR_INVALID_ARG, "unet_pool_backward: C %u (a multiple of 32, 32 .. 1024)", C);
-    LNH_REQUIRE(N && H0 >= 2 && W0 >= 2 && (uint64_t)N * H0 * W0 <= kTrainMaxPixels, LNH_ERR_INVALID_ARG,
+    UNET_REQUIRE_CHANNELS("unet_pool_backward", "C", C, 32);
+    LNH_REQUIRE(N && H0 >= 2 && W0 >= 2 && (uint64_t)N * H0 * W0 <= kUnetMaxPixels, LNH_ERR_INVALID_ARG,
                 "unet_pool_backward: source [%u, %u, %u] (at least 2 x 2, up to 2^26 pixels)", N, H0, W0);
     LNH_REQUIRE(dskip ? (skip_stride >= C && skip_stride <= 2048 && skip_stride % 8 == 0) : skip_stride == 0, LNH_ERR_INVALID_ARG,
                 "unet_pool_backward: skip stride %u (with dskip: a multiple of 8 from C = %u to 2048; without: 0)", skip_stride, C);
-    LNH_REQUIRE(is_aligned16(x) && is_aligned16(dpool) && is_aligned16(dskip) && is_aligned16(dx), LNH_ERR_INVALID_ARG,
+    LNH_REQUIRE(aligned16(x) && aligned16(dpool) && aligned16(dskip) && aligned16(dx), LNH_ERR_INVALID_ARG,
                 "unet_pool_backward: every pointer must be 16-byte aligned");
     PoolBwdArgs a{(const half_t *)x, (const half_t *)dpool, (const half_t *)dskip, (half_t *)dx, H0, W0, C, skip_stride,
                   (uint64_t)N * H0 * W0};
@@ -317,7 +296,7 @@ int lnh_unet_pool_backward(const void *x, uint32_t N, uint32_t H0, uint32_t W0, 
 
 uint64_t lnh_unet_head_backward_workspace_size(uint32_t N, uint32_t H, uint32_t W) {
     const uint64_t M = (uint64_t)N * H * W;
-    if (!N || !H || !W || M > kTrainMaxPixels) return 0;
+    if (!N || !H || !W || M > kUnetMaxPixels) return 0;
     return (M + 63) / 64 * kHeadCols * sizeof(float);
 }
 
@@ -328,7 +307,7 @@ int lnh_unet_head_backward(const void *a, uint32_t N, uint32_t H, uint32_t W, co
     LNH_REQUIRE(need, LNH_ERR_INVALID_ARG, "unet_head_backward: image [%u, %u, %u] (1 .. 2^26 pixels)", N, H, W);
     LNH_REQUIRE(ws_bytes >= need, LNH_ERR_INVALID_ARG, "unet_head_backward: workspace of %llu bytes, %llu needed",
                 (unsigned long long)ws_bytes, (unsigned long long)need);
-    LNH_REQUIRE(is_aligned16(a) && is_aligned16(weight) && is_aligned16(ws) && is_aligned16(dx), LNH_ERR_INVALID_ARG,
+    LNH_REQUIRE(aligned16(a) && aligned16(weight) && aligned16(ws) && aligned16(dx), LNH_ERR_INVALID_ARG,
                 "unet_head_backward: a, weight, the workspace and dx must be 16-byte aligned");
     const uint64_t M = (uint64_t)N * H * W;
     HeadBwdArgs h{(const half_t *)a, (const half_t *)weight, dlogits, (half_t *)dx, (float *)ws, M};
@@ -339,11 +318,9 @@ int lnh_unet_head_backward(const void *a, uint32_t N, uint32_t H, uint32_t W, co
 
 int lnh_unet_pack_upconv(const float *weight, uint32_t Cin, uint32_t Cout, void *fwd, void *bwd, lnh_stream_t stream) {
     LNH_REQUIRE(weight && fwd, LNH_ERR_INVALID_ARG, "unet_pack_upconv: null pointer");
-    LNH_REQUIRE(Cin >= 64 && Cin <= 1024 && Cin % 64 == 0, LNH_ERR_INVALID_ARG, "unet_pack_upconv: Cin %u (a multiple of 64, 64 .. 1024)",
-                Cin);
-    LNH_REQUIRE(Cout >= 64 && Cout <= 1024 && Cout % 64 == 0, LNH_ERR_INVALID_ARG,
-                "unet_pack_upconv: Cout %u (a multiple of 64, 64 .. 1024)", Cout);
-    LNH_REQUIRE(is_aligned16(weight) && is_aligned16(fwd) && is_aligned16(bwd), LNH_ERR_INVALID_ARG,
+    UNET_REQUIRE_CHANNELS("unet_pack_upconv", "Cin", Cin, 64);
+    UNET_REQUIRE_CHANNELS("unet_pack_upconv", "Cout", Cout, 64);
+    LNH_REQUIRE(aligned16(weight) && aligned16(fwd) && aligned16(bwd), LNH_ERR_INVALID_ARG,
                 "unet_pack_upconv: every pointer must be 16-byte aligned");
     PackUpArgs a{weight, (half_t *)fwd, (half_t *)bwd, Cin, Cout};
     LNH_LAUNCH(k_unet_pack_upconv, dim3(div_up((uint64_t)Cin * Cout * 8, 256)), dim3(256), 0, (hipStream_t)stream, a);
@@ -353,20 +330,12 @@ int lnh_unet_pack_upconv(const float *weight, uint32_t Cin, uint32_t Cout, void 
 int lnh_unet_upconv2x2_backward_data(const void *dy, uint32_t Hd, uint32_t Wd, uint32_t dy_stride, uint32_t dy_offset, uint32_t N,
                                      uint32_t H, uint32_t W, uint32_t Cin, uint32_t Cout, const void *weight, void *dx,
                                      lnh_stream_t stream) {
-    LNH_REQUIRE(dy && weight && dx, LNH_ERR_INVALID_ARG, "unet_upconv2x2_backward_data: null pointer");
-    LNH_REQUIRE(Cin >= 64 && Cin <= 1024 && Cin % 64 == 0, LNH_ERR_INVALID_ARG,
-                "unet_upconv2x2_backward_data: Cin %u (a multiple of 64, 64 .. 1024)", Cin);
-    LNH_REQUIRE(Cout >= 32 && Cout <= 1024 && Cout % 32 == 0, LNH_ERR_INVALID_ARG,
-                "unet_upconv2x2_backward_data: Cout %u (a multiple of 32, 32 .. 1024)", Cout);
-    LNH_REQUIRE(N && H && W && (uint64_t)N * H * W * 4 <= kTrainMaxPixels, LNH_ERR_INVALID_ARG,
-                "unet_upconv2x2_backward_data: image [%u, %u, %u] (output of 1 .. 2^26 pixels)", N, H, W);
-    LNH_REQUIRE(Hd >= 2 * H && Hd - 2 * H <= 1 && Wd >= 2 * W && Wd - 2 * W <= 1, LNH_ERR_INVALID_ARG,
-                "unet_upconv2x2_backward_data: dy of %u x %u over an output of %u x %u (each 0 or 1 larger)", Hd, Wd, 2 * H, 2 * W);
-    LNH_REQUIRE(dy_stride % 8 == 0 && dy_offset % 8 == 0 && dy_stride <= 2048 && (uint64_t)dy_offset + Cout <= dy_stride,
-                LNH_ERR_INVALID_ARG, "unet_upconv2x2_backward_data: channels [%u, %u + %u) of %u per pixel (offset and stride multiples "
-                "of 8, stride up to 2048)", dy_offset, dy_offset, Cout, dy_stride);
-    LNH_REQUIRE(is_aligned16(dy) && is_aligned16(weight) && is_aligned16(dx), LNH_ERR_INVALID_ARG,
-                "unet_upconv2x2_backward_data: every pointer must be 16-byte aligned");
+    const char *what = "unet_upconv2x2_backward_data";
+    LNH_REQUIRE(dy && weight && dx, LNH_ERR_INVALID_ARG, "%s: null pointer", what);
+    UNET_REQUIRE_CHANNELS(what, "Cin", Cin, 64);
+    UNET_REQUIRE_CHANNELS(what, "Cout", Cout, 32);
+    if (int rc = unet_upconv_dy_window(what, N, H, W, Hd, Wd, dy_stride, dy_offset, Cout)) return rc;
+    LNH_REQUIRE(aligned16(dy) && aligned16(weight) && aligned16(dx), LNH_ERR_INVALID_ARG, "%s: every pointer must be 16-byte aligned", what);
     UpBwdArgs a{(const half_t *)dy, (const half_t *)weight, (half_t *)dx, H, W, Hd, Wd, dy_stride, dy_offset, Cin, Cout,
                 (uint64_t)N * H * W};
     LNH_LAUNCH(k_unet_upconv_bwd_data, dim3(div_up(a.M, 64), Cin / 64), dim3(256), 0, (hipStream_t)stream, a);
@@ -375,32 +344,25 @@ int lnh_unet_upconv2x2_backward_data(const void *dy, uint32_t Hd, uint32_t Wd, u
 
 uint64_t lnh_unet_upconv2x2_backward_weight_workspace_size(uint32_t N, uint32_t H, uint32_t W, uint32_t Cin, uint32_t Cout) {
     if (!upconv_wgrad_shape_ok(N, H, W, Cin, Cout)) return 0;
-    const UpSplit sp = upconv_wgrad_split((uint64_t)N * H * W, Cin, Cout);
+    const UnetSplit sp = upconv_wgrad_split((uint64_t)N * H * W, Cin, Cout);
     return (uint64_t)sp.S * ((uint64_t)Cin * Cout * 4 + Cout) * sizeof(float);
 }
 
 int lnh_unet_upconv2x2_backward_weight(const void *x, const void *dy, uint32_t Hd, uint32_t Wd, uint32_t dy_stride,
                                        uint32_t dy_offset, uint32_t N, uint32_t H, uint32_t W, uint32_t Cin, uint32_t Cout, void *ws,
                                        uint64_t ws_bytes, float *dweight, float *dbias, lnh_stream_t stream) {
-    LNH_REQUIRE(x && dy && ws && dweight && dbias, LNH_ERR_INVALID_ARG, "unet_upconv2x2_backward_weight: null pointer");
-    LNH_REQUIRE(Cin >= 64 && Cin <= 1024 && Cin % 64 == 0, LNH_ERR_INVALID_ARG,
-                "unet_upconv2x2_backward_weight: Cin %u (a multiple of 64, 64 .. 1024)", Cin);
-    LNH_REQUIRE(Cout >= 64 && Cout <= 1024 && Cout % 64 == 0, LNH_ERR_INVALID_ARG,
-                "unet_upconv2x2_backward_weight: Cout %u (a multiple of 64, 64 .. 1024)", Cout);
-    LNH_REQUIRE(N && H && W && (uint64_t)N * H * W * 4 <= kTrainMaxPixels, LNH_ERR_INVALID_ARG,
-                "unet_upconv2x2_backward_weight: image [%u, %u, %u] (output of 1 .. 2^26 pixels)", N, H, W);
-    LNH_REQUIRE(Hd >= 2 * H && Hd - 2 * H <= 1 && Wd >= 2 * W && Wd - 2 * W <= 1, LNH_ERR_INVALID_ARG,
-                "unet_upconv2x2_backward_weight: dy of %u x %u over an output of %u x %u (each 0 or 1 larger)", Hd, Wd, 2 * H, 2 * W);
-    LNH_REQUIRE(dy_stride % 8 == 0 && dy_offset % 8 == 0 && dy_stride <= 2048 && (uint64_t)dy_offset + Cout <= dy_stride,
-                LNH_ERR_INVALID_ARG, "unet_upconv2x2_backward_weight: channels [%u, %u + %u) of %u per pixel (offset and stride "
-                "multiples of 8, stride up to 2048)", dy_offset, dy_offset, Cout, dy_stride);
+    const char *what = "unet_upconv2x2_backward_weight";
+    LNH_REQUIRE(x && dy && ws && dweight && dbias, LNH_ERR_INVALID_ARG, "%s: null pointer", what);
+    UNET_REQUIRE_CHANNELS(what, "Cin", Cin, 64);
+    UNET_REQUIRE_CHANNELS(what, "Cout", Cout, 64);
+    if (int rc = unet_upconv_dy_window(what, N, H, W, Hd, Wd, dy_stride, dy_offset, Cout)) return rc;
     const uint64_t need = lnh_unet_upconv2x2_backward_weight_workspace_size(N, H, W, Cin, Cout);
-    LNH_REQUIRE(ws_bytes >= need, LNH_ERR_INVALID_ARG, "unet_upconv2x2_backward_weight: workspace of %llu bytes, %llu needed",
-                (unsigned long long)ws_bytes, (unsigned long long)need);
-    LNH_REQUIRE(is_aligned16(x) && is_aligned16(dy) && is_aligned16(ws), LNH_ERR_INVALID_ARG,
-                "unet_upconv2x2_backward_weight: x, dy and the workspace must be 16-byte aligned");
+    LNH_REQUIRE(ws_bytes >= need, LNH_ERR_INVALID_ARG, "%s: workspace of %llu bytes, %llu needed", what, (unsigned long long)ws_bytes,
+                (unsigned long long)need);
+    LNH_REQUIRE(aligned16(x) && aligned16(dy) && aligned16(ws), LNH_ERR_INVALID_ARG, "%s: x, dy and the workspace must be 16-byte aligned",
+                what);
     const uint64_t M = (uint64_t)N * H * W, nw = (uint64_t)Cin * Cout * 4, slice = nw + Cout;
-    const UpSplit sp = upconv_wgrad_split(M, Cin, Cout);
+    const UnetSplit sp = upconv_wgrad_split(M, Cin, Cout);
     UpWgtArgs a{(const half_t *)x, (const half_t *)dy, (float *)ws, H, W, Hd, Wd, dy_stride, dy_offset, Cin, Cout, M, sp.L};
     const hipStream_t s = (hipStream_t)stream;
     LNH_LAUNCH(k_unet_upconv_bwd_weight, dim3(sp.S, Cin / 64, Cout / 64), dim3(256), 0, s, a);

@@ -1,6 +1,7 @@
 // unet_train_conv.hip — the training-mode convolution layer of the ray-drop U-Net around the raw convolution: weight
 // pack, batch statistics, BatchNorm + ReLU and their backward.  Contract: include/lidarnerf_hip.h, "U-Net training".  (The raw
-// convolution itself — lnh_unet_conv3x3_raw, forward and data gradient — is the RAW epilogue of k_unet_conv3x3 in unet.hip.)
+// convolution itself — lnh_unet_conv3x3_raw, forward and data gradient — is the RAW epilogue of k_unet_conv3x3 in unet.hip.)  The
+// 16-byte load, aligned16, the pixel bound and the channel-range message are unet_common.h's; the partial rule (bn_split) is this file's.
 //   k_unet_pack_conv3x3   the live fp32 parameter [Cout, Cin, 3, 3] -> the forward image [Cout, 9, Cpad] of lnh_unet_conv3x3 (thread
 //                         per (co, padded ci), ci fastest: nine coalesced 2-byte stores) and the data-gradient image [Cin, 9, Cout],
 //                         bwd[ci, t, co] = W[co, ci, 8 - t] (thread per (ci, co), co fastest).
@@ -15,17 +16,13 @@
 //                         two sums to f32.
 //   k_unet_bn_bwd_dz      dz = fp16(scale (g - dbeta / M - xhat dgamma / M)) in fp32; every element is read before its owner writes it,
 //                         so dz may be da.
-#include "common.h"
+#include "unet_common.h"
 
 namespace {
 
-constexpr uint64_t kBnMaxPixels = 1ull << 26;
 constexpr uint32_t kBnBlockPixels = 256;    // pixels per partial, times ceil(M / 2^14): at most 64 partials per channel
 constexpr uint64_t kBnPartialSpan = 1ull << 14;
 constexpr uint32_t kBnSlab = 64, kBnRows = 32;  // channels per workgroup; pixel rows of its 256 threads
-
-__device__ __forceinline__ half8_t rd8(const half_t *p) { return *reinterpret_cast<const half8_t *>(p); }
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 struct PackConvArgs {
     const float *w;
@@ -62,7 +59,7 @@ BnSplit bn_split(uint64_t M) {
     return BnSplit{P, (uint32_t)((M + P - 1) / P)};
 }
 
-bool bn_shape_ok(uint64_t M, uint32_t C) { return M >= 2 && M <= kBnMaxPixels && C >= 32 && C <= 1024 && C % 32 == 0; }
+bool bn_shape_ok(uint64_t M, uint32_t C) { return M >= 2 && M <= kUnetMaxPixels && unet_channels_ok(C, 32); }
 
 // A workgroup owns kBnSlab channels (slab blockIdx.y) of the P pixels of partial blockIdx.x: thread (r, g) = (t / 8, t % 8) chains 8
 // channels over the pixels begin + r, begin + r + 32, ..  This adds the 32 rows per column in ascending r and writes the partial.
@@ -99,7 +96,7 @@ k_unet_bn_stats(BnStatsArgs a) {
     for (int j = 0; j < 8; j++) s0[j] = s1[j] = 0.0;
 #pragma unroll 4
     for (uint64_t p = c0 < a.C ? begin + r : end; p < end; p += kBnRows) {
-        const half8_t v = rd8(a.z + p * a.C + c0);
+        const half8_t v = ld8(a.z + p * a.C + c0);
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             const double x = (double)v[j];
@@ -155,9 +152,9 @@ k_unet_bn_relu(BnReluArgs a) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= a.M * G) return;
     const uint32_t c0 = (uint32_t)(i % G) * 8;
-    const half8_t v = rd8(a.z + i * 8);
-    const f32x4_t s[2] = {*reinterpret_cast<const f32x4_t *>(a.scale + c0), *reinterpret_cast<const f32x4_t *>(a.scale + c0 + 4)};
-    const f32x4_t t[2] = {*reinterpret_cast<const f32x4_t *>(a.shift + c0), *reinterpret_cast<const f32x4_t *>(a.shift + c0 + 4)};
+    const half8_t v = ld8(a.z + i * 8);
+    const f32x4 s[2] = {*reinterpret_cast<const f32x4 *>(a.scale + c0), *reinterpret_cast<const f32x4 *>(a.scale + c0 + 4)};
+    const f32x4 t[2] = {*reinterpret_cast<const f32x4 *>(a.shift + c0), *reinterpret_cast<const f32x4 *>(a.shift + c0 + 4)};
     half8_t o;
 #pragma unroll
     for (int j = 0; j < 8; j++) o[j] = (half_t)fmaxf(fmaf((float)v[j], s[j >> 2][j & 3], t[j >> 2][j & 3]), 0.0f);
@@ -187,7 +184,7 @@ k_unet_bn_bwd_sums(BnBwdArgs a) {
 #pragma unroll 2
     for (uint64_t p = live ? begin + r : end; p < end; p += kBnRows) {
         const uint64_t e = p * a.C + c0;
-        const half8_t z = rd8(a.z + e), act = rd8(a.a + e), da = rd8(a.da + e);
+        const half8_t z = ld8(a.z + e), act = ld8(a.a + e), da = ld8(a.da + e);
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             const float gj = act[j] > (half_t)0 ? (float)da[j] : 0.0f;
@@ -219,7 +216,7 @@ k_unet_bn_bwd_dz(BnBwdArgs a) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= a.M * G) return;
     const uint32_t c0 = (uint32_t)(i % G) * 8;
-    const half8_t z = rd8(a.z + i * 8), act = rd8(a.a + i * 8), da = rd8(a.da + i * 8);
+    const half8_t z = ld8(a.z + i * 8), act = ld8(a.a + i * 8), da = ld8(a.da + i * 8);
     const float M = (float)a.M;
     half8_t o;
 #pragma unroll
@@ -232,20 +229,17 @@ k_unet_bn_bwd_dz(BnBwdArgs a) {
     *reinterpret_cast<half8_t *>(a.dz + i * 8) = o;
 }
 
-bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" {
 
 int lnh_unet_pack_conv3x3(const float *weight, uint32_t Cout, uint32_t Cin, void *fwd, void *bwd, lnh_stream_t stream) {
     LNH_REQUIRE(weight && fwd, LNH_ERR_INVALID_ARG, "unet_pack_conv3x3: null pointer");
-    LNH_REQUIRE(Cout >= 64 && Cout <= 1024 && Cout % 64 == 0, LNH_ERR_INVALID_ARG,
-                "unet_pack_conv3x3: Cout %u (a multiple of 64, 64 .. 1024)", Cout);
+    UNET_REQUIRE_CHANNELS("unet_pack_conv3x3", "Cout", Cout, 64);
     LNH_REQUIRE(Cin >= 1 && Cin <= 1024 && (Cin <= 32 || Cin % 32 == 0), LNH_ERR_INVALID_ARG,
                 "unet_pack_conv3x3: Cin %u (1 .. 32, or a multiple of 32 up to 1024)", Cin);
     LNH_REQUIRE(!bwd || Cin % 64 == 0, LNH_ERR_INVALID_ARG, "unet_pack_conv3x3: the bwd image needs Cin %u to be a multiple of 64", Cin);
-    LNH_REQUIRE(al16(weight) && al16(fwd) && al16(bwd), LNH_ERR_INVALID_ARG, "unet_pack_conv3x3: every pointer must be 16-byte aligned");
+    LNH_REQUIRE(aligned16(weight) && aligned16(fwd) && aligned16(bwd), LNH_ERR_INVALID_ARG, "unet_pack_conv3x3: every pointer must be 16-byte aligned");
     PackConvArgs a{weight, (half_t *)fwd, (half_t *)bwd, Cout, Cin, Cin <= 32 ? 32u : Cin};
     const uint64_t threads = (uint64_t)Cout * a.Cpad + (bwd ? (uint64_t)Cin * Cout : 0);
     LNH_LAUNCH(k_unet_pack_conv3x3, dim3(div_up(threads, 256)), dim3(256), 0, (hipStream_t)stream, a);
@@ -261,15 +255,15 @@ int lnh_unet_bn_stats(const void *z, uint64_t M, uint32_t C, const float *gamma,
                       void *ws, uint64_t ws_bytes, float *mean, float *invstd, float *scale, float *shift, float *running_mean,
                       float *running_var, lnh_stream_t stream) {
     LNH_REQUIRE(z && gamma && beta && ws && mean && invstd && scale && shift, LNH_ERR_INVALID_ARG, "unet_bn_stats: null pointer");
-    LNH_REQUIRE(M >= 2 && M <= kBnMaxPixels, LNH_ERR_INVALID_ARG,
+    LNH_REQUIRE(M >= 2 && M <= kUnetMaxPixels, LNH_ERR_INVALID_ARG,
                 "unet_bn_stats: M %llu values per channel (2 .. 2^26; one value has no variance)", (unsigned long long)M);
-    LNH_REQUIRE(C >= 32 && C <= 1024 && C % 32 == 0, LNH_ERR_INVALID_ARG, "unet_bn_stats: C %u (a multiple of 32, 32 .. 1024)", C);
+    UNET_REQUIRE_CHANNELS("unet_bn_stats", "C", C, 32);
     LNH_REQUIRE(eps >= 0.0 && momentum >= 0.0 && momentum <= 1.0, LNH_ERR_INVALID_ARG,
                 "unet_bn_stats: eps %g (>= 0), momentum %g (0 .. 1)", eps, momentum);
     const uint64_t need = lnh_unet_bn_stats_workspace_size(M, C);
     LNH_REQUIRE(ws_bytes >= need, LNH_ERR_INVALID_ARG, "unet_bn_stats: workspace of %llu bytes, %llu needed",
                 (unsigned long long)ws_bytes, (unsigned long long)need);
-    LNH_REQUIRE(al16(z) && al16(ws) && al16(scale) && al16(shift), LNH_ERR_INVALID_ARG,
+    LNH_REQUIRE(aligned16(z) && aligned16(ws) && aligned16(scale) && aligned16(shift), LNH_ERR_INVALID_ARG,
                 "unet_bn_stats: z, the workspace, scale and shift must be 16-byte aligned");
     const BnSplit sp = bn_split(M);
     const hipStream_t s = (hipStream_t)stream;
@@ -282,9 +276,9 @@ int lnh_unet_bn_stats(const void *z, uint64_t M, uint32_t C, const float *gamma,
 
 int lnh_unet_bn_relu(const void *z, uint64_t M, uint32_t C, const float *scale, const float *shift, void *a, lnh_stream_t stream) {
     LNH_REQUIRE(z && scale && shift && a, LNH_ERR_INVALID_ARG, "unet_bn_relu: null pointer");
-    LNH_REQUIRE(M >= 1 && M <= kBnMaxPixels, LNH_ERR_INVALID_ARG, "unet_bn_relu: M %llu pixels (1 .. 2^26)", (unsigned long long)M);
-    LNH_REQUIRE(C >= 32 && C <= 1024 && C % 32 == 0, LNH_ERR_INVALID_ARG, "unet_bn_relu: C %u (a multiple of 32, 32 .. 1024)", C);
-    LNH_REQUIRE(al16(z) && al16(scale) && al16(shift) && al16(a), LNH_ERR_INVALID_ARG,
+    LNH_REQUIRE(M >= 1 && M <= kUnetMaxPixels, LNH_ERR_INVALID_ARG, "unet_bn_relu: M %llu pixels (1 .. 2^26)", (unsigned long long)M);
+    UNET_REQUIRE_CHANNELS("unet_bn_relu", "C", C, 32);
+    LNH_REQUIRE(aligned16(z) && aligned16(scale) && aligned16(shift) && aligned16(a), LNH_ERR_INVALID_ARG,
                 "unet_bn_relu: every pointer must be 16-byte aligned");
     BnReluArgs r{(const half_t *)z, scale, shift, (half_t *)a, C, M};
     LNH_LAUNCH(k_unet_bn_relu, dim3(div_up(M * (C / 8), 256)), dim3(256), 0, (hipStream_t)stream, r);
@@ -298,13 +292,13 @@ int lnh_unet_bn_relu_backward(const void *z, const void *a, const void *da, uint
                               float *dbeta, lnh_stream_t stream) {
     LNH_REQUIRE(z && a && da && mean && invstd && scale && ws && dz && dgamma && dbeta, LNH_ERR_INVALID_ARG,
                 "unet_bn_relu_backward: null pointer");
-    LNH_REQUIRE(M >= 2 && M <= kBnMaxPixels, LNH_ERR_INVALID_ARG, "unet_bn_relu_backward: M %llu values per channel (2 .. 2^26)",
+    LNH_REQUIRE(M >= 2 && M <= kUnetMaxPixels, LNH_ERR_INVALID_ARG, "unet_bn_relu_backward: M %llu values per channel (2 .. 2^26)",
                 (unsigned long long)M);
-    LNH_REQUIRE(C >= 32 && C <= 1024 && C % 32 == 0, LNH_ERR_INVALID_ARG, "unet_bn_relu_backward: C %u (a multiple of 32, 32 .. 1024)", C);
+    UNET_REQUIRE_CHANNELS("unet_bn_relu_backward", "C", C, 32);
     const uint64_t need = lnh_unet_bn_relu_backward_workspace_size(M, C);
     LNH_REQUIRE(ws_bytes >= need, LNH_ERR_INVALID_ARG, "unet_bn_relu_backward: workspace of %llu bytes, %llu needed",
                 (unsigned long long)ws_bytes, (unsigned long long)need);
-    LNH_REQUIRE(al16(z) && al16(a) && al16(da) && al16(ws) && al16(dz), LNH_ERR_INVALID_ARG,
+    LNH_REQUIRE(aligned16(z) && aligned16(a) && aligned16(da) && aligned16(ws) && aligned16(dz), LNH_ERR_INVALID_ARG,
                 "unet_bn_relu_backward: z, a, da, the workspace and dz must be 16-byte aligned");
     const BnSplit sp = bn_split(M);
     const hipStream_t s = (hipStream_t)stream;

@@ -8,10 +8,11 @@
 //   lnh_unet_grad_sumsq    sum g^2 over the table's gradients as one float64: kSumBlocks partials, finished in ascending order.
 //   lnh_unet_rmsprop_step  unscale, clip, weight decay, square_avg, momentum_buffer, parameter — fp32 per element, each operation
 //                          rounded on its own (the library is built with -ffp-contract=off) in the order torch applies them.
-// No float atomics, no host read, no allocation; every sum's order depends on the sizes alone.
+// No float atomics, no host read, no allocation; every sum's order depends on the sizes alone.  (unet_common.h: aligned16 and the
+// 2^26 bound; the partial rule of the loss is this file's.)
 #include <cmath>
 
-#include "common.h"
+#include "unet_common.h"
 
 namespace {
 
@@ -115,7 +116,7 @@ k_unet_grad_sumsq(const lnh_urs_tensor *__restrict__ table, uint32_t n, double *
         const uint64_t off = (uint64_t)(c - pre[k]) * kChunk, left = table[k].numel - off;
         const uint32_t m = left < kChunk ? (uint32_t)left : kChunk;
         const float *g = table[k].grad + off;
-        if ((((uintptr_t)g) & 15) == 0) {
+        if (aligned16(g)) {
             float4 v[4];
 #pragma unroll
             for (uint32_t j = 0; j < 4; j++) {
@@ -254,7 +255,7 @@ int check_table(const void *table, uint32_t n, const void *state, const char *wh
 extern "C" {
 
 uint64_t lnh_unet_loss_grad_workspace_size(uint64_t M) {
-    if (M < 1 || M > (1ull << 26)) return 0;
+    if (M < 1 || M > kUnetMaxPixels) return 0;
     return (uint64_t)loss_parts(M) * 3 * sizeof(double);
 }
 
@@ -263,7 +264,7 @@ int lnh_unet_loss_grad(const float *logits, const void *masks, uint32_t mask_dty
     LNH_REQUIRE(logits && masks && ws && loss && dlogits, LNH_ERR_INVALID_ARG, "unet_loss_grad: null pointer");
     LNH_REQUIRE(mask_dtype == LNH_UNET_MASK_F32 || mask_dtype == LNH_UNET_MASK_U8, LNH_ERR_INVALID_ARG,
                 "unet_loss_grad: mask_dtype %u; LNH_UNET_MASK_F32 or LNH_UNET_MASK_U8", mask_dtype);
-    LNH_REQUIRE(M >= 1 && M <= (1ull << 26), LNH_ERR_INVALID_ARG, "unet_loss_grad: M = %llu; 1 .. 2^26 elements", (unsigned long long)M);
+    LNH_REQUIRE(M >= 1 && M <= kUnetMaxPixels, LNH_ERR_INVALID_ARG, "unet_loss_grad: M = %llu; 1 .. 2^26 elements", (unsigned long long)M);
     LNH_REQUIRE(std::isfinite(loss_scale) && loss_scale > 0.0, LNH_ERR_INVALID_ARG, "unet_loss_grad: loss_scale must be positive and finite");
     LNH_REQUIRE(ws_bytes >= lnh_unet_loss_grad_workspace_size(M), LNH_ERR_INVALID_ARG, "unet_loss_grad: workspace of %llu bytes, %llu needed",
                 (unsigned long long)ws_bytes, (unsigned long long)lnh_unet_loss_grad_workspace_size(M));

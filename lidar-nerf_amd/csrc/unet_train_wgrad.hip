@@ -1,9 +1,10 @@
 // unet_train_wgrad.hip — the weight gradient of the ray-drop U-Net's 3 x 3 convolutions.  Contract:
 // include/lidarnerf_hip.h, "U-Net training", lnh_unet_conv3x3_backward_weight.
 //   dW[co, ci, t] = sum over the M = N H W output pixels p of dz[p, co] X[p + off(t), ci], t = 3 (dy + 1) + (dx + 1) the FORWARD tap.
-//   X is the operand k_unet_conv3x3 (csrc/unet.hip) read and exists nowhere: source 0, max-pooled 2 x 2 on read (floor; the maximum
-//   formed by that kernel's own chain of comparisons), then the channels of source 1, which reads as zero for y >= H1 or x >= W1; a
-//   tap outside the image is zero.  fp16 operands, fp32 sums on v_mfma_f32_16x16x32_f16, no float atomics.
+//   X is the operand k_unet_conv3x3 (csrc/unet.hip) read and exists nowhere: source 0, max-pooled 2 x 2 on read (floor), then the
+//   channels of source 1, which reads as zero for y >= H1 or x >= W1; a tap outside the image is zero.  The rule is unet_common.h's
+//   (UnetConvGeom and its functions: which source, which address, the maximum's chain of comparisons), called by both kernels; the
+//   sources' geometry check and the slice split (unet_pixel_split) are there too.  fp16 operands, fp32 sums on v_mfma_f32_16x16x32_f16, no float atomics.
 //   k_unet_conv_wgrad   the summed index (the pixel) is the slow memory index of both operands, so workgroup (slice, ci block, co
 //                       block) walks its pixel slice in steps of 32: thread (pixel r = t / 8, chunk t % 8) reads 8 channels of dz and,
 //                       for each of the nine taps, 8 channels of X at the shifted pixel (16-byte reads, four and a maximum where
@@ -29,30 +30,20 @@
 //   The split, from the shape alone: S = min(ceil(M / 256), max(1, floor(32 MiB / (36 Cp Cout)))) slices of L = ceil(M / S) rounded
 //   up to the 32-pixel step, then S = ceil(M / L): 266 slices for the first layer of a 66 x 1030 frame, one for every layer of
 //   256 x 512 channels and more (the deepest: one 37.7 MB partial).  Same shape, same bits.
-#include "common.h"
+#include "unet_common.h"
 
 namespace {
 
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 typedef __fp16 fp16x4_t __attribute__((__vector_size__(4 * sizeof(__fp16))));  // what the transposed-read builtin returns
 
-constexpr uint64_t kWgMaxPixels = 1ull << 26;
 constexpr uint32_t kWgPitch = 80;                 // halves per LDS row of 64 channels (160 bytes: see the bank picture above)
 constexpr uint64_t kWgSliceBudget = 32ull << 20;  // bytes of partials the split rule allows itself
 
-__device__ __forceinline__ half8_t ld8(const half_t *p) { return *reinterpret_cast<const half8_t *>(p); }
-__device__ __forceinline__ half8_t zero8() { return half8_t{0, 0, 0, 0, 0, 0, 0, 0}; }
-__device__ __forceinline__ half8_t max8(half8_t a, half8_t b) {  // k_unet_conv3x3's comparison, so the pooled operand is the same
-    half8_t r;
-#pragma unroll
-    for (int i = 0; i < 8; i++) r[i] = a[i] > b[i] ? a[i] : b[i];
-    return r;
-}
-
 struct WgradArgs {
-    const half_t *s0, *s1, *dz;
+    UnetConvGeom g;
+    const half_t *dz;
     float *part;  // [S][9][Cout][Cp]
-    uint32_t H, W, H0, W0, C0, H1, W1, C1, Cout, pool;
+    uint32_t Cout;
     uint64_t M, L;  // output pixels; pixels per slice (a multiple of 32)
 };
 
@@ -87,45 +78,34 @@ k_unet_conv_wgrad(WgradArgs a) {
     __shared__ __attribute__((aligned(16))) half_t ds[32 * kWgPitch];
     const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6, c = lane & 15, g = lane >> 4;
     const uint32_t spix = t >> 3, chunk = t & 7;  // this thread's tile row and 8-channel chunk when staging
-    const uint32_t ci0 = blockIdx.y * 64, co0 = blockIdx.z * 64, Cp = a.C0 + a.C1;
+    const UnetConvGeom &G = a.g;
+    const uint32_t ci0 = blockIdx.y * 64, co0 = blockIdx.z * 64, Cp = G.C0 + G.C1;
     const uint64_t begin = (uint64_t)blockIdx.x * a.L, end = begin + a.L < a.M ? begin + a.L : a.M;
-    const uint64_t HW = (uint64_t)a.H * a.W, row0 = (uint64_t)a.W0 * a.C0;
     const uint32_t ch = ci0 + 8 * chunk;                // the staged channels ch .. ch + 7 of the concatenated operand:
-    const int kind = ch < a.C0 ? 0 : ch < Cp ? 1 : 2;  // source 0, source 1, or past the last channel (zero)
+    const int kind = ch < G.C0 ? 0 : ch < Cp ? 1 : 2;  // source 0, source 1, or past the last channel (zero)
 
     half8_t xr[9], dr;
     auto fetch = [&](uint64_t base) {
         const uint64_t p = base + spix;
         const bool valid = p < end;
-        const uint64_t pq = valid ? p : 0;
-        const uint32_t n = (uint32_t)(pq / HW), yx = (uint32_t)(pq % HW);
-        const int y = (int)(yx / a.W), x = (int)(yx % a.W);
+        const UnetPixel q = unet_pixel(valid ? p : 0, G.H, G.W);
         dr = valid ? ld8(a.dz + p * a.Cout + co0 + 8 * chunk) : zero8();
 #pragma unroll
         for (int tap = 0; tap < 9; tap++) {
-            const int yy = y + tap / 3 - 1, xx = x + tap % 3 - 1;
-            const bool in0 = valid && yy >= 0 && yy < (int)a.H && xx >= 0 && xx < (int)a.W;
+            const int yy = (int)q.y + tap / 3 - 1, xx = (int)q.x + tap % 3 - 1;
+            const bool in0 = unet_tap_in0(G, valid, yy, xx);
             half8_t v = zero8();
-            if (kind == 0 && in0) {
-                const uint32_t sy = a.pool ? 2 * yy : yy, sx = a.pool ? 2 * xx : xx;  // (2 yy + 1 <= 2 H - 1 <= H0 - 1)
-                const half_t *src = a.s0 + (((uint64_t)n * a.H0 + sy) * a.W0 + sx) * a.C0 + ch;
-                v = ld8(src);
-                if (a.pool) {
-                    v = max8(v, ld8(src + a.C0));
-                    v = max8(v, max8(ld8(src + row0), ld8(src + row0 + a.C0)));
-                }
-            } else if (kind == 1 && in0 && yy < (int)a.H1 && xx < (int)a.W1) {
-                v = ld8(a.s1 + (((uint64_t)n * a.H1 + yy) * a.W1 + xx) * a.C1 + (ch - a.C0));
-            }
+            if (kind == 0 && in0) v = unet_ld8_src0(G, unet_tap_src0(G, q.n, yy, xx) + ch);
+            else if (kind == 1 && unet_tap_in1(G, in0, yy, xx)) v = ld8(unet_tap_src1(G, q.n, yy, xx) + (ch - G.C0));
             xr[tap] = v;
         }
     };
 
-    f32x4_t acc[9][4];
+    f32x4 acc[9][4];
 #pragma unroll
     for (int tap = 0; tap < 9; tap++)
 #pragma unroll
-        for (int j = 0; j < 4; j++) acc[tap][j] = f32x4_t{0, 0, 0, 0};
+        for (int j = 0; j < 4; j++) acc[tap][j] = f32x4{0, 0, 0, 0};
 
     fetch(begin);
     for (uint64_t base = begin; base < end; base += 32) {  // (a trip count of the workgroup: every thread takes every LDS read)
@@ -141,7 +121,7 @@ k_unet_conv_wgrad(WgradArgs a) {
         for (int tap = 0; tap < 9; tap++) {
             const half8_t af = fragment<TR>(xs[tap], 16 * wave, lane);
 #pragma unroll
-            for (int j = 0; j < 4; j++) acc[tap][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf[j], acc[tap][j], 0, 0, 0);
+            for (int j = 0; j < 4; j++) acc[tap][j] = UNET_MFMA(af, bf[j], acc[tap][j]);
         }
         __syncthreads();
     }
@@ -152,7 +132,7 @@ k_unet_conv_wgrad(WgradArgs a) {
     for (int tap = 0; tap < 9; tap++)
 #pragma unroll
         for (int j = 0; j < 4; j++)
-            *reinterpret_cast<f32x4_t *>(dst + ((uint64_t)tap * a.Cout + co0 + 16 * j + c) * Cp + ci) = acc[tap][j];
+            *reinterpret_cast<f32x4 *>(dst + ((uint64_t)tap * a.Cout + co0 + 16 * j + c) * Cp + ci) = acc[tap][j];
 }
 
 // Both finishing kernels add the slices of an element in ascending order in float64 and round once; they differ in who owns what.
@@ -201,26 +181,14 @@ k_unet_conv_wgrad_finish_wide(const float *__restrict__ part, uint32_t S, uint32
     dweight[(i % n) * 9 + tap] = (float)s;
 }
 
-struct WgSplit {
-    uint32_t S;
-    uint64_t L;
-};
-
-WgSplit conv_wgrad_split(uint64_t M, uint32_t Cp, uint32_t Cout) {
-    const uint64_t budget = kWgSliceBudget / (36ull * Cp * Cout), pieces = (M + 255) / 256;
-    const uint64_t S = pieces < budget ? pieces : (budget ? budget : 1);
-    const uint64_t L = ((M + S - 1) / S + 31) / 32 * 32;
-    return WgSplit{(uint32_t)((M + L - 1) / L), L};
-}
+UnetSplit conv_wgrad_split(uint64_t M, uint32_t Cp, uint32_t Cout) { return unet_pixel_split(M, 36ull * Cp * Cout, kWgSliceBudget); }
 
 bool conv_wgrad_shape_ok(uint32_t N, uint32_t H0, uint32_t W0, uint32_t pool, uint32_t C0, uint32_t C1, uint32_t Cout) {
-    if (pool > 1 || !N || !H0 || !W0 || (uint64_t)N * H0 * W0 > kWgMaxPixels) return false;
+    if (pool > 1 || !N || !H0 || !W0 || (uint64_t)N * H0 * W0 > kUnetMaxPixels) return false;
     if (!(pool ? H0 / 2 : H0) || !(pool ? W0 / 2 : W0)) return false;
-    const bool c0_ok = C0 == 32 ? C1 == 0 : (C0 >= 64 && C0 <= 1024 && C0 % 64 == 0 && (C1 == 0 || C1 == C0));
-    return c0_ok && Cout >= 64 && Cout <= 1024 && Cout % 64 == 0;
+    const bool c0_ok = C0 == 32 ? C1 == 0 : (unet_channels_ok(C0, 64) && (C1 == 0 || C1 == C0));
+    return c0_ok && unet_channels_ok(Cout, 64);
 }
-
-bool wg_aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -239,34 +207,27 @@ int lnh_unet_conv3x3_backward_weight(const void *src0, uint32_t C0, uint32_t H0,
     const char *what = "unet_conv3x3_backward_weight";
     LNH_REQUIRE(src0 && dz && ws && dweight, LNH_ERR_INVALID_ARG, "%s: null pointer", what);
     LNH_REQUIRE(pool <= 1, LNH_ERR_INVALID_ARG, "%s: pool %u (0 or 1)", what, pool);
-    LNH_REQUIRE(C0 == 32 || (C0 >= 64 && C0 <= 1024 && C0 % 64 == 0), LNH_ERR_INVALID_ARG,
+    LNH_REQUIRE(C0 == 32 || unet_channels_ok(C0, 64), LNH_ERR_INVALID_ARG,
                 "%s: C0 %u (32, or a multiple of 64 up to 1024)", what, C0);
     LNH_REQUIRE(C1 == 0 || (C1 == C0 && C0 != 32), LNH_ERR_INVALID_ARG, "%s: C1 %u beside C0 %u (0, or C0 where C0 is a multiple of 64)",
                 what, C1, C0);
     LNH_REQUIRE((C1 != 0) == (src1 != nullptr), LNH_ERR_INVALID_ARG, "%s: src1 and C1 must be given together", what);
-    LNH_REQUIRE(Cout >= 64 && Cout <= 1024 && Cout % 64 == 0, LNH_ERR_INVALID_ARG, "%s: Cout %u (a multiple of 64, 64 .. 1024)", what,
-                Cout);
+    UNET_REQUIRE_CHANNELS(what, "Cout", Cout, 64);
     LNH_REQUIRE(C0 == 32 ? (Cin >= 1 && Cin <= 32) : Cin == C0 + C1, LNH_ERR_INVALID_ARG,
                 "%s: Cin %u (C0 + C1 = %u; 1 .. 32 for the padded first layer, C0 = 32)", what, Cin, C0 + C1);
-    const uint32_t H = pool ? H0 / 2 : H0, W = pool ? W0 / 2 : W0;
-    LNH_REQUIRE(N && H && W && (uint64_t)N * H0 * W0 <= kWgMaxPixels, LNH_ERR_INVALID_ARG,
-                "%s: source [%u, %u, %u], pool %u (output of 1 .. 2^26 pixels)", what, N, H0, W0, pool);
-    if (C1) {
-        LNH_REQUIRE(H1 <= H && H - H1 <= 1 && W1 <= W && W - W1 <= 1 && H1 && W1, LNH_ERR_INVALID_ARG,
-                    "%s: second source %u x %u under an output of %u x %u (each 0 or 1 smaller)", what, H1, W1, H, W);
-    }
+    WgradArgs a{};
+    a.g = UnetConvGeom{(const half_t *)src0, (const half_t *)src1, 0, 0, H0, W0, C0, H1, W1, C1, pool};
+    if (int rc = unet_conv_geometry(what, N, a.g)) return rc;
     LNH_REQUIRE(variant <= LNH_UNET_WGRAD_TR, LNH_ERR_INVALID_ARG, "%s: variant %u (0, 1 or 2)", what, variant);
     const uint64_t need = lnh_unet_conv3x3_backward_weight_workspace_size(N, H0, W0, pool, C0, C1, Cout);
     LNH_REQUIRE(need && ws_bytes >= need, LNH_ERR_INVALID_ARG, "%s: workspace of %llu bytes, %llu needed", what,
                 (unsigned long long)ws_bytes, (unsigned long long)need);
-    LNH_REQUIRE(wg_aligned16(src0) && wg_aligned16(src1) && wg_aligned16(dz) && wg_aligned16(ws) && wg_aligned16(dweight),
-                LNH_ERR_INVALID_ARG, "%s: every pointer must be 16-byte aligned", what);
+    LNH_REQUIRE(aligned16(src0) && aligned16(src1) && aligned16(dz) && aligned16(ws) && aligned16(dweight), LNH_ERR_INVALID_ARG,
+                "%s: every pointer must be 16-byte aligned", what);
     const uint32_t Cp = C0 + C1;
-    WgradArgs a{};
-    a.s0 = (const half_t *)src0; a.s1 = (const half_t *)src1; a.dz = (const half_t *)dz; a.part = (float *)ws;
-    a.H = H; a.W = W; a.H0 = H0; a.W0 = W0; a.C0 = C0; a.H1 = H1; a.W1 = W1; a.C1 = C1; a.Cout = Cout; a.pool = pool;
-    a.M = (uint64_t)N * H * W;
-    const WgSplit sp = conv_wgrad_split(a.M, Cp, Cout);
+    a.dz = (const half_t *)dz; a.part = (float *)ws; a.Cout = Cout;
+    a.M = (uint64_t)N * a.g.H * a.g.W;
+    const UnetSplit sp = conv_wgrad_split(a.M, Cp, Cout);
     a.L = sp.L;
     const hipStream_t s = (hipStream_t)stream;
     const dim3 grid(sp.S, (Cp + 63) / 64, Cout / 64);

@@ -34,23 +34,28 @@ def unet_input(images, out):
     return out
 
 
-def conv3x3(src0, weight, scale, shift, out, src1=None, pool=False, tile=0):
-    """lnh_unet_conv3x3: out [N, H, W, Cout] from src0 [N, H0, W0, C0] (pool: its 2 x 2 maximum) and the optional src1
-    [N, H1, W1, C1]; weight fp16 [Cout, 9, C0 + C1], scale / shift f32 [Cout]."""
-    _nhwc(src0, "src0"), _nhwc(out, "out")
-    N, H0, W0, C0 = src0.shape
+def conv_operand(src0, src1, pool, out, what):
+    """The source arguments of the three 3 x 3 entry points, (src0, C0, H0, W0, pool, src1, C1, H1, W1) as they take them, from src0
+    [N, H0, W0, C0] (pool: its 2 x 2 maximum is read) and the optional src1 [N, H1, W1, C1]; then N, the channel count of `out` — the
+    tensor `what` of the output's size [N, H, W, .] — and whether out and src1 fit src0's batch and output size."""
+    N, H0, W0, C0 = _nhwc(src0, "src0").shape
+    Cout = _nhwc(out, what).shape[3]
     H1 = W1 = C1 = 0
     if src1 is not None:
         _, H1, W1, C1 = _nhwc(src1, "src1").shape
-    Cout = out.shape[3]
-    H, W = (H0 // 2, W0 // 2) if pool else (H0, W0)
-    if tuple(out.shape) != (N, H, W, Cout) or tuple(weight.shape) != (Cout, 9, C0 + C1) or weight.dtype != torch.float16 or \
-            scale.dtype != torch.float32 or shift.dtype != torch.float32 or scale.numel() != Cout or shift.numel() != Cout or \
-            (src1 is not None and src1.shape[0] != N):
+    fits = tuple(out.shape[:3]) == ((N, H0 // 2, W0 // 2) if pool else (N, H0, W0)) and (src1 is None or src1.shape[0] == N)
+    return (_hip.ptr(src0), C0, H0, W0, int(bool(pool)), _hip.ptr(src1), C1, H1, W1), N, Cout, fits
+
+
+def conv3x3(src0, weight, scale, shift, out, src1=None, pool=False, tile=0):
+    """lnh_unet_conv3x3: out [N, H, W, Cout] from src0 [N, H0, W0, C0] (pool: its 2 x 2 maximum) and the optional src1
+    [N, H1, W1, C1]; weight fp16 [Cout, 9, C0 + C1], scale / shift f32 [Cout]."""
+    operand, N, Cout, fits = conv_operand(src0, src1, pool, out, "out")
+    if not fits or tuple(weight.shape) != (Cout, 9, operand[1] + operand[6]) or weight.dtype != torch.float16 or \
+            scale.dtype != torch.float32 or shift.dtype != torch.float32 or scale.numel() != Cout or shift.numel() != Cout:
         raise RuntimeError("lidarnerf.unet.conv3x3: shapes of out / weight / scale / shift do not fit the sources")
     _hip.require_cuda(weight, scale, shift)
-    _hip.call("lnh_unet_conv3x3", _hip.ptr(src0), C0, H0, W0, int(bool(pool)), _hip.ptr(src1), C1, H1, W1, _hip.ptr(weight),
-              _hip.ptr(scale), _hip.ptr(shift), N, Cout, int(tile), _hip.ptr(out))
+    _hip.call("lnh_unet_conv3x3", *operand, _hip.ptr(weight), _hip.ptr(scale), _hip.ptr(shift), N, Cout, int(tile), _hip.ptr(out))
     return out
 
 
@@ -94,11 +99,65 @@ def workspace_layout(N, H, W):
     for l in range(4):
         h, w = sizes[l + 1]
         bufs += [(f"up{l}", (N, 2 * h, 2 * w, CHANNELS[l])), (f"d{l}", (N,) + sizes[l] + (CHANNELS[l],))]
+    placed, total = place([(name, shape, torch.float16) for name, shape in bufs])
+    return [e[:3] for e in placed], total
+
+
+def _nbytes(shape, dtype):
+    n = torch.empty(0, dtype=dtype).element_size()
+    for d in shape:
+        n *= d
+    return n
+
+
+def place(bufs):
+    """[(name, shape, dtype)] -> ([(name, byte offset, shape, dtype)], total bytes): one after the other, each 256-byte aligned."""
     out, off = [], 0
-    for name, shape in bufs:
-        out.append((name, off, shape))
-        off += (shape[0] * shape[1] * shape[2] * shape[3] * 2 + 255) // 256 * 256
+    for name, shape, dtype in bufs:
+        out.append((name, off, shape, dtype))
+        off += (_nbytes(shape, dtype) + 255) // 256 * 256
     return out, off
+
+
+def carve(raw, layout):
+    """{name: view} of the buffers of a layout — entries (name, byte offset, shape[, dtype]), fp16 without a dtype — in the byte
+    tensor `raw`."""
+    views = {}
+    for name, off, shape, *dtype in layout:
+        dtype = dtype[0] if dtype else torch.float16
+        views[name] = raw[off:off + _nbytes(shape, dtype)].view(dtype).view(shape)
+    return views
+
+
+def layer_table(n_channels=10, decoder_mid="mid"):
+    """The 18 convolution layers in execution order, one dict each — the one statement of the net's topology; packing, inference and
+    the training forward walk it forwards, the training backward in reverse.
+      conv, bn       state-dict prefixes of the layer's Conv2d and BatchNorm2d
+      src0, src1     buffer names of the operand; src1 None but for the concatenating layers
+      pool           src0 is max-pooled 2 x 2 on read
+      out            the activation buffer.  The first activation of decoder level l is `decoder_mid`{l}: inference reuses mid{l},
+                     training keeps dmid{l} beside it (the backward needs both)
+      level, cin (C0 + C1 of the parameter), cout
+      up             None, or for a concatenating layer the block index i of the transposed convolution up{i + 1}.up (state-dict
+                     prefix `up_name`) that makes src1 from the previous layer's activation
+      dx             the buffer that receives the layer's data gradient: the previous layer's gradient buffer g{k - 1}, dcat{l} for a
+                     concatenating layer, dpool{l} for a pooling one; None for layer 0
+      dskip          for a pooling layer: the concatenation gradient whose first channels are the skip gradient of src0."""
+    def pair(prefix, src0, src1, pool, mid, out, level, cin, dx, **more):
+        c, k = CHANNELS[level], len(layers)
+        return [dict(conv=f"{prefix}.0", bn=f"{prefix}.1", src0=src0, src1=src1, pool=pool, out=mid, level=level, cin=cin, cout=c,
+                     up=None, dx=dx, **more),
+                dict(conv=f"{prefix}.3", bn=f"{prefix}.4", src0=mid, src1=None, pool=False, out=out, level=level, cin=c, cout=c,
+                     up=None, dx=f"g{k}")]
+    layers = []
+    layers += pair("inc.double_conv", "input", None, False, "mid0", "x0", 0, n_channels, None)
+    for l in range(1, 5):
+        layers += pair(f"down{l}.maxpool_conv.1.double_conv", f"x{l - 1}", None, True, f"mid{l}", f"x{l}", l, CHANNELS[l - 1], f"dpool{l}",
+                       dskip=f"dcat{l - 1}")
+    for i, l in enumerate((3, 2, 1, 0)):
+        layers += pair(f"up{i + 1}.conv.double_conv", f"x{l}", f"up{l}", False, f"{decoder_mid}{l}", f"d{l}", l, 2 * CHANNELS[l], f"dcat{l}")
+        layers[-2].update(up=i, up_name=f"up{i + 1}.up")
+    return layers
 
 
 # ---- the module: the reference's state-dict names and shapes ----------------------------------------------------------------------
@@ -163,11 +222,6 @@ class RayDropUNet(nn.Module):
         return net.to(torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device))
 
     # -- packing --
-    def _double_convs(self):
-        """The nine DoubleConv containers in execution order: inc, down1 .. down4, up1 .. up4."""
-        return [self.inc.double_conv] + [getattr(self, f"down{i}").maxpool_conv[1].double_conv for i in range(1, 5)] + \
-            [getattr(self, f"up{i}").conv.double_conv for i in range(1, 5)]
-
     @staticmethod
     def _pack_conv(conv, bn):
         w = conv.weight.detach()
@@ -184,12 +238,10 @@ class RayDropUNet(nn.Module):
         """The fp16 weight images and fp32 scale / shift vectors the kernels read (layouts: include/lidarnerf_hip.h): one-time
         torch ops wherever the parameters live; load_state_dict and every move or cast (_apply) call it.  After changing a
         parameter in place, call it again."""
-        convs = []
-        for seq in self._double_convs():
-            convs += [self._pack_conv(seq[0], seq[1]), self._pack_conv(seq[3], seq[4])]
+        table = layer_table(self.n_channels)
+        convs = [self._pack_conv(self.get_submodule(lay["conv"]), self.get_submodule(lay["bn"])) for lay in table]
         ups = []
-        for i in range(1, 5):
-            m = getattr(self, f"up{i}").up
+        for m in (self.get_submodule(lay["up_name"]) for lay in table if lay["up"] is not None):
             w = m.weight.detach()  # [Cin, Cout, 2, 2] -> [2dy + dx, Cout, Cin]
             ups.append((w.permute(2, 3, 1, 0).reshape(4, w.shape[1], w.shape[0]).to(torch.float16).contiguous(),
                         m.bias.detach().to(torch.float32).contiguous()))
@@ -221,9 +273,7 @@ class RayDropUNet(nn.Module):
             if need == 0 or need != total:
                 raise RuntimeError(f"RayDropUNet: lnh_unet_workspace_size({N}, {H}, {W}) = {need}, the layout needs {total}")
             raw = torch.empty(total, dtype=torch.uint8, device=device)
-            views = {name: raw[off:off + shape[0] * shape[1] * shape[2] * shape[3] * 2].view(torch.float16).view(shape)
-                     for name, off, shape in layout}
-            ws = self._workspaces[key] = {"raw": raw, "views": views,
+            ws = self._workspaces[key] = {"raw": raw, "views": carve(raw, layout),
                                           "logits": torch.empty(N, 1, H, W, dtype=torch.float32, device=device),
                                           "mask": torch.empty(N, 1, H, W, dtype=torch.float32, device=device)}
         return ws
@@ -247,17 +297,11 @@ class RayDropUNet(nn.Module):
         images = images.detach().to(torch.float32).contiguous()
         ws = self._workspace(N, H, W, images.device)
         v = ws["views"]
-        unet_input(images, v["input"])
-        conv3x3(v["input"], *convs[0], v["mid0"])
-        conv3x3(v["mid0"], *convs[1], v["x0"])
-        for l in range(1, 5):
-            conv3x3(v[f"x{l - 1}"], *convs[2 * l], v[f"mid{l}"], pool=True)
-            conv3x3(v[f"mid{l}"], *convs[2 * l + 1], v[f"x{l}"])
-        cur = v["x4"]
-        for i, l in enumerate((3, 2, 1, 0)):
-            upconv2x2(cur, *ups[i], v[f"up{l}"])
-            conv3x3(v[f"x{l}"], *convs[10 + 2 * i], v[f"mid{l}"], src1=v[f"up{l}"])
-            cur = conv3x3(v[f"mid{l}"], *convs[11 + 2 * i], v[f"d{l}"])
+        cur = unet_input(images, v["input"])
+        for lay, packed in zip(layer_table(self.n_channels), convs):
+            if lay["up"] is not None:  # a decoder block begins: the transposed convolution of what came before
+                upconv2x2(cur, *ups[lay["up"]], v[lay["src1"]])
+            cur = conv3x3(v[lay["src0"]], *packed, v[lay["out"]], src1=v.get(lay["src1"]), pool=lay["pool"])
         head(cur, hw, hb, ws["logits"], ws["mask"] if want_mask else None)
         return ws
 

@@ -107,11 +107,8 @@ def head_backward(a, weight, dlogits, ws, dx, dweight, dbias):
     for t, n, what in ((dlogits, N * H * W, "dlogits"), (dweight, 64, "dweight"), (dbias, 1, "dbias")):
         if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.numel() == n):
             raise RuntimeError(f"lidarnerf.unet_train.head_backward: {what} must be f32 with {n} elements")
-    _hip.require_cuda(weight, dlogits, ws, dweight, dbias)
-    need = head_backward_workspace_bytes(N, H, W)
-    have = ws.numel() * ws.element_size()
-    if have < need:
-        raise RuntimeError(f"lidarnerf.unet_train.head_backward: the workspace holds {have} bytes, {need} needed")
+    _hip.require_cuda(weight, dlogits, dweight, dbias)
+    have = _ws_bytes(ws, head_backward_workspace_bytes(N, H, W), "head_backward")
     _hip.require_symbols(_SYMBOLS, "U-Net training")
     _hip.call("lnh_unet_head_backward", _hip.ptr(a), N, H, W, _hip.ptr(weight), _hip.ptr(dlogits), _hip.ptr(ws), have, _hip.ptr(dx),
               _hip.ptr(dweight), _hip.ptr(dbias))
@@ -170,10 +167,8 @@ def upconv2x2_backward_weight(x, dy, ws, dweight, dbias, offset=0):
     Cout = dweight.shape[1]
     if not (torch.is_tensor(dbias) and dbias.dtype == torch.float32 and dbias.numel() == Cout and dbias.is_contiguous()):
         raise RuntimeError(f"lidarnerf.unet_train.upconv2x2_backward_weight: dbias must be contiguous f32 [{Cout}]")
-    _hip.require_cuda(ws, dweight, dbias)
-    need, have = upconv2x2_backward_weight_workspace_bytes(N, H, W, Cin, Cout), ws.numel() * ws.element_size()
-    if have < need:
-        raise RuntimeError(f"lidarnerf.unet_train.upconv2x2_backward_weight: the workspace holds {have} bytes, {need} needed")
+    _hip.require_cuda(dweight, dbias)
+    have = _ws_bytes(ws, upconv2x2_backward_weight_workspace_bytes(N, H, W, Cin, Cout), "upconv2x2_backward_weight")
     _hip.require_symbols(_SYMBOLS, "U-Net training")
     _hip.call("lnh_unet_upconv2x2_backward_weight", _hip.ptr(x), _hip.ptr(dy), Hd, Wd, Cs, int(offset), N, H, W, Cin, Cout, _hip.ptr(ws),
               have, _hip.ptr(dweight), _hip.ptr(dbias))
@@ -201,20 +196,12 @@ def pack_conv3x3(weight, fwd, bwd=None):
 def conv3x3_raw(src0, weight, out, src1=None, pool=False, tile=0):
     """lnh_unet_conv3x3_raw: lidarnerf.unet.conv3x3 without scale / shift, out = fp16(acc).  With pack_conv3x3's bwd image as weight and
     dz as src0 it is the data gradient of the layer: out [N, H, W, C0 + C1]."""
-    _nhwc(src0, "src0"), _nhwc(out, "out")
-    N, H0, W0, C0 = src0.shape
-    H1 = W1 = C1 = 0
-    if src1 is not None:
-        _, H1, W1, C1 = _nhwc(src1, "src1").shape
-    Cout = out.shape[3]
-    H, W = (H0 // 2, W0 // 2) if pool else (H0, W0)
-    if tuple(out.shape) != (N, H, W, Cout) or not torch.is_tensor(weight) or tuple(weight.shape) != (Cout, 9, C0 + C1) or \
-            weight.dtype != torch.float16 or (src1 is not None and src1.shape[0] != N):
+    operand, N, Cout, fits = _unet.conv_operand(src0, src1, pool, out, "out")
+    if not fits or not torch.is_tensor(weight) or tuple(weight.shape) != (Cout, 9, operand[1] + operand[6]) or weight.dtype != torch.float16:
         raise RuntimeError("lidarnerf.unet_train.conv3x3_raw: shapes of out / weight do not fit the sources")
     _hip.require_cuda(weight)
     _hip.require_symbols(_SYMBOLS, "U-Net training")
-    _hip.call("lnh_unet_conv3x3_raw", _hip.ptr(src0), C0, H0, W0, int(bool(pool)), _hip.ptr(src1), C1, H1, W1, _hip.ptr(weight), N, Cout,
-              int(tile), _hip.ptr(out))
+    _hip.call("lnh_unet_conv3x3_raw", *operand, _hip.ptr(weight), N, Cout, int(tile), _hip.ptr(out))
     return out
 
 
@@ -321,43 +308,24 @@ def conv3x3_backward_weight(src0, dz, ws, dweight, src1=None, pool=False, varian
     layer's weight for dz fp16 [N, H, W, Cout], from the operand the forward convolution read: src0 fp16 [N, H0, W0, C0] (pooled 2 x 2
     on read with pool), then the channels of src1 fp16 [N, H1, W1, C1].  Cin = C0 + C1, or the real channel count (up to 32) of the
     padded first layer.  variant: 0, _hip.UNET_WGRAD_GATHER or _hip.UNET_WGRAD_TR (the same bits)."""
-    N, H0, W0, C0 = _nhwc(src0, "src0").shape
-    H1 = W1 = C1 = 0
-    if src1 is not None:
-        _, H1, W1, C1 = _nhwc(src1, "src1").shape
-    H, W = (H0 // 2, W0 // 2) if pool else (H0, W0)
-    Cout = _nhwc(dz, "dz").shape[3]
+    operand, N, Cout, fits = _unet.conv_operand(src0, src1, pool, dz, "dz")
     if not (torch.is_tensor(dweight) and dweight.dtype == torch.float32 and dweight.dim() == 4 and dweight.is_contiguous() and
-            dweight.shape[0] == Cout and tuple(dweight.shape[2:]) == (3, 3)) or tuple(dz.shape[:3]) != (N, H, W) or \
-            (src1 is not None and src1.shape[0] != N):
+            dweight.shape[0] == Cout and tuple(dweight.shape[2:]) == (3, 3)) or not fits:
         raise RuntimeError("lidarnerf.unet_train.conv3x3_backward_weight: dweight contiguous f32 [Cout, Cin, 3, 3], dz [N, H, W, Cout] "
                            "over the sources' batch and output size")
-    _hip.require_cuda(ws, dweight)
-    have = ws.numel() * ws.element_size()
-    need = conv3x3_backward_weight_workspace_bytes(N, H0, W0, pool, C0, C1, Cout)
-    if need and have < need:
-        raise RuntimeError(f"lidarnerf.unet_train.conv3x3_backward_weight: the workspace holds {have} bytes, {need} needed")
+    _hip.require_cuda(dweight)
+    _, C0, H0, W0, _, _, C1, _, _ = operand  # (a shape the kernel refuses needs 0 bytes here: the entry point names the fault)
+    have = _ws_bytes(ws, conv3x3_backward_weight_workspace_bytes(N, H0, W0, pool, C0, C1, Cout), "conv3x3_backward_weight")
     _hip.require_symbols(_SYMBOLS, "U-Net training")
-    _hip.call("lnh_unet_conv3x3_backward_weight", _hip.ptr(src0), C0, H0, W0, int(bool(pool)), _hip.ptr(src1), C1, H1, W1, _hip.ptr(dz), N,
-              Cout, dweight.shape[1], int(variant), _hip.ptr(ws), have, _hip.ptr(dweight))
+    _hip.call("lnh_unet_conv3x3_backward_weight", *operand, _hip.ptr(dz), N, Cout, dweight.shape[1], int(variant), _hip.ptr(ws), have,
+              _hip.ptr(dweight))
     return dweight
 
 
 # ---- the whole net in training mode ---------------------------------------------------------------------------------------------------
 def train_layers(n_channels=10):
-    """The 18 convolution layers in execution order, one dict each: `conv` / `bn` (state-dict prefixes), `src0`, `src1` (buffer names;
-    src1 None but for the concatenating layers), `pool`, `out` (the activation buffer), `level`, `cin` (C0 + C1 of the parameter) and
-    `cout`."""
-    def pair(prefix, src0, src1, pool, mid, out, level, cin):
-        c = CHANNELS[level]
-        return [dict(conv=f"{prefix}.0", bn=f"{prefix}.1", src0=src0, src1=src1, pool=pool, out=mid, level=level, cin=cin, cout=c),
-                dict(conv=f"{prefix}.3", bn=f"{prefix}.4", src0=mid, src1=None, pool=False, out=out, level=level, cin=c, cout=c)]
-    layers = pair("inc.double_conv", "input", None, False, "mid0", "x0", 0, n_channels)
-    for l in range(1, 5):
-        layers += pair(f"down{l}.maxpool_conv.1.double_conv", f"x{l - 1}", None, True, f"mid{l}", f"x{l}", l, CHANNELS[l - 1])
-    for i, l in enumerate((3, 2, 1, 0)):
-        layers += pair(f"up{i + 1}.conv.double_conv", f"x{l}", f"up{l}", False, f"dmid{l}", f"d{l}", l, 2 * CHANNELS[l])
-    return layers
+    """lidarnerf.unet.layer_table with the buffer names of training: the decoder's first activations are dmid{l}."""
+    return _unet.layer_table(n_channels, decoder_mid="dmid")
 
 
 def train_workspace_layout(N, H, W, n_channels=10):
@@ -403,14 +371,7 @@ def train_workspace_layout(N, H, W, n_channels=10):
              ("logits", (N, 1, H, W), f32)]
     bufs += [(f"dcw{k}", (lay["cout"], lay["cin"], 3, 3), f32) for k, lay in enumerate(layers)]
     bufs.append(("ws_cw", (max(_conv_wgrad_bytes(N, sizes, lay) for lay in layers),), u8))
-    out, off = [], 0
-    for name, shape, dtype in bufs:
-        n = 1
-        for d in shape:
-            n *= d
-        out.append((name, off, shape, dtype))
-        off += (n * torch.empty(0, dtype=dtype).element_size() + 255) // 256 * 256
-    return out, off
+    return _unet.place(bufs)
 
 
 def _conv_wgrad_bytes(N, sizes, lay):
@@ -430,23 +391,18 @@ def _train_state(net, N, H, W, device):
             raise RuntimeError("lidarnerf.unet_train: the workspace of a shape must exist before a call is captured (run it eagerly once)")
         layout, total = train_workspace_layout(N, H, W, net.n_channels)
         raw = torch.empty(total, dtype=torch.uint8, device=device)
-        views = {}
-        for name, off, shape, dtype in layout:
-            n = 1
-            for d in shape:
-                n *= d
-            views[name] = raw[off:off + n * torch.empty(0, dtype=dtype).element_size()].view(dtype).view(shape)
+        views = _unet.carve(raw, layout)
         layers = train_layers(net.n_channels)
         grads = {"outc.conv.weight": views["dhw"], "outc.conv.bias": views["dhb"]}
         conv_grads = {}
         for k, lay in enumerate(layers):
             conv_grads[lay["conv"] + ".weight"] = views[f"dcw{k}"]
             s = views[f"stat{k}"]
-            lay.update(index=k, operand=(views[lay["src0"]], None if lay["src1"] is None else views[lay["src1"]]), z=views[f"z{k}"],
-                       a=views[lay["out"]], dz=views[f"g{k}"], dweight=views[f"dcw{k}"], mean=s[0], invstd=s[1], scale=s[2], shift=s[3], dgamma=s[4], dbeta=s[5])
+            lay.update(index=k, operand=(views[lay["src0"]], views.get(lay["src1"])), z=views[f"z{k}"], a=views[lay["out"]], dz=views[f"g{k}"],
+                       dweight=views[f"dcw{k}"], mean=s[0], invstd=s[1], scale=s[2], shift=s[3], dgamma=s[4], dbeta=s[5])
             grads[lay["bn"] + ".weight"], grads[lay["bn"] + ".bias"] = s[4], s[5]
-        for i in range(4):
-            grads[f"up{i + 1}.up.weight"], grads[f"up{i + 1}.up.bias"] = views[f"dupw{i}"], views[f"dupb{i}"]
+        for name, i in ((lay["up_name"], lay["up"]) for lay in layers if lay["up"] is not None):
+            grads[name + ".weight"], grads[name + ".bias"] = views[f"dupw{i}"], views[f"dupb{i}"]
         # "grads": all 64 names; "grads_no_conv": the 46 a train_backward without the convolution weights fills and returns
         st = cache[key] = {"key": key, "raw": raw, "views": views, "layers": layers, "grads": {**grads, **conv_grads},
                            "grads_no_conv": grads, "logits": views["logits"]}
@@ -487,9 +443,8 @@ def train_forward(net, images, state=None):
     counters = []
     cur = None
     for k, lay in enumerate(state["layers"]):
-        if lay["src1"] is not None:  # a decoder block begins: the transposed convolution of what came before
-            i = (k - 10) // 2
-            up = net.get_submodule(f"up{i + 1}.up")
+        if lay["up"] is not None:  # a decoder block begins: the transposed convolution of what came before
+            i, up = lay["up"], net.get_submodule(lay["up_name"])
             pack_upconv(_live(up.weight, "up.weight"), v[f"uf{i}"], v[f"ub{i}"])
             _unet.upconv2x2(cur, v[f"uf{i}"], _live(up.bias, "up.bias"), v[lay["src1"]])
         conv, bn = net.get_submodule(lay["conv"]), net.get_submodule(lay["bn"])
@@ -525,30 +480,23 @@ def train_backward(net, state, dlogits, conv_weights=False):
             tuple(dlogits.shape) == (N, 1, H, W)):
         raise RuntimeError(f"lidarnerf.unet_train.train_backward: dlogits must be a contiguous f32 [{N}, 1, {H}, {W}] GPU tensor")
     grads = state["grads"] if conv_weights else state["grads_no_conv"]
-    head_backward(v["d0"], v["hw"], dlogits.detach(), v["ws_head"], v["g17"], grads["outc.conv.weight"], grads["outc.conv.bias"])
-
-    def layer_backward(k, dx):
-        lay = layers[k]
+    head_backward(layers[-1]["a"], v["hw"], dlogits.detach(), v["ws_head"], layers[-1]["dz"], grads["outc.conv.weight"],
+                  grads["outc.conv.bias"])
+    for k in range(len(layers) - 1, -1, -1):
+        lay, before = layers[k], layers[k - 1]  # (`before` is read only where a layer has one: up, pool)
+        dx = v.get(lay["dx"])
         bn_relu_backward(lay["z"], lay["a"], lay["dz"], lay["mean"], lay["invstd"], lay["scale"], v["ws_bn"], lay["dz"], lay["dgamma"],
                          lay["dbeta"])
         if conv_weights:
             conv3x3_backward_weight(lay["operand"][0], lay["dz"], v["ws_cw"], lay["dweight"], src1=lay["operand"][1], pool=lay["pool"])
         if dx is not None:
             conv3x3_raw(lay["dz"], v[f"wb{k}"], dx)
-
-    for i in (3, 2, 1, 0):  # up4 .. up1: level l = 3 - i
-        l, k = 3 - i, 10 + 2 * i
-        layer_backward(k + 1, v[f"g{k}"])
-        layer_backward(k, v[f"dcat{l}"])
-        x, dx = (v["x4"], v["g9"]) if i == 0 else (v[f"d{l + 1}"], v[f"g{k - 1}"])
-        upconv2x2_backward_weight(x, v[f"dcat{l}"], v["ws_up"], v[f"dupw{i}"], v[f"dupb{i}"], offset=CHANNELS[l])
-        upconv2x2_backward_data(v[f"dcat{l}"], v[f"ub{i}"], dx, offset=CHANNELS[l])
-    for l in (4, 3, 2, 1):  # down4 .. down1
-        layer_backward(2 * l + 1, v[f"g{2 * l}"])
-        layer_backward(2 * l, v[f"dpool{l}"])
-        pool_backward(v[f"x{l - 1}"], v[f"dpool{l}"], v[f"g{2 * l - 1}"], dskip=v[f"dcat{l - 1}"])
-    layer_backward(1, v["g0"])
-    layer_backward(0, None)
+        if lay["up"] is not None:  # dx is the concatenation's gradient: its second half is the transposed convolution's, read in place
+            i, half = lay["up"], lay["cin"] // 2
+            upconv2x2_backward_weight(before["a"], dx, v["ws_up"], v[f"dupw{i}"], v[f"dupb{i}"], offset=half)
+            upconv2x2_backward_data(dx, v[f"ub{i}"], before["dz"], offset=half)
+        if lay["pool"]:
+            pool_backward(lay["operand"][0], dx, before["dz"], dskip=v[lay["dskip"]])
     return grads
 
 

@@ -276,3 +276,40 @@ def test_integer_problems_are_exact():
         a, b = R.integer_unet_forward(sd, x), R.integer_unet_forward(sd, x, quantize=True)
         assert torch.equal(a, b) and float(a.abs().max()) < 2 ** 24
         assert a.unique().numel() > 100 and float((a != 0).double().mean()) > 0.5  # the net is alive
+
+
+def test_host_answers_are_as_recorded():
+    """Every lnh_unet_* entry point with each argument it refuses (and calls wrong in two ways, which pin the order of the checks):
+    return code and lnh_last_error() text; every *_workspace_size function on the levels of the shapes the layout tests use and on
+    what it answers 0 for — the table of tests/unet_host_cases.py against tests/golden/unet_host.json, recorded from the library
+    of the commit named in that file.  No call reaches a launch: the record holds a refusal for each one, which is asserted before
+    anything is called."""
+    import json
+
+    import unet_host_cases as cases
+    from lidarnerf import _hip
+    with open(os.path.join(GOLDEN, "unet_host.json")) as f:
+        rec = json.load(f)
+    lib = _hip.lib()
+    assert lib.lnh_version() == rec["recorded_from"]["lnh_version"]
+    want = rec["refusals"]
+    names = [name for name, _, _ in cases.calls()]
+    assert set(names) == set(want) and len(names) == len(set(names)) >= 400
+    assert all(a["rc"] == INVALID_ARG == cases.INVALID_ARG and a["error"] for a in want.values())
+    unet_exports = {n for n in _hip.EXPORTS if n.startswith("lnh_unet_")}
+    assert {n for n in unet_exports if not n.endswith("_workspace_size")} == set(cases.BASES) == set(cases.WRONG)
+    assert all(sum("+" in case for case in cases.WRONG[fn]) >= 2 for fn in cases.WRONG)
+    got = cases.refusal_answers(lib, only=set(want))
+    for name in sorted(want):
+        assert got[name] == want[name], (name, got[name], want[name])
+    sizes = rec["sizes"]
+    assert {fn for _, fn, _ in cases.size_calls()} == {n for n in unet_exports if n.endswith("_workspace_size")}
+    got = cases.size_answers(lib)
+    assert set(got) == set(sizes)
+    for name in sorted(sizes):
+        assert got[name] == sizes[name], (name, got[name], sizes[name])
+    # the record itself holds what it is meant to pin: nothing but the listed shapes answers 0, and no size function touches the error
+    for name, a in sizes.items():
+        dead = "/zero/" in name or ("/1x16x16/" in name and name.startswith("lnh_unet_bn_") and name.endswith(("layer8", "layer9")))
+        assert (a["bytes"] == 0) == dead, name
+    assert len({a["error"] for a in sizes.values()}) == 1
