@@ -4,6 +4,7 @@
 // mlp_common.h for the register-resident layer chaining and the fp16 / bf16 element-type builds
 // (lidar_color_bf16.hip compiles this file again with bf16 MFMA operands: entry points lnh_lidar_color_*_bf16).
 #include "mlp_common.h"
+#include "transmittance.h"
 #include "wgrad.h"
 #include <type_traits>
 
@@ -154,12 +155,12 @@ k_color_forward(ColorArgs a) {
 // compositing sums (k_lidar_composite_fwd: weights_sum, depth = sum w z, image = sum w rgb).  The three kernels it
 // replaces each walked the ray at HBM latency and handed weights / rgb to the next through HBM; here the weights and
 // the permutation of the ray stay in LDS between the scan and the colour head (6.6 KB per wave at 832 samples).
-// sigma_m, weights and rgb are still written: the backward pass reads them.  weights_sum and depth are summed in the
-// order of k_lidar_composite_fwd (bit-identical); image is summed by the lanes that hold the colours (same value to fp32
-// rounding).
+// sigma_m, weights and rgb are still written: the backward pass reads them.  Step 1 is the walk of transmittance.h, the
+// one k_merge_weights and k_lidar_composite_fwd take, and weights_sum and depth are summed in the order of
+// k_lidar_composite_fwd (bit-identical); image is summed by the lanes that hold the colours (same value to fp32 rounding).
 __global__ void __launch_bounds__(256)
 k_color_forward_ray(ColorArgs a) {
-    constexpr int HT = 4, HS = 2, NT = 4, kChunks = 7;
+    constexpr int HT = 4, HS = 2, NT = 4;
     extern __shared__ __attribute__((aligned(16))) char smem_ray[];
     const uint32_t wid = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
     const uint32_t nw = blockDim.x >> 6, nwaves = gridDim.x * nw;
@@ -184,29 +185,17 @@ k_color_forward_ray(ColorArgs a) {
         for (uint32_t base0 = 0; base0 < a.T; base0 += 64 * kChunks) {
             float zi[kChunks], zn[kChunks], sg[kChunks];
             int32_t pi[kChunks];
-#pragma unroll
-            for (int u = 0; u < kChunks; u++) {
-                const uint32_t i = base0 + u * 64 + lane, ic = i < a.T ? i : 0, in = i + 1 < a.T ? i + 1 : ic;
-                pi[u] = pr[ic];
-                zi[u] = zr[ic];
-                zn[u] = zr[in];
-            }
+            load_chunks(zr, base0, a.T, lane, zi, zn, [&](int u, uint32_t ic) { pi[u] = pr[ic]; });
 #pragma unroll
             for (int u = 0; u < kChunks; u++) sg[u] = sp[pi[u]];
 #pragma unroll
             for (int u = 0; u < kChunks; u++) {
                 const uint32_t i = base0 + u * 64 + lane;
                 if (base0 + u * 64 >= a.T) break;  // wave-uniform
-                float alpha = 0.0f, om = 1.0f;
-                if (i < a.T) {
-                    const float delta = (i + 1 < a.T) ? (zn[u] - zi[u]) : sd;
-                    alpha = 1.0f - expf(-delta * a.density_scale * sg[u]);
-                    om = 1.0f - alpha + 1e-15f;
-                }
-                const float incl = wave_scan_mul(om, (int)lane);
-                float excl = __shfl_up(incl, 1, 64);
-                if (lane == 0) excl = 1.0f;
-                const float w = alpha * (carry * excl);
+                Alpha al;
+                if (i < a.T) al = alpha_of(zi[u], zn[u], i + 1 < a.T, sg[u], sd, a.density_scale);
+                const WalkStep s = walk_step(al.om, carry, (int)lane);
+                const float w = al.alpha * s.T;
                 if (i < a.T) {
                     a.sigma_m[(size_t)ray * a.T + i] = sg[u];
                     a.weights_out[(size_t)ray * a.T + i] = w;
@@ -215,7 +204,7 @@ k_color_forward_ray(ColorArgs a) {
                 }
                 ws += w;
                 dep += i < a.T ? w * zi[u] : 0.0f;
-                carry *= __shfl(incl, 63, 64);
+                carry = walk_carry(s);
             }
         }
         ws = wave_sum(ws);

@@ -22,6 +22,7 @@
 // free.  The per-ray sum of d(hidden0) gives the gradient of the direction part of W0 after one small GEMM.
 #include "common.h"
 #include "lidar_steps.h"
+#include "transmittance.h"
 
 namespace {
 
@@ -68,40 +69,27 @@ k_merge_weights(const float *__restrict__ z, const float *__restrict__ sigma_pt,
     const float *sp = sigma_pt + (size_t)ray * T;
     const int32_t *pr = perm + (size_t)ray * T;
     const float sd = sample_dist[ray];
-    // kChunks 64-sample chunks are requested at once (perm, z, then the gathered sigma) and scanned from registers:
-    // one dependent round trip per chunk made this one-wave-per-ray kernel run at HBM latency (see lidar_render.hip)
-    constexpr int kChunks = 7;
+    // kChunks 64-sample chunks are requested at once (perm, z, then the gathered sigma) and scanned from registers; the
+    // walk itself is transmittance.h's, the one k_lidar_weights takes: same bits for the same merged samples
     float carry = 1.0f;
     for (uint32_t base0 = 0; base0 < T; base0 += 64 * kChunks) {
         float zi[kChunks], zn[kChunks], sg[kChunks];
         int32_t pi[kChunks];
-#pragma unroll
-        for (int u = 0; u < kChunks; u++) {
-            const uint32_t i = base0 + u * 64 + lane, ic = i < T ? i : 0, in = i + 1 < T ? i + 1 : ic;
-            pi[u] = pr[ic];
-            zi[u] = zr[ic];
-            zn[u] = zr[in];
-        }
+        load_chunks(zr, base0, T, lane, zi, zn, [&](int u, uint32_t ic) { pi[u] = pr[ic]; });
 #pragma unroll
         for (int u = 0; u < kChunks; u++) sg[u] = sp[pi[u]];
 #pragma unroll
         for (int u = 0; u < kChunks; u++) {
             const uint32_t i = base0 + u * 64 + lane;
             if (base0 + u * 64 >= T) break;  // wave-uniform
-            float alpha = 0.0f, om = 1.0f;
-            if (i < T) {
-                const float delta = (i + 1 < T) ? (zn[u] - zi[u]) : sd;
-                alpha = 1.0f - expf(-delta * density_scale * sg[u]);
-                om = 1.0f - alpha + 1e-15f;
-            }
-            const float incl = wave_scan_mul(om, lane);
-            float excl = __shfl_up(incl, 1, 64);
-            if (lane == 0) excl = 1.0f;
+            Alpha a;
+            if (i < T) a = alpha_of(zi[u], zn[u], i + 1 < T, sg[u], sd, density_scale);
+            const WalkStep s = walk_step(a.om, carry, lane);
             if (i < T) {
                 sigma_m[(size_t)ray * T + i] = sg[u];
-                weights[(size_t)ray * T + i] = alpha * (carry * excl);
+                weights[(size_t)ray * T + i] = a.alpha * s.T;
             }
-            carry *= __shfl(incl, 63, 64);
+            carry = walk_carry(s);
         }
     }
 }

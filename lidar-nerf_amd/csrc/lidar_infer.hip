@@ -16,6 +16,7 @@
 // No float atomics anywhere: two runs give the same bits.  Built with -ffp-contract=off (see raymarch.hip).
 #include "common.h"
 #include "march_cell.h"
+#include "transmittance.h"
 
 namespace {
 
@@ -173,16 +174,9 @@ k_lidar_composite_rays(uint32_t n_alive_max, uint32_t n_step, uint32_t N, uint32
         const uint32_t step = base + gl;
         const bool in = !stopped && step < count;
         const size_t i = (size_t)offset + (in ? step : 0);
-        float alpha = 0.0f, z = 0.0f, f[K];
-#pragma unroll
-        for (int k = 0; k < K; k++) f[k] = 0.0f;
-        if (in) {
-            alpha = 1.0f - expf(-sigmas[i] * deltas[i * 2]);
-            z = (xyzs[i * 3] - ox) * dx + (xyzs[i * 3 + 1] - oy) * dy + (xyzs[i * 3 + 2] - oz) * dz;
-#pragma unroll
-            for (int k = 0; k < K; k++) f[k] = feats[i * K + k];
-        }
-        float incl = 1.0f - alpha;  // multiplicative scan inside the group
+        const RaySample<K> s = load_ray_sample<K>(in, i, sigmas, feats, deltas, xyzs, ox, oy, oz, dx, dy, dz);
+        // the sample load is the training compositors'; the scan is not walk_step: W is a run-time width inside a wave
+        float incl = 1.0f - s.alpha;  // multiplicative scan inside the group
         for (uint32_t o = 1; o < W; o <<= 1) {
             const float u = __shfl_up(incl, o, 64);
             if (gl >= o) incl *= u;
@@ -193,11 +187,11 @@ k_lidar_composite_rays(uint32_t n_alive_max, uint32_t n_step, uint32_t N, uint32
         // stop after the first sample that takes T below the threshold
         const unsigned long long stop = (__ballot(in && Tn < T_thresh) >> gshift) & gmask;
         const uint32_t last = stop ? (uint32_t)__builtin_ctzll(stop) : W - 1;
-        const float w = (in && gl <= last) ? alpha * T : 0.0f;
+        const float w = (in && gl <= last) ? s.alpha * T : 0.0f;
         ws += w;
-        d += w * z;
+        d += w * s.z;
 #pragma unroll
-        for (int k = 0; k < K; k++) acc[k] += w * f[k];
+        for (int k = 0; k < K; k++) acc[k] += w * s.f[k];
         const float Tnext = __shfl(Tn, (int)(gshift + last), 64);
         if (!stopped) Tc = Tnext;
         if (stop) stopped = true;

@@ -5,47 +5,18 @@
 //   * samples are consumed in rounds of 64 (lane = sample within the round), so every global load/store of the
 //     wave is one contiguous 256 B segment;
 //   * the transmittance prod_{j<i}(1 - alpha_j + 1e-15) is an inclusive product scan inside the wave (shuffle
-//     ladder) with a scalar carry between rounds — no [N,T+1] cumprod tensor ever reaches HBM;
+//     ladder) with a scalar carry between rounds — no [N,T+1] cumprod tensor ever reaches HBM.  The alpha rule, the
+//     round of that walk and the seven-chunk prefetch live in transmittance.h, shared with lidar_field.hip,
+//     lidar_color.hip and raymarch.hip: the kernels agree bit for bit because they run the same definitions;
 //   * depth / image / weight sums are lane-partial accumulators reduced once per ray;
 //   * backward recomputes the scan and uses  dL/dalpha_i = T_i c_i - (sum_{j>i} w_j c_j) / (1 - alpha_i + 1e-15),
 //     the same quotient form torch.cumprod's autograd uses; it includes the DEPTH gradient (the reference's CUDA
 //     compositor drops it, raymarching.py:330, but the LiDAR loss is depth dominated and the PyTorch path keeps it);
 //   * resampling (stage-1 weights -> pdf -> cdf -> inverse-cdf lookup -> sort -> merge) keeps the ray's cdf and z in
 //     LDS; the merge is rank arithmetic on two sorted runs, not a 832-element sort.
-#include "common.h"
+#include "transmittance.h"
 
 namespace {
-
-constexpr float kEps = 1e-15f;  // renderer.py:189,241
-
-struct RoundVals {
-    float z, alpha, om, w;
-};
-
-// alpha/omega of sample i (renderer.py:233-241)
-__device__ __forceinline__ void sample_alpha(const float *__restrict__ z, const float *__restrict__ sigma, uint32_t i,
-                                             uint32_t T, float sample_dist, float density_scale, float &zi,
-                                             float &delta, float &alpha, float &om, float &e) {
-    zi = z[i];
-    const float zn = (i + 1 < T) ? z[i + 1] : 0.0f;
-    delta = (i + 1 < T) ? (zn - zi) : sample_dist;
-    e = expf(-delta * density_scale * sigma[i]);
-    alpha = 1.0f - e;
-    om = 1.0f - alpha + kEps;
-}
-
-// The same from values already in registers (zn = z[i+1], ignored for the last sample).
-__device__ __forceinline__ void alpha_of(float zi, float zn, bool has_next, float sg, float sample_dist,
-                                         float density_scale, float &delta, float &alpha, float &om, float &e) {
-    delta = has_next ? (zn - zi) : sample_dist;
-    e = expf(-delta * density_scale * sg);
-    alpha = 1.0f - e;
-    om = 1.0f - alpha + kEps;
-}
-// The per-ray kernels below are one wave per ray walking the ray in 64-sample chunks with a scan carry: left as a plain
-// loop every chunk pays its own HBM round trip (13 dependent ones at 832 samples — the kernels ran at that latency, not
-// at bandwidth).  They therefore request kChunks chunks at once and scan them from registers.
-constexpr int kChunks = 7;
 
 // ------------------------------------------------------------------------------------------------ weights only
 __global__ void __launch_bounds__(256)
@@ -60,13 +31,11 @@ k_lidar_weights(const float *__restrict__ z, const float *__restrict__ sigma, co
     float carry = 1.0f;
     for (uint32_t base = 0; base < T; base += 64) {
         const uint32_t i = base + lane;
-        float zi = 0, delta, alpha = 0.0f, om = 1.0f, e;
-        if (i < T) sample_alpha(zr, sr, i, T, sd, density_scale, zi, delta, alpha, om, e);
-        const float incl = wave_scan_mul(om, lane);
-        float excl = __shfl_up(incl, 1, 64);
-        if (lane == 0) excl = 1.0f;
-        if (i < T) wr[i] = alpha * (carry * excl);
-        carry *= __shfl(incl, 63, 64);
+        Alpha a;
+        if (i < T) a = alpha_of(zr[i], i + 1 < T ? zr[i + 1] : 0.0f, i + 1 < T, sr[i], sd, density_scale);
+        const WalkStep s = walk_step(a.om, carry, lane);
+        if (i < T) wr[i] = a.alpha * s.T;
+        carry = walk_carry(s);
     }
 }
 
@@ -89,31 +58,25 @@ k_lidar_composite_fwd(const float *__restrict__ z, const float *__restrict__ sig
     for (int k = 0; k < K; k++) img[k] = 0.0f;
     for (uint32_t base0 = 0; base0 < T; base0 += 64 * kChunks) {
         float zi[kChunks], zn[kChunks], sg[kChunks], c[kChunks][K];
-#pragma unroll
-        for (int u = 0; u < kChunks; u++) {
-            const uint32_t i = base0 + u * 64 + lane, ic = i < T ? i : 0, in = i + 1 < T ? i + 1 : ic;
-            zi[u] = zr[ic];
-            zn[u] = zr[in];
+        load_chunks(zr, base0, T, lane, zi, zn, [&](int u, uint32_t ic) {
             sg[u] = sr[ic];
 #pragma unroll
             for (int k = 0; k < K; k++) c[u][k] = cr[(size_t)ic * K + k];
-        }
+        });
 #pragma unroll
         for (int u = 0; u < kChunks; u++) {
             const uint32_t i = base0 + u * 64 + lane;
             if (base0 + u * 64 >= T) break;  // wave-uniform
-            float delta, alpha = 0.0f, om = 1.0f, e;
-            if (i < T) alpha_of(zi[u], zn[u], i + 1 < T, sg[u], sd, density_scale, delta, alpha, om, e);
-            const float incl = wave_scan_mul(om, lane);
-            float excl = __shfl_up(incl, 1, 64);
-            if (lane == 0) excl = 1.0f;
-            const float w = alpha * (carry * excl);
+            Alpha a;
+            if (i < T) a = alpha_of(zi[u], zn[u], i + 1 < T, sg[u], sd, density_scale);
+            const WalkStep s = walk_step(a.om, carry, lane);
+            const float w = a.alpha * s.T;
             if (i < T && wr) wr[i] = w;
             ws += w;
             dep += i < T ? w * zi[u] : 0.0f;
 #pragma unroll
             for (int k = 0; k < K; k++) img[k] += i < T ? w * c[u][k] : 0.0f;
-            carry *= __shfl(incl, 63, 64);
+            carry = walk_carry(s);
         }
     }
     ws = wave_sum(ws);
@@ -149,13 +112,10 @@ k_lidar_composite_bwd(const float *__restrict__ g_ws, const float *__restrict__ 
 #pragma unroll
     for (int k = 0; k < K; k++) gim[k] = g_image ? g_image[(size_t)ray * K + k] : 0.0f;
 
-    auto load_chunks = [&](uint32_t base0, float (&zi)[kChunks], float (&zn)[kChunks], float (&sg)[kChunks],
-                           float (&ci)[kChunks]) {
-#pragma unroll
-        for (int u = 0; u < kChunks; u++) {
-            const uint32_t i = base0 + u * 64 + lane, ic = i < T ? i : 0, in = i + 1 < T ? i + 1 : ic;
-            zi[u] = zr[ic];
-            zn[u] = zr[in];
+    // the chunks of both passes: z, sigma and c_i = g_ws + g_depth z_i + sum_k g_img_k rgb_ik
+    auto load = [&](uint32_t base0, float (&zi)[kChunks], float (&zn)[kChunks], float (&sg)[kChunks],
+                    float (&ci)[kChunks]) {
+        load_chunks(zr, base0, T, lane, zi, zn, [&](int u, uint32_t ic) {
             sg[u] = sr[ic];
             float c[K];
 #pragma unroll
@@ -163,24 +123,22 @@ k_lidar_composite_bwd(const float *__restrict__ g_ws, const float *__restrict__ 
             ci[u] = gws + gdp * zi[u];
 #pragma unroll
             for (int k = 0; k < K; k++) ci[u] += gim[k] * c[k];
-        }
+        });
     };
-    // pass 1: total = sum_i w_i c_i with c_i = g_ws + g_depth z_i + sum_k g_img_k rgb_ik
+    // pass 1: total = sum_i w_i c_i
     float carry = 1.0f, total = 0.0f;
     for (uint32_t base0 = 0; base0 < T; base0 += 64 * kChunks) {
         float zi[kChunks], zn[kChunks], sg[kChunks], ci[kChunks];
-        load_chunks(base0, zi, zn, sg, ci);
+        load(base0, zi, zn, sg, ci);
 #pragma unroll
         for (int u = 0; u < kChunks; u++) {
             const uint32_t i = base0 + u * 64 + lane;
             if (base0 + u * 64 >= T) break;  // wave-uniform
-            float delta, alpha = 0.0f, om = 1.0f, e;
-            if (i < T) alpha_of(zi[u], zn[u], i + 1 < T, sg[u], sd, density_scale, delta, alpha, om, e);
-            const float incl = wave_scan_mul(om, lane);
-            float excl = __shfl_up(incl, 1, 64);
-            if (lane == 0) excl = 1.0f;
-            total += i < T ? alpha * (carry * excl) * ci[u] : 0.0f;
-            carry *= __shfl(incl, 63, 64);
+            Alpha a;
+            if (i < T) a = alpha_of(zi[u], zn[u], i + 1 < T, sg[u], sd, density_scale);
+            const WalkStep s = walk_step(a.om, carry, lane);
+            total += i < T ? a.alpha * s.T * ci[u] : 0.0f;
+            carry = walk_carry(s);
         }
     }
     total = wave_sum(total);
@@ -190,31 +148,28 @@ k_lidar_composite_bwd(const float *__restrict__ g_ws, const float *__restrict__ 
     float pref_carry = 0.0f;
     for (uint32_t base0 = 0; base0 < T; base0 += 64 * kChunks) {
         float zi[kChunks], zn[kChunks], sg[kChunks], ci[kChunks];
-        load_chunks(base0, zi, zn, sg, ci);
+        load(base0, zi, zn, sg, ci);
 #pragma unroll
         for (int u = 0; u < kChunks; u++) {
             const uint32_t i = base0 + u * 64 + lane;
             if (base0 + u * 64 >= T) break;  // wave-uniform
-            float delta = 0.0f, alpha = 0.0f, om = 1.0f, e = 1.0f;
-            if (i < T) alpha_of(zi[u], zn[u], i + 1 < T, sg[u], sd, density_scale, delta, alpha, om, e);
+            Alpha a;
+            if (i < T) a = alpha_of(zi[u], zn[u], i + 1 < T, sg[u], sd, density_scale);
             const float cu = i < T ? ci[u] : 0.0f;
-            const float incl = wave_scan_mul(om, lane);
-            float excl = __shfl_up(incl, 1, 64);
-            if (lane == 0) excl = 1.0f;
-            const float Ti = carry * excl;
-            const float w = alpha * Ti;
+            const WalkStep s = walk_step(a.om, carry, lane);
+            const float w = a.alpha * s.T;
             const float wc = w * cu;
             const float pref = pref_carry + wave_scan_add(wc, lane);  // inclusive prefix of w c
             if (i < T) {
                 const float suffix = total - pref;  // sum_{j>i} w_j c_j
-                const float dalpha = Ti * cu - suffix / om;
-                gs[i] = dalpha * (delta * density_scale * e);  // d alpha / d sigma = delta * s * exp(-delta s sigma)
+                const float dalpha = s.T * cu - suffix / a.om;
+                gs[i] = dalpha * (a.delta * density_scale * a.e);  // d alpha / d sigma = delta * s * exp(-delta s sigma)
                 if (gc) {
 #pragma unroll
                     for (int k = 0; k < K; k++) gc[(size_t)i * K + k] = w * gim[k];
                 }
             }
-            carry *= __shfl(incl, 63, 64);
+            carry = walk_carry(s);
             pref_carry = __shfl(pref, 63, 64);
         }
     }
@@ -258,18 +213,15 @@ k_lidar_resample(const float *__restrict__ z, const float *__restrict__ sigma, c
     float carry = 1.0f, wsum = 0.0f;
     for (uint32_t base = 0; base < T; base += 64) {
         const uint32_t i = base + lane;
-        float zi = 0, delta, alpha = 0.0f, om = 1.0f, e;
-        if (i < T) sample_alpha(zs, sg, i, T, sd, density_scale, zi, delta, alpha, om, e);
-        const float incl = wave_scan_mul(om, lane);
-        float excl = __shfl_up(incl, 1, 64);
-        if (lane == 0) excl = 1.0f;
-        const float w = alpha * (carry * excl);
+        Alpha a;
+        if (i < T) a = alpha_of(zs[i], i + 1 < T ? zs[i + 1] : 0.0f, i + 1 < T, sg[i], sd, density_scale);
+        const WalkStep s = walk_step(a.om, carry, lane);
         if (i >= 1 && i + 1 < T) {
-            const float wp = w + 1e-5f;  // renderer.py:17
+            const float wp = a.alpha * s.T + 1e-5f;  // renderer.py:17
             cdf[i] = wp;
             wsum += wp;
         }
-        carry *= __shfl(incl, 63, 64);
+        carry = walk_carry(s);
     }
     wsum = wave_sum(wsum);
     __syncthreads();

@@ -8,6 +8,7 @@
 #include "common.h"
 #include "march_cell.h"
 #include "scan.h"
+#include "transmittance.h"
 
 namespace {
 
@@ -473,15 +474,8 @@ k_composite_train_bwd(const float *__restrict__ grad_ws, const float *__restrict
 // the running sums the backward needs out of additive scans, the early stop out of a ballot.  (Round 4: the thread-per-ray
 // form of these two kernels — the reference's shape, raymarching.cu:577-772 — ran 4096 rays as 64 single-wave workgroups
 // with ~77 dependent iterations each: 41 + 33 us per step of the NeRF-MVL-shaped bench, latency from end to end.)
-__device__ __forceinline__ float wave_scan_mul(float v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float u = __shfl_up(v, o, 64);
-        if (lane >= o) v *= u;
-    }
-    return v;
-}
-
+// The round of the walk is transmittance.h's, the one the dense compositors take, here without the epsilon; the sample
+// load is shared with the alive-ray evaluation (lidar_infer.hip).
 template <int K>
 __global__ void __launch_bounds__(256)
 k_lidar_composite_ragged_fwd(const float *__restrict__ sigmas, const float *__restrict__ feats,
@@ -505,29 +499,18 @@ k_lidar_composite_ragged_fwd(const float *__restrict__ sigmas, const float *__re
             const uint32_t step = base + lane;
             const bool in = step < num_steps;
             const size_t i = (size_t)offset + (in ? step : 0);
-            float alpha = 0.0f, z = 0.0f, f[K];
-#pragma unroll
-            for (int k = 0; k < K; k++) f[k] = 0.0f;
-            if (in) {
-                alpha = 1.0f - expf(-sigmas[i] * deltas[i * 2]);
-                z = (xyzs[i * 3] - ox) * dx + (xyzs[i * 3 + 1] - oy) * dy + (xyzs[i * 3 + 2] - oz) * dz;
-#pragma unroll
-                for (int k = 0; k < K; k++) f[k] = feats[i * K + k];
-            }
-            const float incl = wave_scan_mul(1.0f - alpha, lane);
-            float excl = __shfl_up(incl, 1, 64);
-            if (lane == 0) excl = 1.0f;
-            const float T = Tc * excl, Tn = Tc * incl;  // T_i, T_{i+1}
+            const RaySample<K> s = load_ray_sample<K>(in, i, sigmas, feats, deltas, xyzs, ox, oy, oz, dx, dy, dz);
+            const WalkStep t = walk_step(1.0f - s.alpha, Tc, lane);
             // stop after the first sample that takes T below the threshold
-            const unsigned long long stop = __ballot(in && Tn < T_thresh);
+            const unsigned long long stop = __ballot(in && t.Tn < T_thresh);
             const int last = stop ? __ffsll(stop) - 1 : 63;
-            const float w = (in && lane <= last) ? alpha * T : 0.0f;
+            const float w = (in && lane <= last) ? s.alpha * t.T : 0.0f;
             ws += w;
-            d += w * z;
+            d += w * s.z;
 #pragma unroll
-            for (int k = 0; k < K; k++) acc[k] += w * f[k];
+            for (int k = 0; k < K; k++) acc[k] += w * s.f[k];
             if (stop) break;
-            Tc = __shfl(Tn, 63, 64);
+            Tc = walk_carry(t);
         }
         ws = wave_sum(ws);
         d = wave_sum(d);
@@ -573,37 +556,25 @@ k_lidar_composite_ragged_bwd(const float *__restrict__ grad_ws, const float *__r
         const uint32_t step = base + lane;
         const bool in = step < num_steps;
         const size_t i = (size_t)offset + (in ? step : 0);
-        float alpha = 0.0f, z = 0.0f, dt = 0.0f, f[K];
-#pragma unroll
-        for (int k = 0; k < K; k++) f[k] = 0.0f;
-        if (in) {
-            dt = deltas[i * 2];
-            alpha = 1.0f - expf(-sigmas[i] * dt);
-            z = (xyzs[i * 3] - ox) * dx + (xyzs[i * 3 + 1] - oy) * dy + (xyzs[i * 3 + 2] - oz) * dz;
-#pragma unroll
-            for (int k = 0; k < K; k++) f[k] = feats[i * K + k];
-        }
-        const float incl = wave_scan_mul(1.0f - alpha, lane);
-        float excl = __shfl_up(incl, 1, 64);
-        if (lane == 0) excl = 1.0f;
-        const float T = Tc * excl, Tn = Tc * incl;
-        const unsigned long long stop = __ballot(in && Tn < T_thresh);
+        const RaySample<K> s = load_ray_sample<K>(in, i, sigmas, feats, deltas, xyzs, ox, oy, oz, dx, dy, dz);
+        const WalkStep t = walk_step(1.0f - s.alpha, Tc, lane);
+        const unsigned long long stop = __ballot(in && t.Tn < T_thresh);
         const int last = stop ? __ffsll(stop) - 1 : 63;
         const bool use = in && lane <= last;
-        const float w = use ? alpha * T : 0.0f;
-        const float d = dc + wave_scan_add(w * z, lane);  // sum_{j <= i} w_j z_j
-        float g = gws * (1.0f - ws_final) + gd * (Tn * z - (d_final - d));
+        const float w = use ? s.alpha * t.T : 0.0f;
+        const float d = dc + wave_scan_add(w * s.z, lane);  // sum_{j <= i} w_j z_j
+        float g = gws * (1.0f - ws_final) + gd * (t.Tn * s.z - (d_final - d));
 #pragma unroll
         for (int k = 0; k < K; k++) {
-            const float a = accc[k] + wave_scan_add(w * f[k], lane);
-            g += gi[k] * (Tn * f[k] - (fin[k] - a));
+            const float a = accc[k] + wave_scan_add(w * s.f[k], lane);
+            g += gi[k] * (t.Tn * s.f[k] - (fin[k] - a));
             if (use) grad_feats[i * K + k] = gi[k] * w;
             accc[k] = __shfl(a, 63, 64);
         }
-        if (use) grad_sigmas[i] = dt * g;
+        if (use) grad_sigmas[i] = s.dt * g;
         if (stop) break;
         dc = __shfl(d, 63, 64);
-        Tc = __shfl(Tn, 63, 64);
+        Tc = walk_carry(t);
     }
 }
 

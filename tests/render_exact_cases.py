@@ -1,7 +1,8 @@
 """Problems and references of tests/test_render_exact_gpu.py (NumPy only; conditions, coverage and sensitivity are asserted
 without a GPU by tests/test_render_exact_cpu.py): the per-ray scan kernels of csrc/lidar_render.hip (lnh_lidar_weights,
 lnh_lidar_composite_forward / _backward, lnh_lidar_resample*) and their relatives in csrc/lidar_field.hip
-(lnh_lidar_merge_weights, lnh_lidar_sample_points, lnh_lidar_coarse_sample_points).
+(lnh_lidar_merge_weights, lnh_lidar_sample_points, lnh_lidar_coarse_sample_points).  The walk they share — alpha rule, round of
+the product scan, seven-round prefetch — is defined once, in csrc/transmittance.h.
 
 TIER A — one right float32 value in any scan order.  The library is built with -ffp-contract=off and expf is the only operation of
 these kernels that IEEE does not pin; the only values of expf every implementation agrees on are expf(-0) = 1 and expf(x) = 0 for
@@ -21,9 +22,9 @@ import numpy as np
 
 F = np.float32
 U = 2.0 ** -24                 # unit roundoff of float32
-EPS = F(1e-15)                 # kEps of csrc/lidar_render.hip
+EPS = F(1e-15)                 # kTransEps of csrc/transmittance.h
 OPAQUE = float(2 ** 20)
-ROUND, CHUNKS, WG_RAYS = 64, 7, 4
+ROUND, CHUNKS, WG_RAYS = 64, 7, 4  # (CHUNKS: kChunks of csrc/transmittance.h)
 GROUP = ROUND * CHUNKS         # 448 samples are requested at once
 LATTICE = 2.0 ** -10
 

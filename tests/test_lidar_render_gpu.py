@@ -46,6 +46,55 @@ def test_weights_and_composite_forward(N, T):
     torch.testing.assert_close(img.cpu(), (w_ref[..., None] * rgb).sum(-2), rtol=1e-5, atol=1e-6)
 
 
+@pytest.mark.parametrize("T", [1, 2, 65, 449, 897])
+def test_every_dense_walker_returns_the_same_weights(T):
+    """lnh_lidar_weights, lnh_lidar_composite_forward, lnh_lidar_merge_weights (identity perm) and
+    lnh_lidar_color_composite_forward walk a ray with the one definition of csrc/transmittance.h: the same weights bit for
+    bit on general alphas (the exact known-answer tests use alpha in {0, 1}, which cannot tell alpha * (carry * excl) from
+    (alpha * carry) * excl), and equal weights_sum / depth from the two compositing entry points.  N = 5: the second
+    workgroup holds a lone ray; T = 449 / 897: one sample past one / two groups of seven 64-sample rounds."""
+    from gpu_util import call
+    N, ds = 5, 2.0
+    g = torch.Generator().manual_seed(100 + T)
+    z = torch.sort(torch.rand(N, T, generator=g) * 0.8 + 0.01, dim=1)[0]
+    sigma = torch.rand(N, T, generator=g) * 4
+    sd = 0.8 / T * (1 + torch.arange(N, dtype=torch.float32) / 8)
+    # the data is not degenerate: the float64 restatement of the weights has general alphas and visible weights everywhere
+    z64, s64 = z.double().numpy(), sigma.double().numpy()
+    delta = np.concatenate([np.diff(z64, axis=1), sd.double().numpy()[:, None]], axis=1)
+    alpha = 1.0 - np.exp(-delta * ds * s64)
+    trans = np.cumprod(np.concatenate([np.ones((N, 1)), 1.0 - alpha + 1e-15], axis=1), axis=1)
+    w64 = alpha * trans[:, :-1]
+    assert (w64 > 1e-8).mean() >= 0.95
+    if T >= 2:
+        assert ((alpha > 1e-6) & (alpha < 0.999)).mean() >= 0.95
+    if T >= 65:
+        assert trans[:, -1].min() > 0.03
+
+    zc, sc, sdc = z.cuda(), sigma.cuda(), sd.cuda()
+    perm = torch.arange(T, dtype=torch.int32).expand(N, T).contiguous().cuda()
+    h16 = (torch.randn(N * T, 16, generator=g) * 0.5).half().cuda()
+    cdir = torch.randn(N, 64, generator=g).cuda()
+    w16 = (torch.randn(64 * 16 + 64 * 64 + 16 * 64, generator=g) * 0.2).half().cuda()
+    rgb = torch.rand(N, T, 2, generator=g).cuda()
+
+    def new(*shape):
+        return torch.full(shape, float("nan"), device="cuda")
+    w_a, w_b, w_c, w_d = new(N, T), new(N, T), new(N, T), new(N, T)
+    ws_b, dp_b, im_b, ws_d, dp_d, im_d = new(N), new(N), new(N, 2), new(N), new(N), new(N, 2)
+    sig_c, sig_d, rgb_d = new(N, T), new(N, T), new(N, T, 2)
+    call("lnh_lidar_weights", zc, sc, sdc, N, T, ds, w_a)
+    call("lnh_lidar_composite_forward", zc, sc, rgb, sdc, N, T, 2, ds, w_b, ws_b, dp_b, im_b)
+    call("lnh_lidar_merge_weights", zc, sc, perm, sdc, N, T, ds, sig_c, w_c)
+    call("lnh_lidar_color_composite_forward", zc, sc, perm, sdc, h16, cdir, w16, N, T, ds, sig_d, w_d, rgb_d, ws_d, dp_d, im_d)
+    # they are the weights, not merely equal.  float32 against float64: alpha = 1 - e is two roundings near 1 (2 * 2^-24
+    # absolute), T_i a product of up to 897 rounded factors (897 * 2^-24 = 5.4e-5 relative)
+    np.testing.assert_allclose(w_a.cpu().numpy(), w64, rtol=1e-4, atol=2e-7)
+    assert torch.equal(w_b, w_a) and torch.equal(w_c, w_a) and torch.equal(w_d, w_a)
+    assert torch.equal(sig_c, sc) and torch.equal(sig_d, sc)
+    assert torch.equal(ws_d, ws_b) and torch.equal(dp_d, dp_b)
+
+
 @pytest.mark.parametrize("K", [1, 2, 3])
 def test_composite_backward_matches_autograd(K):
     from gpu_util import call
