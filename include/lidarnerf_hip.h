@@ -533,6 +533,8 @@ LNH_API int lnh_lidar_merge_weights(const float *z, const float *sigma_pt, const
  *   alpha_i*(i-gi)^2) with predictions/targets masked by gt ray-drop; gt [N,3] = (raydrop, intensity, depth); also
  *   writes d loss/d depth [N] and d loss/d image [N,2], multiplied by *grad_scale when grad_scale != NULL (the loss
  *   scale of the training step: backward() then has nothing left to multiply).  `loss` need not be cleared.
+ *   grad_depth / grad_image may be NULL (each on its own): that gradient is not written — the value alone, for a step whose
+ *   gradients lnh_lidar_color_composite_forward_train has formed.
  */
 LNH_API int lnh_lidar_coarse_samples(const float *u, uint32_t N, uint32_t T, float near, float far, float *z,
                                      lnh_stream_t stream);
@@ -682,6 +684,29 @@ LNH_API int lnh_lidar_color_composite_forward(const float *z, const float *sigma
                                               const void *w16, uint32_t N, uint32_t T, float density_scale,
                                               float *sigma_m, float *weights, float *rgb, float *weights_sum,
                                               float *depth, float *image, lnh_stream_t stream);
+/*
+ * lnh_lidar_color_composite_forward_train: the same forward tail for a TRAINING step under the default loss (nerf/utils.py:
+ * 712-746 = lnh_lidar_loss, one ray per patch) — weights, weights_sum, depth and image of lnh_lidar_color_composite_forward
+ * with the same bits (sigma_m and rgb, which only the compositing backward read, stay in the workgroup's LDS and are NOT
+ * written), and then, in the wave that has just finished the ray n:
+ *   grad_image[n,:], d loss / d depth[n] — lnh_lidar_loss's gradients of that ray (a closed form of depth[n], image[n,:],
+ *     gt[n,:] = (raydrop, intensity, depth), N and the three alphas; times *grad_scale when grad_scale != NULL; sign(0) = 0),
+ *   grad_sigma[n,:] — lnh_lidar_composite_backward (K = 2, grad_weights_sum = NULL, grad_rgb = NULL) on those two, the
+ *     adjoint of renderer.py:217-298's weights / depth / image,
+ * both bit-identical to the chain lnh_lidar_color_composite_forward -> lnh_lidar_loss -> lnh_lidar_composite_backward (the
+ * kernels share the per-ray loss and the two passes of the adjoint as device functions: same expressions, same lane <->
+ * sample mapping, same summation order; the adjoint takes alpha_i and T_i as the forward walk of the same wave formed
+ * them instead of walking the ray again).  The backward pass then starts at lnh_lidar_color_backward_image.  The loss
+ * VALUE is not formed here: call lnh_lidar_loss on depth / image with grad_depth = grad_image = NULL.  T <= 2048.
+ * (Added without moving lnh_version: detect by symbol.)
+ */
+LNH_API int lnh_lidar_color_composite_forward_train(const float *z, const float *sigma_pt, const int32_t *perm,
+                                                    const float *sample_dist, const void *h16, const float *cdir,
+                                                    const void *w16, uint32_t N, uint32_t T, float density_scale,
+                                                    const float *gt, float alpha_d, float alpha_r, float alpha_i,
+                                                    const float *grad_scale, float *weights, float *weights_sum,
+                                                    float *depth, float *image, float *grad_sigma, float *grad_image,
+                                                    lnh_stream_t stream);
 /*
  * lnh_lidar_color_backward: grad_rgb [N,T,2], grad_sigma [N,T] (merged order, from lnh_lidar_composite_backward)
  * -> grad_h16 [N*T,16] fp16 in POINT order (col 0 = grad_sigma * exp(clamp(pre,-15,15)), activation.py:17-19;
@@ -1419,6 +1444,13 @@ LNH_API int lnh_lidar_color_composite_forward_bf16(const float *z, const float *
                                                    const void *w16, uint32_t N, uint32_t T, float density_scale,
                                                    float *sigma_m, float *weights, float *rgb, float *weights_sum,
                                                    float *depth, float *image, lnh_stream_t stream);
+LNH_API int lnh_lidar_color_composite_forward_train_bf16(const float *z, const float *sigma_pt, const int32_t *perm,
+                                                         const float *sample_dist, const void *h16, const float *cdir,
+                                                         const void *w16, uint32_t N, uint32_t T, float density_scale,
+                                                         const float *gt, float alpha_d, float alpha_r, float alpha_i,
+                                                         const float *grad_scale, float *weights, float *weights_sum,
+                                                         float *depth, float *image, float *grad_sigma,
+                                                         float *grad_image, lnh_stream_t stream);
 LNH_API int lnh_lidar_color_backward_bf16(const float *grad_rgb, const float *grad_sigma, const void *h16,
                                      const int32_t *perm, const float *weights, const float *cdir, const void *w16,
                                      uint32_t N, uint32_t T, void *grad_h16, float *grad_w, float *ray_sum,

@@ -4,6 +4,8 @@
 // mlp_common.h for the register-resident layer chaining and the fp16 / bf16 element-type builds
 // (lidar_color_bf16.hip compiles this file again with bf16 MFMA operands: entry points lnh_lidar_color_*_bf16).
 #include "mlp_common.h"
+#include "composite_adjoint.h"
+#include "lidar_loss_ray.h"
 #include "transmittance.h"
 #include "wgrad.h"
 #include <type_traits>
@@ -39,6 +41,12 @@ struct ColorArgs {
     float *sigma_m;         // out [N,T] densities in merged order
     float *weights_out;     // out [N,T]
     float *wsum, *depth, *image;  // out [N], [N], [N,2]
+    // training variant of the forward tail (k_color_forward_ray<true>): the default loss's gradient of the ray and the
+    // compositing adjoint follow the ray's forward in the same wave
+    const float *gt;          // [N,3] (raydrop, intensity, depth)
+    const float *grad_scale;  // device scalar the loss gradients are multiplied by, or null
+    float a_d, a_r, a_i;
+    float *gs_out, *gi_out;   // out [N,T] d loss / d sigma (merged order), [N,2] d loss / d image
     // ragged rays (occupancy-grid sampling, BASELINE config 4): the samples of ray-table entry r are the rows
     // rays[3r+1] .. + rays[3r+2] of the flat [M, *] buffers, in order (no permutation, no weight mask: every marched
     // sample lies in an occupied cell), rays[3r] is the ray's index into the per-ray buffers (cdir, S)
@@ -158,14 +166,61 @@ k_color_forward(ColorArgs a) {
 // sigma_m, weights and rgb are still written: the backward pass reads them.  Step 1 is the walk of transmittance.h, the
 // one k_merge_weights and k_lidar_composite_fwd take, and weights_sum and depth are summed in the order of
 // k_lidar_composite_fwd (bit-identical); image is summed by the lanes that hold the colours (same value to fp32 rounding).
+// TRAIN: with the default loss in 1 x 1 mode d loss / d (depth, image) of a ray is a closed form of that ray's own outputs
+// (lidar_loss_ray.h), so the wave goes on to the compositing adjoint of its ray (composite_adjoint.h: the two passes of
+// k_lidar_composite_bwd<2>, bit for bit) and writes g_sigma and g_image: the backward pass then starts at the colour head,
+// without the 26 us launch that re-read z, sigma_m and rgb from HBM twice.  The adjoint re-takes no walk: step 1 leaves
+// T_i and e_i = exp(-delta_i s sigma_i) of every sample in LDS (the weight of a sample is (1 - e_i) T_i, the product step 1
+// itself forms), the colour head leaves the two colours there (in the slot word it has consumed and one more), and only z is
+// read again.  4 x T words per wave instead of 2 x T: 53 KB per workgroup at 832 samples, three workgroups per CU as the
+// registers allow anyway.  sigma_m and rgb are not written at all — nothing else reads them in a training step.
+// (Re-walking the ray from sigma_m and rgb read back out of L2, as the stand-alone kernel does from HBM, cost the tail
+// more than the launch it saved: profiles/train_tail.txt.)
+struct AdjointStash {
+    static constexpr bool kBatched = true;
+    const float *zr;           // [T] merged depths (global)
+    const float *Tl, *el;      // [T] T_i, e_i (LDS)
+    const uint32_t *c0l;       // [T] colour 0, as bits (LDS)
+    const float *c1l;          // [T] colour 1 (LDS)
+    float sd, density_scale, gws, gdp, gim0, gim1;
+    uint32_t T;
+    int lane;
+    float zi[kChunks], zn[kChunks];
+
+    __device__ __forceinline__ void begin() {}
+    // only z comes from memory and is requested kChunks rounds ahead; the stash is read where it is used (LDS latency)
+    __device__ __forceinline__ void load(uint32_t base0) {
+        load_chunks(zr, base0, T, lane, zi, zn, [](int, uint32_t) {});
+    }
+    // (the expressions of AdjointWalk::load for c_i, K = 2, and of alpha_of for what the stash does not hold; a padding
+    //  lane has alpha = 0 and reads sample 0's T)
+    __device__ __forceinline__ AdjointSample sample(int u, uint32_t i) const {
+        const uint32_t ic = i < T ? i : 0;
+        const float e = el[ic], c0 = __uint_as_float(c0l[ic]), c1 = c1l[ic];
+        float ci = gws + gdp * zi[u];
+        ci += gim0 * c0;
+        ci += gim1 * c1;
+        const float alpha = i < T ? 1.0f - e : 0.0f;
+        const float delta = i + 1 < T ? (zn[u] - zi[u]) : sd;
+        return {alpha, 1.0f - alpha + kTransEps, Tl[ic], delta * density_scale * e, ci};
+    }
+};
+
+template <bool TRAIN>
 __global__ void __launch_bounds__(256)
 k_color_forward_ray(ColorArgs a) {
     constexpr int HT = 4, HS = 2, NT = 4;
     extern __shared__ __attribute__((aligned(16))) char smem_ray[];
-    const uint32_t wid = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
+    uint32_t wid = threadIdx.x >> 6;
+    // (TRAIN: known wave-uniform — the four LDS rows and the ray's addresses stay in scalar registers, which keeps the
+    //  training form at the three waves per SIMD of the inference form)
+    if constexpr (TRAIN) wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)wid);
+    const uint32_t lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
     const uint32_t nw = blockDim.x >> 6, nwaves = gridDim.x * nw;
-    float *wl = reinterpret_cast<float *>(smem_ray) + (size_t)wid * 2 * a.T;   // this wave's weights [T]
-    uint32_t *sl = reinterpret_cast<uint32_t *>(wl + a.T);                     // ... and slots [T]
+    // this wave's weights [T] (TRAIN: T_i) and slots [T] (TRAIN: colour 0 once the span is through the colour head)
+    float *wl = reinterpret_cast<float *>(smem_ray) + (size_t)wid * (TRAIN ? 4 : 2) * a.T;
+    uint32_t *sl = reinterpret_cast<uint32_t *>(wl + a.T);
+    float *el = wl + 2 * (size_t)a.T, *c1l = wl + 3 * (size_t)a.T;  // (TRAIN) e_i, colour 1
     half8_t w0[HT], w1[HT][HS], w2[HS];
 #pragma unroll
     for (int t = 0; t < HT; t++) {
@@ -197,9 +252,14 @@ k_color_forward_ray(ColorArgs a) {
                 const WalkStep s = walk_step(al.om, carry, (int)lane);
                 const float w = al.alpha * s.T;
                 if (i < a.T) {
-                    a.sigma_m[(size_t)ray * a.T + i] = sg[u];
                     a.weights_out[(size_t)ray * a.T + i] = w;
-                    wl[i] = w;
+                    if constexpr (TRAIN) {
+                        wl[i] = s.T;
+                        el[i] = al.e;
+                    } else {
+                        a.sigma_m[(size_t)ray * a.T + i] = sg[u];
+                        wl[i] = w;
+                    }
                     sl[i] = (uint32_t)pi[u];
                 }
                 ws += w;
@@ -222,17 +282,26 @@ k_color_forward_ray(ColorArgs a) {
             for (int n = 0; n < NT; n++) {
                 const uint32_t i = s0 + 16 * n + c;
                 valid[n] = i < a.T;
-                wgt[n] = valid[n] ? wl[i] : 0.0f;
+                if constexpr (TRAIN) wgt[n] = valid[n] ? (1.0f - el[i]) * wl[i] : 0.0f;  // = alpha * T, as step 1 formed it
+                else wgt[n] = valid[n] ? wl[i] : 0.0f;
                 slot[n] = valid[n] ? sl[i] : 0u;
                 msk[n] = wgt[n] > kMaskThresh;
                 any |= msk[n];
             }
-            float *rgb_row = a.rgb + ((size_t)ray * a.T + s0) * 2;
+            // (TRAIN: the colours stay in LDS for the adjoint — every lane has read its slots of the span above)
+            auto store_rgb = [&](int n, float r0, float r1) {
+                if constexpr (TRAIN) {
+                    sl[s0 + 16 * n + c] = __float_as_uint(r0);
+                    c1l[s0 + 16 * n + c] = r1;
+                } else {
+                    *reinterpret_cast<float2 *>(a.rgb + ((size_t)ray * a.T + s0 + 16 * n + c) * 2) = make_float2(r0, r1);
+                }
+            };
             if (!__any(any)) {  // whole span transparent: colour is defined as 0 there
                 if (g == 0) {
 #pragma unroll
                     for (int n = 0; n < NT; n++)
-                        if (valid[n]) *reinterpret_cast<float2 *>(rgb_row + (16 * n + c) * 2) = make_float2(0.0f, 0.0f);
+                        if (valid[n]) store_rgb(n, 0.0f, 0.0f);
                 }
                 continue;
             }
@@ -266,7 +335,7 @@ k_color_forward_ray(ColorArgs a) {
                     // the unfused path rounds the MLP output to fp16 before the sigmoid (autocast Linear output)
                     const float r0 = msk[n] ? sigmoidf((float)(half_t)o[0]) : 0.0f;
                     const float r1 = msk[n] ? sigmoidf((float)(half_t)o[1]) : 0.0f;
-                    *reinterpret_cast<float2 *>(rgb_row + (16 * n + c) * 2) = make_float2(r0, r1);
+                    store_rgb(n, r0, r1);
                     img0 += wgt[n] * r0;
                     img1 += wgt[n] * r1;
                 }
@@ -282,6 +351,17 @@ k_color_forward_ray(ColorArgs a) {
             a.wsum[ray] = ws;
             a.depth[ray] = dep;
             *reinterpret_cast<float2 *>(a.image + (size_t)ray * 2) = make_float2(img0, img1);
+        }
+        if constexpr (TRAIN) {
+            // ---- 3) the loss gradient of the ray from the values lane 0 has just stored, and the compositing adjoint
+            const float im0 = __shfl(img0, 0, 64), im1 = __shfl(img1, 0, 64);
+            const float gsc = a.grad_scale ? *a.grad_scale : 1.0f;
+            const RayLoss rl = lidar_loss_ray(dep, im0, im1, a.gt[(size_t)ray * 3], a.gt[(size_t)ray * 3 + 1],
+                                              a.gt[(size_t)ray * 3 + 2], a.N, a.a_d, a.a_r, a.a_i, gsc);
+            if (lane == 0) *reinterpret_cast<float2 *>(a.gi_out + (size_t)ray * 2) = make_float2(rl.g_image0, rl.g_image1);
+            const float gim[2] = {rl.g_image0, rl.g_image1};
+            AdjointStash src{zr, wl, el, sl, c1l, sd, a.density_scale, 0.0f, rl.g_depth, gim[0], gim[1], a.T, (int)lane};
+            composite_adjoint_passes<2>(src, a.T, gim, (int)lane, a.gs_out + (size_t)ray * a.T, nullptr);
         }
     }
 }
@@ -796,25 +876,61 @@ int LNH_MLP_FN(lnh_lidar_color_forward)(const void *h16, const int32_t *perm, co
     return lnh_check_launch("lnh_lidar_color_forward");
 }
 
-int LNH_MLP_FN(lnh_lidar_color_composite_forward)(const float *z, const float *sigma_pt, const int32_t *perm,
-                                                  const float *sample_dist, const void *h16, const float *cdir,
-                                                  const void *w16, uint32_t N, uint32_t T, float density_scale,
-                                                  float *sigma_m, float *weights, float *rgb, float *weights_sum,
-                                                  float *depth, float *image, lnh_stream_t stream) {
-    LNH_REQUIRE(z && sigma_pt && perm && sample_dist && h16 && cdir && w16 && sigma_m && weights && rgb && weights_sum &&
-                    depth && image, LNH_ERR_INVALID_ARG, "lidar_color_composite_forward: null pointer");
+// the forward tail; `train` (null: inference): the loss inputs and gradient outputs of the training variant
+static int color_composite_forward_launch(const char *what, const float *z, const float *sigma_pt, const int32_t *perm,
+                                          const float *sample_dist, const void *h16, const float *cdir, const void *w16,
+                                          uint32_t N, uint32_t T, float density_scale, float *sigma_m, float *weights,
+                                          float *rgb, float *weights_sum, float *depth, float *image, const ColorArgs *train,
+                                          lnh_stream_t stream) {
+    LNH_REQUIRE(z && sigma_pt && perm && sample_dist && h16 && cdir && w16 && (train || (sigma_m && rgb)) && weights &&
+                    weights_sum && depth && image, LNH_ERR_INVALID_ARG, "%s: null pointer", what);
     if (N == 0 || T == 0) return LNH_OK;
-    LNH_REQUIRE((uint64_t)N * T < 0xffffffffull, LNH_ERR_UNSUPPORTED, "lidar_color_composite_forward: N*T must fit 32 bits");
-    const size_t lds = (size_t)4 * 2 * T * sizeof(float);  // weights + slots of the four rays of a workgroup
-    LNH_REQUIRE(lds <= 64 * 1024, LNH_ERR_UNSUPPORTED,
-                "lidar_color_composite_forward: T=%u needs %zu B of LDS (> 64 KiB); use the three separate entry points", T, lds);
+    LNH_REQUIRE((uint64_t)N * T < 0xffffffffull, LNH_ERR_UNSUPPORTED, "%s: N*T must fit 32 bits", what);
+    // weights + slots of the four rays of a workgroup; training: T_i, e_i, slots / colour 0, colour 1
+    const size_t lds = (size_t)4 * (train ? 4 : 2) * T * sizeof(float);
+    LNH_REQUIRE(T <= 2048, LNH_ERR_UNSUPPORTED,
+                "%s: T=%u needs %zu B of LDS (T <= 2048); use the three separate entry points", what, T, lds);
+    if (lds > 64 * 1024)  // (training only: 128 KiB at T = 2048, of the CU's 160)
+        (void)hipFuncSetAttribute((const void *)k_color_forward_ray<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     ColorArgs a{};
     a.h16 = (const half_t *)h16; a.perm = perm; a.cdir = cdir; a.W = (const half_t *)w16; a.rgb = rgb; a.N = N; a.T = T;
     a.z = z; a.sigma_pt = sigma_pt; a.sample_dist = sample_dist; a.density_scale = density_scale;
     a.sigma_m = sigma_m; a.weights_out = weights; a.wsum = weights_sum; a.depth = depth; a.image = image;
     const uint32_t wgs = (N + 3) / 4;
-    LNH_LAUNCH(k_color_forward_ray, dim3(wgs < 4096 ? wgs : 4096), dim3(256), lds, (hipStream_t)stream, a);
-    return lnh_check_launch("lnh_lidar_color_composite_forward");
+    if (train) {
+        a.gt = train->gt; a.grad_scale = train->grad_scale; a.a_d = train->a_d; a.a_r = train->a_r; a.a_i = train->a_i;
+        a.gs_out = train->gs_out; a.gi_out = train->gi_out;
+        LNH_LAUNCH(k_color_forward_ray<true>, dim3(wgs < 4096 ? wgs : 4096), dim3(256), lds, (hipStream_t)stream, a);
+    } else {
+        LNH_LAUNCH(k_color_forward_ray<false>, dim3(wgs < 4096 ? wgs : 4096), dim3(256), lds, (hipStream_t)stream, a);
+    }
+    return lnh_check_launch(what);
+}
+
+int LNH_MLP_FN(lnh_lidar_color_composite_forward)(const float *z, const float *sigma_pt, const int32_t *perm,
+                                                  const float *sample_dist, const void *h16, const float *cdir,
+                                                  const void *w16, uint32_t N, uint32_t T, float density_scale,
+                                                  float *sigma_m, float *weights, float *rgb, float *weights_sum,
+                                                  float *depth, float *image, lnh_stream_t stream) {
+    return color_composite_forward_launch("lnh_lidar_color_composite_forward", z, sigma_pt, perm, sample_dist, h16, cdir, w16,
+                                          N, T, density_scale, sigma_m, weights, rgb, weights_sum, depth, image, nullptr,
+                                          stream);
+}
+
+int LNH_MLP_FN(lnh_lidar_color_composite_forward_train)(const float *z, const float *sigma_pt, const int32_t *perm,
+                                                        const float *sample_dist, const void *h16, const float *cdir,
+                                                        const void *w16, uint32_t N, uint32_t T, float density_scale,
+                                                        const float *gt, float alpha_d, float alpha_r, float alpha_i,
+                                                        const float *grad_scale, float *weights, float *weights_sum,
+                                                        float *depth, float *image, float *grad_sigma,
+                                                        float *grad_image, lnh_stream_t stream) {
+    LNH_REQUIRE(gt && grad_sigma && grad_image, LNH_ERR_INVALID_ARG, "lnh_lidar_color_composite_forward_train: null pointer");
+    ColorArgs t{};
+    t.gt = gt; t.grad_scale = grad_scale; t.a_d = alpha_d; t.a_r = alpha_r; t.a_i = alpha_i;
+    t.gs_out = grad_sigma; t.gi_out = grad_image;
+    return color_composite_forward_launch("lnh_lidar_color_composite_forward_train", z, sigma_pt, perm, sample_dist, h16, cdir,
+                                          w16, N, T, density_scale, nullptr, weights, nullptr, weights_sum, depth, image, &t,
+                                          stream);
 }
 
 // second launch of the colour backward: the workgroups' partials [W2: 4 tiles | W1: 16 tiles | W0g: 4 tiles] added up in

@@ -2,6 +2,7 @@
 // launches per step (renderer.py:129-161 sampling set-up, network.py:215-221 direction term, nerf/utils.py:712-746
 // loss).  Each is one launch here; none of them is bandwidth- or compute-relevant, the point is the launch count.
 #include "common.h"
+#include "lidar_loss_ray.h"
 #include "lidar_steps.h"
 #include "wgrad.h"
 
@@ -223,15 +224,15 @@ k_lidar_loss(const float *__restrict__ depth, const float *__restrict__ image, c
     const float gsc = grad_scale ? *grad_scale : 1.0f;
     float l = 0.0f;
     for (uint32_t n = threadIdx.x; n < N; n += kLossThreads) {
-        const float gr = gt[n * 3], gi = gt[n * 3 + 1] * gr, gd = gt[n * 3 + 2] * gr;
-        const float pr = image[n * 2], pi = image[n * 2 + 1] * gr, pd = depth[n] * gr;
-        const float dd = pd - gd, dr = pr - gr, di = pi - gi;
-        l += a_d * fabsf(dd) + a_r * dr * dr + a_i * di * di;
-        const float inv = 1.0f / (float)N;
-        const float sgn = dd > 0.0f ? 1.0f : (dd < 0.0f ? -1.0f : 0.0f);  // torch: sign(0) = 0
-        g_depth[n] = a_d * sgn * gr * inv * gsc;
-        g_image[n * 2] = 2.0f * a_r * dr * inv * gsc;
-        g_image[n * 2 + 1] = 2.0f * a_i * di * gr * inv * gsc;
+        // (the ray's term and gradients: lidar_loss_ray.h, shared with the training forward tail in lidar_color.hip)
+        const RayLoss r = lidar_loss_ray(depth[n], image[n * 2], image[n * 2 + 1], gt[n * 3], gt[n * 3 + 1], gt[n * 3 + 2], N,
+                                         a_d, a_r, a_i, gsc);
+        l += r.l;
+        if (g_depth) g_depth[n] = r.g_depth;
+        if (g_image) {
+            g_image[n * 2] = r.g_image0;
+            g_image[n * 2 + 1] = r.g_image1;
+        }
     }
     loss_finish(l, 1.0f / (float)N, loss);
 }
@@ -689,8 +690,8 @@ int lnh_lidar_pack_weights_bf16(const float *ws0, uint32_t ld_s0, const float *w
 int lnh_lidar_loss(const float *depth, const float *image, const float *gt, uint32_t N, float alpha_d, float alpha_r,
                    float alpha_i, const float *grad_scale, float *loss, float *grad_depth, float *grad_image,
                    lnh_stream_t stream) {
-    LNH_REQUIRE(depth && image && gt && loss && grad_depth && grad_image, LNH_ERR_INVALID_ARG,
-                "lidar_loss: null pointer");
+    // (grad_depth / grad_image may be null: the training forward tail has formed the gradients, only the value is wanted)
+    LNH_REQUIRE(depth && image && gt && loss, LNH_ERR_INVALID_ARG, "lidar_loss: null pointer");
     LNH_REQUIRE(N <= (1u << 26), LNH_ERR_UNSUPPORTED, "lidar_loss: at most 2^26 rays per call");
     if (N == 0) return lnh_zero_async(loss, sizeof(float), (hipStream_t)stream, "lidar_loss (no rays)");
     LNH_LAUNCH(k_lidar_loss, dim3(1), dim3(kLossThreads), 0, (hipStream_t)stream, depth, image, gt, N, alpha_d,

@@ -14,6 +14,7 @@
 //     compositor drops it, raymarching.py:330, but the LiDAR loss is depth dominated and the PyTorch path keeps it);
 //   * resampling (stage-1 weights -> pdf -> cdf -> inverse-cdf lookup -> sort -> merge) keeps the ray's cdf and z in
 //     LDS; the merge is rank arithmetic on two sorted runs, not a 832-element sort.
+#include "composite_adjoint.h"
 #include "transmittance.h"
 
 namespace {
@@ -112,67 +113,11 @@ k_lidar_composite_bwd(const float *__restrict__ g_ws, const float *__restrict__ 
 #pragma unroll
     for (int k = 0; k < K; k++) gim[k] = g_image ? g_image[(size_t)ray * K + k] : 0.0f;
 
-    // the chunks of both passes: z, sigma and c_i = g_ws + g_depth z_i + sum_k g_img_k rgb_ik
-    auto load = [&](uint32_t base0, float (&zi)[kChunks], float (&zn)[kChunks], float (&sg)[kChunks],
-                    float (&ci)[kChunks]) {
-        load_chunks(zr, base0, T, lane, zi, zn, [&](int u, uint32_t ic) {
-            sg[u] = sr[ic];
-            float c[K];
+    // both passes of the ray: composite_adjoint.h (the training forward tail in lidar_color.hip runs the same passes)
+    AdjointWalk<K> src{zr, sr, cr, sd, density_scale, gws, gdp, {}, T, lane};
 #pragma unroll
-            for (int k = 0; k < K; k++) c[k] = cr[(size_t)ic * K + k];
-            ci[u] = gws + gdp * zi[u];
-#pragma unroll
-            for (int k = 0; k < K; k++) ci[u] += gim[k] * c[k];
-        });
-    };
-    // pass 1: total = sum_i w_i c_i
-    float carry = 1.0f, total = 0.0f;
-    for (uint32_t base0 = 0; base0 < T; base0 += 64 * kChunks) {
-        float zi[kChunks], zn[kChunks], sg[kChunks], ci[kChunks];
-        load(base0, zi, zn, sg, ci);
-#pragma unroll
-        for (int u = 0; u < kChunks; u++) {
-            const uint32_t i = base0 + u * 64 + lane;
-            if (base0 + u * 64 >= T) break;  // wave-uniform
-            Alpha a;
-            if (i < T) a = alpha_of(zi[u], zn[u], i + 1 < T, sg[u], sd, density_scale);
-            const WalkStep s = walk_step(a.om, carry, lane);
-            total += i < T ? a.alpha * s.T * ci[u] : 0.0f;
-            carry = walk_carry(s);
-        }
-    }
-    total = wave_sum(total);
-
-    // pass 2: prefix of w c, gradients
-    carry = 1.0f;
-    float pref_carry = 0.0f;
-    for (uint32_t base0 = 0; base0 < T; base0 += 64 * kChunks) {
-        float zi[kChunks], zn[kChunks], sg[kChunks], ci[kChunks];
-        load(base0, zi, zn, sg, ci);
-#pragma unroll
-        for (int u = 0; u < kChunks; u++) {
-            const uint32_t i = base0 + u * 64 + lane;
-            if (base0 + u * 64 >= T) break;  // wave-uniform
-            Alpha a;
-            if (i < T) a = alpha_of(zi[u], zn[u], i + 1 < T, sg[u], sd, density_scale);
-            const float cu = i < T ? ci[u] : 0.0f;
-            const WalkStep s = walk_step(a.om, carry, lane);
-            const float w = a.alpha * s.T;
-            const float wc = w * cu;
-            const float pref = pref_carry + wave_scan_add(wc, lane);  // inclusive prefix of w c
-            if (i < T) {
-                const float suffix = total - pref;  // sum_{j>i} w_j c_j
-                const float dalpha = s.T * cu - suffix / a.om;
-                gs[i] = dalpha * (a.delta * density_scale * a.e);  // d alpha / d sigma = delta * s * exp(-delta s sigma)
-                if (gc) {
-#pragma unroll
-                    for (int k = 0; k < K; k++) gc[(size_t)i * K + k] = w * gim[k];
-                }
-            }
-            carry = walk_carry(s);
-            pref_carry = __shfl(pref, 63, 64);
-        }
-    }
+    for (int k = 0; k < K; k++) src.gim[k] = gim[k];
+    composite_adjoint_passes<K>(src, T, gim, lane, gs, gc);
 }
 
 // ------------------------------------------------------------------------------------------------ resample + merge

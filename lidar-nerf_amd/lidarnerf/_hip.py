@@ -67,6 +67,7 @@ _SIGS = {
     "lnh_lidar_merge_weights": [P, P, P, P, U32, U32, F32, P, P],
     "lnh_lidar_color_forward": [P, P, P, P, P, U32, U32, P],
     "lnh_lidar_color_composite_forward": [P, P, P, P, P, P, P, U32, U32, F32, P, P, P, P, P, P],
+    "lnh_lidar_color_composite_forward_train": [P, P, P, P, P, P, P, U32, U32, F32, P, F32, F32, F32, P, P, P, P, P, P, P],
     "lnh_lidar_coarse_samples": [P, U32, U32, F32, F32, P],
     "lnh_lidar_dir_term": [P, P, U32, U32, U32, P, P],
     "lnh_lidar_dir_term_freq": [P, U32, P, U32, U32, P, P],
@@ -177,10 +178,13 @@ _OPTIONAL = {"lnh_lidar_eval_frame": "frame evaluation", "lnh_lidar_eval_ssim": 
              "lnh_unet_conv3x3_backward_weight_workspace_size": "U-Net training",
              "lnh_unet_loss_grad": "U-Net training", "lnh_unet_loss_grad_workspace_size": "U-Net training",
              "lnh_unet_grad_sumsq": "U-Net training", "lnh_unet_grad_sumsq_workspace_size": "U-Net training",
-             "lnh_unet_rmsprop_step": "U-Net training"}
+             "lnh_unet_rmsprop_step": "U-Net training",
+             "lnh_lidar_color_composite_forward_train": "training forward tail",
+             "lnh_lidar_color_composite_forward_train_bf16": "training forward tail"}
 for _n in ("lnh_mlp_forward", "lnh_mlp_backward", "lnh_mlp_backward_data", "lnh_mlp_wgrad", "lnh_density_mlp_forward", "lnh_density_mlp_backward",
            "lnh_lidar_dir_term", "lnh_lidar_pack_weights", "lnh_lidar_step_prologue", "lnh_lidar_color_forward", "lnh_lidar_color_backward",
-           "lnh_lidar_color_composite_forward", "lnh_lidar_color_backward_image", "lnh_lidar_dir_term_freq",
+           "lnh_lidar_color_composite_forward", "lnh_lidar_color_composite_forward_train", "lnh_lidar_color_backward_image",
+           "lnh_lidar_dir_term_freq",
            "lnh_ragged_pack_weights", "lnh_ragged_color_input", "lnh_ragged_color_input_rays", "lnh_ragged_color_output",
            "lnh_ragged_color_output_backward", "lnh_ragged_grad_rows", "lnh_ragged_color_forward", "lnh_ragged_color_backward"):
     _SIGS[_n + "_bf16"] = _SIGS[_n]  # bf16-operand build of the MLP kernels (include/lidarnerf_hip.h, last section)

@@ -161,8 +161,11 @@ def step_graphed(trainer, rays_o, rays_d, images_lidar, patch, sampler=None):
     # ... and the marcher (NeRFRenderer.ordered_march is an attribute, assignable between steps: a replay never marches the
     # other way).  The capacity stays the last element of an unsampled step's key.
     marcher = ("ordered_march", bool(getattr(model, "ordered_march", False))) if trainer.occupancy else ()
+    # ... and which forward tail the dense chain takes (fused.train_tail_enabled: LNH_TRAIN_TAIL, read at every call)
+    from .fused import train_tail_enabled
     key = (tuple(rays_o.shape), tuple(images_lidar.shape), tuple(patch), tuple(trainer.alpha), float(trainer.scale),
-           tuple(sorted((k, repr(v)) for k, v in trainer.render_kwargs.items())), trainer.loss_options) + marcher + (cap,)
+           tuple(sorted((k, repr(v)) for k, v in trainer.render_kwargs.items())), trainer.loss_options,
+           ("train_tail", train_tail_enabled())) + marcher + (cap,)
     if sampler is not None:
         # the draw's kernel arguments (sequence, geometry, seed, stream) join the key; the cursor lives in the sampler, so
         # every graph of the capacity ladder reads and advances the same one

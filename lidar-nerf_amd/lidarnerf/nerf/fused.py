@@ -18,6 +18,8 @@ Forward                                                       kernels (liblidarn
   sigma_m, w = merge + weights                                lnh_lidar_color_composite_forward (T+t > 2048:
   rgb = colour_net(h16[perm], cdir) * (w > 1e-4)                lnh_lidar_merge_weights, lnh_lidar_color_forward,
   ws, depth, image = composite(sigma_m, rgb, z_all)             lnh_lidar_composite_forward)
+  (LidarTrainer, default loss: + g_image, g_sigma of the ray   lnh_lidar_color_composite_forward_train: the backward
+   in the same launch — TRAIN_TAIL below)                        then skips lnh_lidar_composite_backward)
 Backward runs the mirror image over all N(T+t) points at once; the hash-table gradient uses the bucketed
 scatter-reduce (no HBM atomics) and, data-parallel, goes on the wire in fp16 window by window.
 """
@@ -361,11 +363,27 @@ def _ragged_field(xyzs, rays, M, bound, enc, table16, wsig16, wcol16, cdir, mdt,
               rays.shape[0], M, rgb.data_ptr())
 
 
+# The training forward tail.  Under the default loss with one ray per patch, d loss / d (depth, image) of a ray is a closed
+# form of that ray's own outputs, so the forward tail can go on to the compositing adjoint of the ray from what its forward
+# walk left in LDS (lnh_lidar_color_composite_forward_train) and the backward pass starts at the colour head;
+# sigma_m and rgb, which only the compositing backward read, are then never written.  The loss is the
+# trainer's, so LidarTrainer.loss offers what the kernel needs — (gt [N, 3], alpha_d, alpha_r, alpha_i, grad_scale device
+# scalar) — in TRAIN_TAIL around its render call; render_lidar takes the offer when the model is training and the samples
+# fit the fused tail, and says so in its result ("train_tail": the gradients of depth_lidar / image_lidar that reach the
+# node are then IGNORED — the caller must not differentiate anything else through them).  LNH_TRAIN_TAIL=0 (read at every
+# call: A/B runs, tests) keeps the three-launch chain forward tail -> lnh_lidar_loss -> lnh_lidar_composite_backward.
+TRAIN_TAIL = None
+
+
+def train_tail_enabled():
+    return os.environ.get("LNH_TRAIN_TAIL", "1") != "0"
+
+
 class FusedLidarRender(Function):
     @staticmethod
     @_no_autocast
     def forward(ctx, rays_o, rays_d, noise, u, embeddings, ws0, ws1, wc0, wc1, wc2, model, density_scale, spec, mdt, near,
-                far, T):
+                far, T, tail=None):
         # noise: [N*T] uniforms of the stratified perturbation, or None (evaluation)
         # mdt: element type of everything MLP-side (packed weights, sigma-net rows, their gradients)
         sfx = _hip.mlp_suffix(mdt)
@@ -440,13 +458,25 @@ class FusedLidarRender(Function):
         if CAPTURE is not None:
             CAPTURE.update(z=z, new_z=new_z, z_all=z_all, perm=perm)
 
-        sigma_m = torch.empty((N, Ttot), dtype=torch.float32, device=dev)
         weights = torch.empty((N, Ttot), dtype=torch.float32, device=dev)
-        rgb = torch.empty((N, Ttot, 2), dtype=torch.float32, device=dev)
+        if tail is None:  # (the training forward tail keeps both in LDS: nothing else reads them)
+            sigma_m = torch.empty((N, Ttot), dtype=torch.float32, device=dev)
+            rgb = torch.empty((N, Ttot, 2), dtype=torch.float32, device=dev)
         ws = torch.empty(N, dtype=torch.float32, device=dev)
         depth = torch.empty(N, dtype=torch.float32, device=dev)
         image = torch.empty((N, 2), dtype=torch.float32, device=dev)
-        if Ttot <= 2048:
+        g_sigma = g_image = None
+        if tail is not None:
+            # ... and the loss gradient + compositing adjoint of every ray behind its forward, in the same launch
+            gt, ad, ar, ai, grad_scale = tail
+            g_sigma = torch.empty((N, Ttot), dtype=torch.float32, device=dev)
+            g_image = torch.empty((N, 2), dtype=torch.float32, device=dev)
+            _hip.call("lnh_lidar_color_composite_forward_train" + sfx, z_all.data_ptr(), sigma_pt.data_ptr(), perm.data_ptr(),
+                      sd.data_ptr(), h16.data_ptr(), cdir.data_ptr(), wcol16.data_ptr(), N, Ttot, float(density_scale),
+                      gt.data_ptr(), float(ad), float(ar), float(ai), None if grad_scale is None else grad_scale.data_ptr(),
+                      weights.data_ptr(), ws.data_ptr(), depth.data_ptr(), image.data_ptr(), g_sigma.data_ptr(),
+                      g_image.data_ptr(), timer="lnh_lidar_color_composite_forward" + sfx)
+        elif Ttot <= 2048:
             # merged densities + weights, colour head, compositing sums: one launch, one wave per ray
             _hip.call("lnh_lidar_color_composite_forward" + sfx, z_all.data_ptr(), sigma_pt.data_ptr(), perm.data_ptr(),
                       sd.data_ptr(), h16.data_ptr(), cdir.data_ptr(), wcol16.data_ptr(), N, Ttot, float(density_scale),
@@ -460,7 +490,11 @@ class FusedLidarRender(Function):
             _hip.call("lnh_lidar_composite_forward", z_all.data_ptr(), sigma_m.data_ptr(), rgb.data_ptr(), sd.data_ptr(),
                       N, Ttot, 2, float(density_scale), None, ws.data_ptr(), depth.data_ptr(), image.data_ptr())
 
-        ctx.save_for_backward(x01, feat, h16, perm, weights, z_all, sigma_m, rgb, sd, cdir, enc_d16, wsig16, wcol16)
+        if tail is not None:  # (the backward does not need z_all either: it goes back to the allocator here)
+            ctx.save_for_backward(x01, feat, h16, perm, weights, g_sigma, g_image, cdir, enc_d16, wsig16, wcol16)
+        else:
+            ctx.save_for_backward(x01, feat, h16, perm, weights, z_all, sigma_m, rgb, sd, cdir, enc_d16, wsig16, wcol16)
+        ctx.train_tail = tail is not None
         ctx.dims, ctx.density_scale, ctx.enc = (N, T, t_new), density_scale, enc
         ctx.table_param, ctx.mdt, ctx.table_dtype = spec.table_param, mdt, embeddings.dtype
         ctx.small_dtypes, ctx.small_params = _small_param_state(small)
@@ -473,23 +507,28 @@ class FusedLidarRender(Function):
     @staticmethod
     @_no_autocast
     def backward(ctx, g_ws, g_depth, g_image, _gw, _gz):
-        x01, feat, h16, perm, weights, z_all, sigma_m, rgb, sd, cdir, enc_d16, wsig16, wcol16 = ctx.saved_tensors
         (N, T, t_new), ds = ctx.dims, ctx.density_scale
         enc, table_param = ctx.enc, ctx.table_param
-        dev = h16.device
         mdt, sfx = ctx.mdt, _hip.mlp_suffix(ctx.mdt)
         Ttot = T + t_new
-        g_ws, g_depth, g_image = (None if g is None else g.contiguous().float() for g in (g_ws, g_depth, g_image))
-        ptr = lambda t: None if t is None else t.data_ptr()
+        if ctx.train_tail:
+            # the forward tail has formed the loss gradient and the compositing adjoint of every ray: straight to the colour head
+            x01, feat, h16, perm, weights, g_sigma, g_image, cdir, enc_d16, wsig16, wcol16 = ctx.saved_tensors
+            dev = h16.device
+        else:
+            x01, feat, h16, perm, weights, z_all, sigma_m, rgb, sd, cdir, enc_d16, wsig16, wcol16 = ctx.saved_tensors
+            dev = h16.device
+            g_ws, g_depth, g_image = (None if g is None else g.contiguous().float() for g in (g_ws, g_depth, g_image))
+            ptr = lambda t: None if t is None else t.data_ptr()
 
-        g_sigma = torch.empty((N, Ttot), dtype=torch.float32, device=dev)
-        # d loss / d rgb = weights (x) d loss / d image is formed inside the colour backward: the compositing backward
-        # writes the density gradient only (grad_rgb = NULL)
-        _hip.call("lnh_lidar_composite_backward", ptr(g_ws), ptr(g_depth), ptr(g_image),
-                  z_all.data_ptr(), sigma_m.data_ptr(), rgb.data_ptr(), sd.data_ptr(), N, Ttot, 2, float(ds),
-                  g_sigma.data_ptr(), None)
-        if g_image is None:
-            g_image = torch.zeros((N, 2), dtype=torch.float32, device=dev)
+            g_sigma = torch.empty((N, Ttot), dtype=torch.float32, device=dev)
+            # d loss / d rgb = weights (x) d loss / d image is formed inside the colour backward: the compositing backward
+            # writes the density gradient only (grad_rgb = NULL)
+            _hip.call("lnh_lidar_composite_backward", ptr(g_ws), ptr(g_depth), ptr(g_image),
+                      z_all.data_ptr(), sigma_m.data_ptr(), rgb.data_ptr(), sd.data_ptr(), N, Ttot, 2, float(ds),
+                      g_sigma.data_ptr(), None)
+            if g_image is None:
+                g_image = torch.zeros((N, 2), dtype=torch.float32, device=dev)
 
         g_h16 = torch.empty((N * Ttot, 16), dtype=mdt, device=dev)
         wws = _hip.wgrad_ws(dev)  # scratch of the fixed-order weight-gradient sums (one per device and stream, kept)
@@ -529,7 +568,7 @@ class FusedLidarRender(Function):
         else:
             _grid_bwd(g_feat, x01, g_table16, enc, B_all, bwd_ws, bwd_flags)
         g_table = _hand_over_table(table_param, g_table16, ctx.table_dtype, handles)
-        return (None, None, None, None, g_table) + g_small + (None,) * 7
+        return (None, None, None, None, g_table) + g_small + (None,) * 8
 
 
 MASK_STATS = None  # bench.py: set to a list to collect, per render call, the fraction of samples with weight > 1e-4
@@ -567,12 +606,25 @@ def render_lidar(model, rays_o, rays_d, num_steps, upsample_steps, perturb, nois
                            device=dev).expand(N, upsample_steps).contiguous()
     sp = model.fused_spec()
     from ..ffmlp.ffmlp import mlp_dtype
+    # the trainer's offer of a training forward tail (TRAIN_TAIL above): taken for a training render of these very rays
+    # whose samples fit the fused tail, by a library that has the entry point
+    tail = TRAIN_TAIL
+    if tail is not None and not (model.training and torch.is_grad_enabled() and num_steps + upsample_steps <= 2048
+                                 and train_tail_enabled() and tail[0].numel() == 3 * N and tail[0].is_cuda):
+        tail = None
+    if tail is not None:
+        _hip.require_symbols(("lnh_lidar_color_composite_forward_train" + _hip.mlp_suffix(mlp_dtype()),),
+                             "the training forward tail (LNH_TRAIN_TAIL=0 keeps the three-launch chain)")
+        tail = (tail[0].reshape(N, 3).float().contiguous(),) + tuple(tail[1:])
     ws, depth, image, weights, _ = FusedLidarRender.apply(rays_o, rays_d, noise, u, sp.table, sp.ws0, sp.ws1, sp.wc0,
                                                           sp.wc1, sp.wc2, model, model.density_scale, sp, mlp_dtype(),
-                                                          float(near), float(far), num_steps)
+                                                          float(near), float(far), num_steps, tail)
     if MASK_STATS is not None:
         MASK_STATS.append((weights > 1e-4).float().mean())
-    return {"depth_lidar": depth.view(*prefix), "image_lidar": image.view(*prefix, 2), "weights_sum_lidar": ws}
+    out = {"depth_lidar": depth.view(*prefix), "image_lidar": image.view(*prefix, 2), "weights_sum_lidar": ws}
+    if tail is not None:
+        out["train_tail"] = True
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ occupancy-grid chain

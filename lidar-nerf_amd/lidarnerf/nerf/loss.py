@@ -99,14 +99,23 @@ class _FusedLidarLoss(torch.autograd.Function):
     """lidar_loss as ONE kernel that also emits d loss / d (depth, image); backward only scales by the upstream scalar."""
 
     @staticmethod
-    def forward(ctx, depth, image, gt, ad, ar, ai, patch=None, grad_scale=None, options=None, scale=None):
+    def forward(ctx, depth, image, gt, ad, ar, ai, patch=None, grad_scale=None, options=None, scale=None, value_only=False):
         # patch = (px, py, scale, alpha_grad): the reference's patch epochs, structural-gradient term included
         # grad_scale (device scalar): the kernel multiplies the gradients it emits by it — the caller then starts
         # backward() from a gradient of ONE (LidarTrainer: the loss scale, without an element-wise launch in backward)
+        # value_only: the render node has formed the gradients itself (fused.TRAIN_TAIL: default loss, no patch) — the same
+        # kernel gives the value, with null gradient outputs, and backward hands nothing back
         n = depth.numel()
         depth, image, gt = depth.reshape(n).float().contiguous(), image.reshape(n, 2).float().contiguous(), \
             gt.reshape(n, 3).float().contiguous()
         loss = torch.empty((), dtype=torch.float32, device=depth.device)
+        ctx.value_only = bool(value_only)
+        if value_only:
+            if patch is not None or (options is not None and not options.is_default):
+                raise ValueError("value_only: the default loss with one ray per patch only")
+            _hip.call("lnh_lidar_loss", depth.data_ptr(), image.data_ptr(), gt.data_ptr(), n, float(ad), float(ar), float(ai),
+                      None, loss.data_ptr(), None, None)
+            return loss
         grads = torch.empty(3 * n, dtype=torch.float32, device=depth.device)  # [d/d depth (n) | d/d image (n, 2)]
         gs = None if grad_scale is None else grad_scale.data_ptr()
         if options is not None and not options.is_default:
@@ -136,10 +145,12 @@ class _FusedLidarLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
+        if ctx.value_only:
+            return (None,) * 11
         (grads,) = ctx.saved_tensors
         # (pre-scaled gradients: the contract of grad_scale is that backward() starts from ONE)
         scaled = grads if ctx.prescaled else grads * g  # one launch for both
-        return scaled[:ctx.n], scaled[ctx.n:].view(ctx.n, 2), None, None, None, None, None, None, None, None
+        return scaled[:ctx.n], scaled[ctx.n:].view(ctx.n, 2), None, None, None, None, None, None, None, None, None
 
 
 class _ScaleGrad(torch.autograd.Function):
@@ -156,14 +167,15 @@ class _ScaleGrad(torch.autograd.Function):
 
 
 def fused_lidar_loss(outputs, images_lidar, alpha_d=1000.0, alpha_r=1.0, alpha_i=10.0, patch=None, grad_scale=None,
-                     options=None, scale=None):
+                     options=None, scale=None, value_only=False):
     """lidar_loss (+ patch_gradient_loss when patch = (px, py, scale, alpha_grad)) through the single-launch kernel (GPU
     tensors only); same value and gradients.  grad_scale (device scalar): the gradients come out multiplied by it and
     backward() must then be started from a gradient of one.  options (LidarLossOptions): any other loss option set of the
-    reference CLI (lnh_lidar_loss_ex; `scale`, the huber delta's, defaults to the patch's)."""
+    reference CLI (lnh_lidar_loss_ex; `scale`, the huber delta's, defaults to the patch's).  value_only: `outputs` come
+    from a render that took the training forward tail (outputs["train_tail"]) — the value alone, its gradients exist."""
     depth, image = outputs["depth_lidar"], outputs["image_lidar"]
     loss = _FusedLidarLoss.apply(depth.reshape(-1), image.reshape(-1, 2), images_lidar, alpha_d, alpha_r, alpha_i, patch,
-                                 grad_scale, options, scale)
+                                 grad_scale, options, scale, value_only)
     return loss
 
 

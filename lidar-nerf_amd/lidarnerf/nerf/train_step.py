@@ -154,10 +154,21 @@ class LidarTrainer:
 
     def loss(self, rays_o, rays_d, images_lidar, patch=(1, 1), grad_scale=None):
         """grad_scale (device scalar): the loss comes back unscaled, its gradient multiplied by it."""
-        out = self.model.render(rays_o, rays_d, cal_lidar_color=True, staged=False, perturb=True,
-                                **self.render_kwargs)
+        from . import fused
         ad, ar, ai, ag = self.alpha
         opts = None if self.loss_options.is_default else self.loss_options
+        # the default loss with one ray per patch, its gradient pre-scaled (backward starts from ONE): the dense fused chain
+        # may form the loss gradient and the compositing adjoint inside its forward tail (fused.TRAIN_TAIL)
+        if opts is None and patch[0] <= 1 and grad_scale is not None and images_lidar.is_cuda:
+            fused.TRAIN_TAIL = (images_lidar, ad, ar, ai, grad_scale)
+        try:
+            out = self.model.render(rays_o, rays_d, cal_lidar_color=True, staged=False, perturb=True,
+                                    **self.render_kwargs)
+        finally:
+            fused.TRAIN_TAIL = None
+        if out.get("train_tail"):
+            # (its gradients are formed already; the same kernel gives the value)
+            return fused_lidar_loss(out, images_lidar, ad, ar, ai, value_only=True)
         if out["depth_lidar"].is_cuda and (patch[0] <= 1 or (patch[1] >= 2 and out["depth_lidar"].numel() %
                                                                (patch[0] * patch[1]) == 0)):
             return fused_lidar_loss(out, images_lidar, ad, ar, ai,
