@@ -793,6 +793,58 @@ LNH_API int lnh_marching_cubes_emit(const float *volume, uint32_t nx, uint32_t n
                                     uint64_t ws_bytes, float *vertices, uint32_t max_vertices, int32_t *triangles,
                                     uint32_t max_triangles, lnh_stream_t stream);
 
+/* ---- mesh baseline fit: projective TSDF fusion of range images, and the trim of the mesh to what was observed — csrc/tsdf.hip.
+ * (Added without moving lnh_version: detect by symbol.)  The meshing function of LidarNVSMeshing.fit
+ * (lidarnvs/lidarnvs_meshing.py) for a sequence of range images with poses; nearest-pixel depth, unit weights, the column
+ * wrap, the fill and the trim are this package's own, not Open3D's.
+ * Lattice: point (ix, iy, iz) at lo[a] + float(i_a) * step[a]; every lattice array is [nx, ny, nz], z fastest, as
+ *   lnh_marching_cubes_* reads it.  lo and step are HOST arrays of 3 floats.
+ * lnh_tsdf_integrate: panos f32 [F,H,W] (a depth <= 0 or not finite: no observation), world_to_lidar f32 [F,12] (the affine
+ *   3 x 4 matrix of each frame, row-major), lidar_K = (fov_up, fov) in degrees.  sum f32 [n] and count u32 [n] are read, added
+ *   to and written back.  For every lattice point, the frames in order 0 .. F-1, all in fp32 with one rounded operation per
+ *   operator and nothing contracted:
+ *     p_a = lo[a] + float(i_a) * step[a]
+ *     q_r = ((m[r][0] * p_x + m[r][1] * p_y) + m[r][2] * p_z) + m[r][3]                       r = x, y, z
+ *     r   = sqrt((q_x q_x + q_y q_y) + q_z q_z); the frame is skipped unless 0 < r < max_depth
+ *     the pixel is lnh_lidar_to_pano's (csrc/pano_geom.h): beta = f32(pi) - f32(atan2(q_y, q_x)), alpha = f32(atan2(q_z,
+ *       sqrt(q_x q_x + q_y q_y))) + down_rad, column = rint(beta / col_step), row = rint(float(H) - alpha / row_step), atan2 in
+ *       double; skipped outside the rows [0, H).  The one difference: a column that rounds to W is column 0
+ *     d   = panos[f][row][column]; skipped unless 0 < d < inf
+ *     s   = d - r; skipped if s < -trunc
+ *     sum += min(s / trunc, 1); count += 1
+ *   One thread owns a lattice point: no atomics, the result is a function of the inputs alone, and the frames split over several
+ *   calls give the bits of one call.  A wave covers a 4 x 4 x 4 brick of lattice points.
+ * lnh_tsdf_finalize: volume f32 [n] = -(sum / float(count)) where count >= min_count (>= 1), else the fill +1.  Free space is
+ *   negative — the BELOW side of lnh_marching_cubes_* at iso 0, so the normals face the sensors — and all unobserved points are
+ *   equal, so no cell made only of them crosses.  (float(count) is exact below 2^24 frames.)
+ * lnh_mesh_vertex_observed: vertices f32 [V,3] in index units -> keep u8 [V] = 1 iff every lattice point of the smallest lattice
+ *   edge / face / cell holding the vertex has count >= min_count: for a marching-cubes vertex the two ends of its edge, for a
+ *   vertex exactly on a lattice point that one point.  0 for a vertex outside [0, n_a - 1] or NaN (compared in integers behind
+ *   the floor, so a dimension above 2^24 is safe).
+ * lnh_mesh_filter_count / _emit: Open3D's remove_vertices_by_mask with keep = 1 meaning "stays".  The kept vertices in order; the
+ *   triangles whose three indices are in [0, V) and kept, in order, renumbered.  Integers only.  count writes counts u32[4]
+ *   (device) = kept vertices, kept triangles, 0, 0 and leaves in the workspace what emit reads: call emit after it on the same
+ *   stream with the same keep, triangles and workspace.  emit never writes past max_vertices / max_triangles rows; a mask of all
+ *   zeros gives counts 0, 0 and needs no emit (max_vertices = 0 is refused; max_triangles = 0 writes the vertices alone).
+ * Errors (before any launch): LNH_ERR_INVALID_ARG for a null pointer, F, H, W or V or T = 0, a lattice dimension below 2, a trunc
+ *   or step that is not positive and finite, a lo that is not finite, fov <= 0, min_count = 0, a workspace smaller than
+ *   lnh_mesh_filter_workspace_size(V, T) (4-byte aligned, contents irrelevant; 0 for a refused size);
+ *   LNH_ERR_UNSUPPORTED for nx * ny * nz >= 2^31, H * W > 2^24, V or T >= 2^31.
+ */
+LNH_API int lnh_tsdf_integrate(const float *panos, const float *world_to_lidar, uint32_t F, uint32_t H, uint32_t W, float fov_up,
+                               float fov, float max_depth, const float *lo, const float *step, uint32_t nx, uint32_t ny,
+                               uint32_t nz, float trunc, float *sum, uint32_t *count, lnh_stream_t stream);
+LNH_API int lnh_tsdf_finalize(const float *sum, const uint32_t *count, uint32_t nx, uint32_t ny, uint32_t nz, uint32_t min_count,
+                              float *volume, lnh_stream_t stream);
+LNH_API int lnh_mesh_vertex_observed(const float *vertices, uint32_t V, const uint32_t *count, uint32_t nx, uint32_t ny,
+                                     uint32_t nz, uint32_t min_count, uint8_t *keep, lnh_stream_t stream);
+LNH_API uint64_t lnh_mesh_filter_workspace_size(uint32_t V, uint32_t T);
+LNH_API int lnh_mesh_filter_count(const uint8_t *keep, uint32_t V, const int32_t *triangles, uint32_t T, void *ws,
+                                  uint64_t ws_bytes, uint32_t *counts, lnh_stream_t stream);
+LNH_API int lnh_mesh_filter_emit(const float *vertices, const uint8_t *keep, uint32_t V, const int32_t *triangles, uint32_t T,
+                                 void *ws, uint64_t ws_bytes, float *out_vertices, uint32_t max_vertices, int32_t *out_triangles,
+                                 uint32_t max_triangles, lnh_stream_t stream);
+
 /* ---- mesh ray casting: watertight closest hit.  (Added without moving lnh_version: detect by symbol.)
  * Replaces RaycastingScene.cast_rays (Open3D / Embree on the host) of lidarnvs/lidarnvs_meshing.py:293-353.
  * Mesh: vertices f32 [V,3], triangles i32 [T,3].  Rays: rays_o, rays_d f32 [N,3]; d need not be normalised.

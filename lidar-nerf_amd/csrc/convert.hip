@@ -19,32 +19,9 @@
 
 namespace {
 
-constexpr double kPi = 3.14159265358979323846;
-
-struct PanoGeom {
-    float pi_f;        // float32(np.pi)
-    float down_rad;    // float32(fov_down / 180 * pi)
-    float col_step;    // float32(2 pi / W)
-    float row_step;    // float32(fov / 180 * pi / H)
-    float max_depth;
-    uint32_t H, W;
-};
-
-__device__ __forceinline__ float atan2_rn(float y, float x) { return (float)atan2((double)y, (double)x); }
-
-// Point -> pixel, shared by the closest-point, bbox-mask and z-buffer paths: the reference's float32 arithmetic.  Returns
-// the row-major pixel id, or kNoPixel for a point the reference skips (dist >= max_depth, outside the image; dist == 0).
-constexpr uint32_t kNoPixel = 0xffffffffu;
+// Point -> pixel, shared by the closest-point, bbox-mask and z-buffer paths (pano_geom.h: the one copy of the arithmetic).
 __device__ __forceinline__ uint32_t pano_pixel(const float *__restrict__ pts, uint32_t i, const PanoGeom &g, float &dist) {
-    const float x = pts[(size_t)i * 4], y = pts[(size_t)i * 4 + 1], z = pts[(size_t)i * 4 + 2];
-    dist = sqrtf(x * x + y * y + z * z);  // np.linalg.norm over 3 float32 values
-    if (!(dist < g.max_depth) || !(dist > 0.0f)) return kNoPixel;  // reference: `if dist >= max_depth: continue`
-    const float beta = g.pi_f - atan2_rn(y, x);
-    const float alpha = atan2_rn(z, sqrtf(x * x + y * y)) + g.down_rad;
-    const float cf = rintf(beta / g.col_step);                 // Python round(): half to even
-    const float rf = rintf((float)g.H - alpha / g.row_step);
-    if (!(rf >= 0.0f) || !(cf >= 0.0f) || rf >= (float)g.H || cf >= (float)g.W) return kNoPixel;
-    return (uint32_t)rf * g.W + (uint32_t)cf;
+    return pano_pixel_xyz<false>(pts[(size_t)i * 4], pts[(size_t)i * 4 + 1], pts[(size_t)i * 4 + 2], g, dist);
 }
 __device__ __forceinline__ unsigned long long pano_key(float dist, uint32_t i) {
     return ((unsigned long long)__float_as_uint(dist) << 32) | i;
@@ -210,18 +187,6 @@ k_pano_to_lidar(const float *__restrict__ pano, const float *__restrict__ intens
     pts[(size_t)p * 4 + 2] = z;
     pts[(size_t)p * 4 + 3] = intens ? intens[p] : 0.0f;
     valid[p] = d != 0.0f;
-}
-
-PanoGeom pano_geom(uint32_t H, uint32_t W, float fov_up, float fov, float max_depth) {
-    PanoGeom g;
-    g.pi_f = (float)kPi;
-    g.down_rad = (float)(((double)fov - (double)fov_up) / 180.0 * kPi);
-    g.col_step = (float)(2.0 * kPi / (double)W);
-    g.row_step = (float)((double)fov / 180.0 * kPi / (double)H);
-    g.max_depth = max_depth;
-    g.H = H;
-    g.W = W;
-    return g;
 }
 
 constexpr uint64_t kFpaMaxPixels = 1ull << 24;

@@ -79,6 +79,11 @@ _SIGS = {
     "lnh_lidar_to_pano_fpa": [P, C.c_uint64, U32, U32, F32, F32, F32, U32, C.c_double, P, C.c_uint64, P, P],
     "lnh_marching_cubes_count": [P, U32, U32, U32, F32, P, C.c_uint64, P],
     "lnh_marching_cubes_emit": [P, U32, U32, U32, F32, P, C.c_uint64, P, U32, P, U32],
+    "lnh_tsdf_integrate": [P, P, U32, U32, U32, F32, F32, F32, P, P, U32, U32, U32, F32, P, P],
+    "lnh_tsdf_finalize": [P, P, U32, U32, U32, U32, P],
+    "lnh_mesh_vertex_observed": [P, U32, P, U32, U32, U32, U32, P],
+    "lnh_mesh_filter_count": [P, U32, P, U32, P, C.c_uint64, P],
+    "lnh_mesh_filter_emit": [P, P, U32, P, U32, P, C.c_uint64, P, U32, P, U32],
     "lnh_raycast_bounds": [P, U32, P, U32, P, C.c_uint64, P, P],
     "lnh_raycast_build_count": [P, U32, P, U32, P, U32, U32, U32, P, C.c_uint64, P, P],
     "lnh_raycast_build_fill": [P, U32, P, U32, P, U32, U32, U32, P, C.c_uint64, P, P, C.c_uint64],
@@ -156,6 +161,9 @@ _OPTIONAL = {"lnh_lidar_eval_frame": "frame evaluation", "lnh_lidar_eval_ssim": 
              "lnh_lidar_to_pano_fpa_workspace_size": "fpa conversion",
              "lnh_marching_cubes_count": "mesh export", "lnh_marching_cubes_emit": "mesh export",
              "lnh_marching_cubes_workspace_size": "mesh export",
+             "lnh_tsdf_integrate": "TSDF fusion", "lnh_tsdf_finalize": "TSDF fusion",
+             "lnh_mesh_vertex_observed": "TSDF fusion", "lnh_mesh_filter_count": "TSDF fusion",
+             "lnh_mesh_filter_emit": "TSDF fusion", "lnh_mesh_filter_workspace_size": "TSDF fusion",
              "lnh_raycast_bounds": "mesh ray casting", "lnh_raycast_build_count": "mesh ray casting",
              "lnh_raycast_build_fill": "mesh ray casting", "lnh_raycast_cast": "mesh ray casting",
              "lnh_raycast_workspace_size": "mesh ray casting",
@@ -196,6 +204,7 @@ EXPORTS = sorted(list(_SIGS) + ["lnh_version", "lnh_last_error", "lnh_arch", "ln
                                  "lnh_lidar_loss_ex_workspace_bytes", "lnh_lidar_eval_workspace_bytes",
                                  "lnh_eval_points_workspace_bytes", "lnh_lidar_to_pano_fpa_workspace_size",
                                  "lnh_marching_cubes_workspace_size", "lnh_raycast_workspace_size",
+                                 "lnh_mesh_filter_workspace_size",
                                  "lnh_knn_workspace_size", "lnh_raydrop_workspace_size", "lnh_raydrop_param_count",
                                  "lnh_unet_workspace_size", "lnh_unet_head_backward_workspace_size",
                                  "lnh_unet_upconv2x2_backward_weight_workspace_size", "lnh_unet_bn_stats_workspace_size",
@@ -263,6 +272,9 @@ def lib():
         if hasattr(L, "lnh_marching_cubes_workspace_size"):
             L.lnh_marching_cubes_workspace_size.argtypes = [U32, U32, U32]
             L.lnh_marching_cubes_workspace_size.restype = C.c_uint64
+        if hasattr(L, "lnh_mesh_filter_workspace_size"):
+            L.lnh_mesh_filter_workspace_size.argtypes = [U32, U32]
+            L.lnh_mesh_filter_workspace_size.restype = C.c_uint64
         if hasattr(L, "lnh_raycast_workspace_size"):
             L.lnh_raycast_workspace_size.argtypes = [U32, U32, U32, U32, U32, C.c_uint64]
             L.lnh_raycast_workspace_size.restype = C.c_uint64

@@ -6,8 +6,10 @@ the GPU.
 What is not pinned against the reference: Open3D's order among equidistant neighbours and NumPy's float32 np.mean
 (here: smallest index first, an fp64 rank-order sum rounded once), and its float64 pose matrices (here fp32).  The pose is taken
 as affine (last row 0 0 0 1), which is what homo_project's division by w amounts to for a LiDAR pose.  The ray-drop U-Net of the
-mesh baselines is lidarnerf/unet.py (RayDropUNet, inference); its training and the meshing itself (MeshNVS has no fit)
-are not part of this.  No CPU fallback.
+mesh baselines is lidarnerf/unet.py (RayDropUNet, inference), its training lidarnerf/unet_trainer.py.
+MeshNVS.fit builds the mesh from a training sequence by TSDF fusion of its range images (lidarnerf/tsdf.py) — this
+package's meshing function, not the reference's Poisson recipe — and MeshNVS.raydrop_dataset makes what the U-Net trainer takes.
+No CPU fallback.
 
 PointCloudNVS is the point-cloud baseline, LidarNVSPCGen of lidarnvs/lidarnvs_pcgen.py:16-248: the training cloud itself is
 projected ("cp": closest point, "fpa": first-peak averaging over a z-buffer), turned back into a cloud, and masked by the
@@ -30,6 +32,13 @@ def _pose(lidar_pose, device):
     if tuple(pose.shape) != (4, 4):
         raise ValueError(f"MeshNVS: lidar_pose must be [4, 4], got {tuple(pose.shape)}")
     return pose.detach().to(device, torch.float32)
+
+
+def _image(image, H, W, device, what):
+    t = torch.from_numpy(np.array(image, dtype=np.float32)) if isinstance(image, np.ndarray) else image  # (a copy)
+    if not torch.is_tensor(t) or t.numel() != H * W:
+        raise ValueError(f"MeshNVS: {what} must hold {H} x {W} values")
+    return t.detach().to(device, torch.float32).reshape(H, W)
 
 
 def transform_points(points, pose):
@@ -84,6 +93,74 @@ class MeshNVS:
         self.index = PointCloudIndex(points.to(self.device), grid_resolution=grid_resolution)
         self.points = self.index.points
         self.point_intensities = inten.detach().reshape(-1).to(self.device, torch.float32).contiguous()
+
+    @classmethod
+    def fit(cls, frames, *, resolution=256, voxel_size=None, truncation=None, box=None, margin=None, min_count=1, max_depth=None,
+            intensity_interpolate_k=5, grid_resolution=None):
+        """LidarNVSMeshing.fit with TSDF fusion as the meshing function: a fitted MeshNVS.  frames: an iterable of dicts with the
+        keys of the reference's extract_dataset_frame that matter — pano [H,W], intensities [H,W], lidar_pose [4,4] (lidar ->
+        world), lidar_K (fov_up, fov), lidar_H, lidar_W (tensors or NumPy arrays).  The world cloud and its intensities (the k-NN
+        index) come from convert.pano_to_lidar_with_intensities and transform_points, of the pixels with a depth > 0; the same
+        panos and poses go into a tsdf.TSDFVolume over `box` (min[3], max[3]; default: the cloud's bounds plus `margin`, whose
+        default is 4 voxel_size, or 5 % of the largest extent without a voxel_size).  Frames of different H x W or K are
+        integrated call by call, in the order given.  max_depth: None = 80, convert's default.  The fitted volume is kept as
+        .volume."""
+        from .tsdf import TSDFVolume
+        frames = list(frames)
+        if not frames:
+            raise ValueError("MeshNVS.fit: no frames")
+        if not torch.cuda.is_available():
+            raise RuntimeError("MeshNVS.fit: needs a GPU (no CPU fallback)")
+        dev = next((f["pano"].device for f in frames if torch.is_tensor(f["pano"]) and f["pano"].is_cuda),
+                   torch.device("cuda", torch.cuda.current_device()))
+        max_depth = 80 if max_depth is None else max_depth
+        groups, clouds, intens = [], [], []
+        with torch.cuda.device(dev):
+            for f in frames:
+                H, W = int(f["lidar_H"]), int(f["lidar_W"])
+                K = tuple(float(x) for x in (f["lidar_K"].tolist() if hasattr(f["lidar_K"], "tolist") else f["lidar_K"]))
+                pano, inten = _image(f["pano"], H, W, dev, "pano"), _image(f["intensities"], H, W, dev, "intensities")
+                pose = _pose(f["lidar_pose"], dev)
+                seen = torch.isfinite(pano) & (pano > 0)  # (NeRF-MVL marks pixels outside its window with -1)
+                local4 = convert.pano_to_lidar_with_intensities(torch.where(seen, pano, torch.zeros_like(pano)), inten, K)
+                clouds.append(transform_points(local4[:, :3].contiguous(), pose))
+                intens.append(local4[:, 3].contiguous())
+                if not groups or groups[-1][0] != (H, W, K):
+                    groups.append(((H, W, K), [], []))
+                groups[-1][1].append(pano)
+                groups[-1][2].append(pose)
+            points, point_intensities = torch.cat(clouds), torch.cat(intens)
+            if points.shape[0] == 0:
+                raise ValueError("MeshNVS.fit: the frames hold no pixel with a depth")
+            if box is None:
+                lo, hi = points.min(0).values.double().cpu().numpy(), points.max(0).values.double().cpu().numpy()
+                if margin is None:
+                    margin = 4.0 * float(voxel_size) if voxel_size is not None else 0.05 * float((hi - lo).max())
+                box = (lo - float(margin), hi + float(margin))
+            volume = TSDFVolume(box, resolution=resolution, voxel_size=voxel_size, truncation=truncation, device=dev)
+            for (_, _, K), panos, poses in groups:
+                volume.integrate(torch.stack(panos), torch.stack(poses), K, max_depth=max_depth)
+            fitted = cls(volume.scene(min_count=min_count), points, point_intensities,
+                         intensity_interpolate_k=intensity_interpolate_k, grid_resolution=grid_resolution)
+        fitted.volume = volume
+        return fitted
+
+    def raydrop_dataset(self, frames):
+        """The reference's generate_raydrop_data_meshing and RaydropDataset.collate_fn in one: (images f32 [N,10,H,W], masks f32
+        [N,H,W]) on the device for frames of one size — raydrop_features of every frame's pose, one after another, and
+        pano != 0 as floats.  What unet_trainer.RayDropUNetTrainer.train_step / train_epoch take."""
+        frames = list(frames)
+        if not frames:
+            raise ValueError("MeshNVS.raydrop_dataset: no frames")
+        H, W = int(frames[0]["lidar_H"]), int(frames[0]["lidar_W"])
+        images, masks = [], []
+        for f in frames:
+            if (int(f["lidar_H"]), int(f["lidar_W"])) != (H, W):
+                raise ValueError(f"MeshNVS.raydrop_dataset: frames of {int(f['lidar_H'])} x {int(f['lidar_W'])} and {H} x {W} do not "
+                                 "stack")
+            images.append(self.raydrop_features(f["lidar_K"], f["lidar_pose"], H, W))
+            masks.append((_image(f["pano"], H, W, self.device, "pano") != 0).to(torch.float32))
+        return torch.cat(images, dim=0).contiguous(), torch.stack(masks)
 
     def set_raydrop(self, model):
         """Store the ray-drop model (a unet.RayDropUNet, or any callable from the [1,10,H,W] feature image to [1,1,H,W] logits) that
