@@ -1,6 +1,6 @@
 """Device-side discipline shared by the exact known-answer GPU tests (tests/test_mlp_exact_gpu.py,
 tests/test_field_exact_gpu.py, tests/test_render_exact_gpu.py, tests/test_loss_exact_gpu.py, tests/test_optim_exact_gpu.py,
-tests/test_ragged_exact_gpu.py):
+tests/test_ragged_exact_gpu.py, tests/test_march_exact_gpu.py):
 sentinel-filled outputs with guard words, NaN rows behind inputs, calls made twice."""
 import numpy as np
 import torch
