@@ -1395,6 +1395,68 @@ LNH_API int lnh_eval_points_finalize(const float *dist_pred, const float *dist_g
                                      float threshold, double *accumulator, double *history, uint32_t max_frames,
                                      lnh_stream_t stream);
 
+/* ---- meters of the NVS baselines' evaluation (lidarnvs/eval.py:9-135 eval_points_and_pano, after the NeRF-MVL crop of
+ * lidarnvs/run.py:200-217), from four images of one frame to a row of numbers on the device, on the caller's stream, with no
+ * host read.  (Added without moving lnh_version: detect by symbol.)  NOT the trainer's meters (lnh_lidar_eval_*): images are
+ * in world scale and flattened first, so the SSIM is 1-D with a 7-wide window over the row-major sequence; dropped pixels
+ * (depth 0) take part in the depth metrics, clamped to 1e-3; there is no ray-drop masking.
+ * gt_pano, pd_pano, gt_int, pd_int: [H*W] f32; mask: [H*W] uint8 or NULL for "every pixel".  The evaluated sequence is the
+ * pixels with mask != 0 in row-major order, n of them; it is addressed as their bounding rectangle of h x w pixels at
+ * (r0, c0), element p at (r0 + p / w, c0 + p % w): the reference's reshape to (h, w) needs n == h * w, and a frame where
+ * that fails is marked bad.  One workspace of lnh_nvs_eval_workspace_bytes(H, W) bytes (8-byte aligned, contents irrelevant;
+ * 0 for an unsupported shape) carries the partials from call to call.
+ * lnh_nvs_eval_frame: per element, in float32 and in the reference's operation order: both depths clamped to [1e-3, 80]
+ *   (a NaN stays a NaN), thresh = max(gt / pd, pd / gt), the three strict comparisons thresh < 1.25, < 1.5625, < 1.953125,
+ *   (gt - pd)^2, |gt_i * intensity_scale - pd_i * intensity_scale| (intensity_scale: 1 for KITTI-360, 255 for NeRF-MVL).
+ *   Per workgroup: the counts and the rectangle as integers, the two sums in fp64, min / max of the clamped ground truth.
+ * lnh_nvs_eval_ssim: skimage.metrics.structural_similarity's defaults on the two clamped sequences as 1-D signals: uniform
+ *   window of 7, sample covariance (7 / 6), K1 0.01, K2 0.03, data_range = the float32 max - min of the clamped ground
+ *   truth, the mean over the n - 6 positions whose window lies inside the sequence.  The five window moments are fp64 sums of
+ *   the 7 float32 values from left to right, S is formed in fp64 with one rounded operation per operator (two identical
+ *   images give exactly 1).  `mask` is the one lnh_nvs_eval_frame was given; it is not read (the rectangle comes from the
+ *   partials).  Over the rectangle also where the masked pixels do not fill it (that frame is bad).
+ * lnh_nvs_eval_finalize: adds the partials in index order, forms the frame's row of LNH_NVS_SLOTS doubles — chamfer and
+ *   F-score copied from points_row, the LNH_PTS_* row lnh_eval_points_finalize made for the same frame (a device pointer) —
+ *   stores it at history[frame * LNH_NVS_SLOTS] when frame = accumulator[LNH_NVS_FRAMES] < max_frames (history may be NULL
+ *   with max_frames 0) and adds it to accumulator[LNH_NVS_SLOTS] (clear that before the first frame): the meters are means
+ *   of per-frame values.  n < 7 gives an SSIM of NaN; data_range 0 is not special-cased (the IEEE result stands).
+ * Call the three in this order on one stream.  Deterministic (integer atomics in LDS only, fixed-order fp64 sums); no
+ * allocation, copy or synchronisation: capturable in a hipGraph.
+ * Errors (before any launch): LNH_ERR_INVALID_ARG for a null or misaligned pointer, H * W = 0, an intensity_scale that is not
+ * positive and finite, a workspace smaller than the query; LNH_ERR_UNSUPPORTED for more than 2^24 pixels.
+ */
+enum {
+    LNH_NVS_DEPTH_RMSE = 0,    /* sqrt(sum (gt - pd)^2 / n) */
+    LNH_NVS_DEPTH_A1 = 1,      /* share of thresh < 1.25, 1.25^2, 1.25^3 */
+    LNH_NVS_DEPTH_A2 = 2,
+    LNH_NVS_DEPTH_A3 = 3,
+    LNH_NVS_DEPTH_SSIM = 4,    /* mean 1-D SSIM */
+    LNH_NVS_INTENSITY_MAE = 5, /* sum |gt_i s - pd_i s| / n */
+    LNH_NVS_CHAMFER = 6,       /* points_row[LNH_PTS_CHAMFER] */
+    LNH_NVS_FSCORE = 7,        /* points_row[LNH_PTS_FSCORE] */
+    LNH_NVS_CROP_R0 = 8,       /* the bounding rectangle of the masked pixels (0 0 0 0 for an empty mask) */
+    LNH_NVS_CROP_C0 = 9,
+    LNH_NVS_CROP_H = 10,
+    LNH_NVS_CROP_W = 11,
+    LNH_NVS_N = 12,            /* masked pixels */
+    LNH_NVS_DATA_RANGE = 13,   /* of the clamped ground truth (NaN for an empty mask) */
+    LNH_NVS_SUM_SQ = 14,       /* the two fp64 sums the rmse and the mae are made of */
+    LNH_NVS_SUM_ABS = 15,
+    LNH_NVS_FRAMES = 16,       /* 1 per row: the accumulator's frame count */
+    LNH_NVS_BAD = 17,          /* 1 if the means cannot use the row: a non-finite metric, n < 7, an empty mask, masked pixels
+                                  that do not fill their rectangle, or a bad points row */
+    LNH_NVS_SLOTS = 18
+};
+LNH_API uint64_t lnh_nvs_eval_workspace_bytes(uint32_t H, uint32_t W);
+LNH_API int lnh_nvs_eval_frame(const float *gt_pano, const float *pd_pano, const float *gt_int, const float *pd_int,
+                               const uint8_t *mask, uint32_t H, uint32_t W, float intensity_scale, void *workspace,
+                               uint64_t workspace_bytes, lnh_stream_t stream);
+LNH_API int lnh_nvs_eval_ssim(const float *gt_pano, const float *pd_pano, const uint8_t *mask, uint32_t H, uint32_t W,
+                              void *workspace, uint64_t workspace_bytes, lnh_stream_t stream);
+LNH_API int lnh_nvs_eval_finalize(uint32_t H, uint32_t W, const void *workspace, uint64_t workspace_bytes,
+                                  const double *points_row, double *accumulator, double *history, uint32_t max_frames,
+                                  lnh_stream_t stream);
+
 /* ------------------------------------------------------------------ training batches drawn on the device ----- */
 /*
  * Replaces KITTI360Dataset.collate / NeRFMVLDataset.collate + get_lidar_rays for a sequence that is preloaded on the

@@ -146,6 +146,9 @@ _SIGS = {
     "lnh_eval_points_project": [P, P, U32, U32, F32, F32, F32, I32, P, C.c_uint64, P, P, P],
     "lnh_eval_points_nn": [P, P, P, U32, P, C.c_uint64, P, P, P, P],
     "lnh_eval_points_finalize": [P, P, P, U32, F32, P, P, U32],
+    "lnh_nvs_eval_frame": [P, P, P, P, P, U32, U32, F32, P, C.c_uint64],
+    "lnh_nvs_eval_ssim": [P, P, P, U32, U32, P, C.c_uint64],
+    "lnh_nvs_eval_finalize": [U32, U32, P, C.c_uint64, P, P, P, U32],
     "lnh_lidar_sample_batch": [P, P, I32, I32, U32, U32, F32, F32, P, P, U32, U32, I32, I32, I32, I32, I32, P, P, P, P],
     "lnh_lidar_frame_rays": [P, I32, I32, U32, U32, F32, F32, P, P],
 }
@@ -155,6 +158,8 @@ _OPTIONAL = {"lnh_lidar_eval_frame": "frame evaluation", "lnh_lidar_eval_ssim": 
              "lnh_lidar_eval_finalize": "frame evaluation", "lnh_lidar_eval_workspace_bytes": "frame evaluation",
              "lnh_eval_points_project": "points evaluation", "lnh_eval_points_nn": "points evaluation",
              "lnh_eval_points_finalize": "points evaluation", "lnh_eval_points_workspace_bytes": "points evaluation",
+             "lnh_nvs_eval_frame": "NVS evaluation", "lnh_nvs_eval_ssim": "NVS evaluation",
+             "lnh_nvs_eval_finalize": "NVS evaluation", "lnh_nvs_eval_workspace_bytes": "NVS evaluation",
              "lnh_lidar_sample_batch": "batch sampling", "lnh_lidar_frame_rays": "batch sampling",
              "lnh_march_rays_train_ordered": "ordered marching",
              "lnh_lidar_to_pano_masked": "bbox-mask conversion", "lnh_lidar_to_pano_fpa": "fpa conversion",
@@ -202,7 +207,8 @@ EXPORTS = sorted(list(_SIGS) + ["lnh_version", "lnh_last_error", "lnh_arch", "ln
                                  "lnh_grid_backward_set_slice_entries", "lnh_grid_forward_set_schedule",
                                  "lnh_wgrad_workspace_bytes",
                                  "lnh_lidar_loss_ex_workspace_bytes", "lnh_lidar_eval_workspace_bytes",
-                                 "lnh_eval_points_workspace_bytes", "lnh_lidar_to_pano_fpa_workspace_size",
+                                 "lnh_eval_points_workspace_bytes", "lnh_nvs_eval_workspace_bytes",
+                                 "lnh_lidar_to_pano_fpa_workspace_size",
                                  "lnh_marching_cubes_workspace_size", "lnh_raycast_workspace_size",
                                  "lnh_mesh_filter_workspace_size",
                                  "lnh_knn_workspace_size", "lnh_raydrop_workspace_size", "lnh_raydrop_param_count",
@@ -266,6 +272,9 @@ def lib():
         if hasattr(L, "lnh_eval_points_workspace_bytes"):
             L.lnh_eval_points_workspace_bytes.argtypes = [U32, U32]
             L.lnh_eval_points_workspace_bytes.restype = C.c_uint64
+        if hasattr(L, "lnh_nvs_eval_workspace_bytes"):
+            L.lnh_nvs_eval_workspace_bytes.argtypes = [U32, U32]
+            L.lnh_nvs_eval_workspace_bytes.restype = C.c_uint64
         if hasattr(L, "lnh_lidar_to_pano_fpa_workspace_size"):
             L.lnh_lidar_to_pano_fpa_workspace_size.argtypes = [C.c_uint64, U32, U32]
             L.lnh_lidar_to_pano_fpa_workspace_size.restype = C.c_uint64
@@ -369,6 +378,12 @@ EVAL_SLOTS = len(EVAL_SLOT_NAMES)
 PTS_SLOT_NAMES = ("chamfer", "fscore", "precision", "recall", "mean_pred", "mean_gt", "count_pred", "count_gt", "frames",
                   "bad")
 PTS_SLOTS = len(PTS_SLOT_NAMES)
+# lnh_nvs_eval_* (include/lidarnerf_hip.h, LNH_NVS_*): row layout of the NVS baselines' meters; the first eight are the keys of
+# the reference's eval_points_and_pano
+NVS_SLOT_NAMES = ("depth_rmse", "depth_a1", "depth_a2", "depth_a3", "depth_ssim", "intensity_mae", "chamfer", "f_score",
+                  "crop_r0", "crop_c0", "crop_h", "crop_w", "n", "data_range", "sum_sq", "sum_abs", "frames", "bad")
+NVS_SLOTS = len(NVS_SLOT_NAMES)
+NVS_METRICS = NVS_SLOT_NAMES[:8]
 
 
 # lnh_lidar_loss_options (include/lidarnerf_hip.h): criterion codes, flags, the struct

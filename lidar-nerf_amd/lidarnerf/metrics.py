@@ -375,10 +375,18 @@ class FramePointsEvaluator:
         depth, gt = pred_depth.detach().float().contiguous(), images_lidar.detach().float().contiguous()
         if self.state is None:
             self._alloc(depth.device)
-        ws, ws_bytes = self._ws.data_ptr(), self._ws.numel() * 8
+        self._project(depth, gt)
+        self._search()
+
+    def _project(self, depth, gt):
+        """The first of update()'s two halves: both images back-projected into self.clouds, their lengths into self.counts."""
         _hip.call("lnh_eval_points_project", depth.data_ptr(), gt.data_ptr(), self.H, self.W, self.intrinsics[0],
-                  self.intrinsics[1], self.scale, int(self.nerf_mvl), ws, ws_bytes, self.clouds[0].data_ptr(),
-                  self.clouds[1].data_ptr(), self.counts.data_ptr())
+                  self.intrinsics[1], self.scale, int(self.nerf_mvl), self._ws.data_ptr(), self._ws.numel() * 8,
+                  self.clouds[0].data_ptr(), self.clouds[1].data_ptr(), self.counts.data_ptr())
+
+    def _search(self):
+        """The second half: nearest neighbours between self.clouds[0] and [1] (self.counts points each), the frame's row."""
+        N, ws, ws_bytes = self.H * self.W, self._ws.data_ptr(), self._ws.numel() * 8
         _hip.call("lnh_eval_points_nn", self.clouds[0].data_ptr(), self.clouds[1].data_ptr(), self.counts.data_ptr(), N, ws,
                   ws_bytes, self.dist[0].data_ptr(), self.idx[0].data_ptr(), self.dist[1].data_ptr(), self.idx[1].data_ptr())
         _hip.call("lnh_eval_points_finalize", self.dist[0].data_ptr(), self.dist[1].data_ptr(), self.counts.data_ptr(), N,

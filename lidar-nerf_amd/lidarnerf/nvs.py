@@ -23,6 +23,7 @@ from . import convert
 from .knn import PointCloudIndex, _check_k, _cloud
 from .raycast import RaycastingScene
 from .raydrop import IN_FEATURES
+from .nvs_eval import FieldNVS, NVSFrameEvaluator, eval_points_and_pano, evaluate_nvs  # noqa: F401 (the evaluation)
 
 CLOUD_KEYS = ("points", "point_intensities", "local_points", "local_point_intensities")
 
@@ -235,6 +236,10 @@ class MeshNVS:
                 "point_intensities": local_inten, "local_points": local_points, "local_point_intensities": local_inten,
                 "hit_dict": out["hit_dict"]}
 
+    def evaluate(self, frames, raydrop=True, nerf_mvl=False, **predict_kwargs):
+        """nvs_eval.evaluate_nvs on this model: (mean metrics under the reference's eight keys, the evaluator)."""
+        return evaluate_nvs(self, frames, raydrop=raydrop, nerf_mvl=nerf_mvl, **predict_kwargs)
+
 
 PCGEN_KEYS = ("pano", "intensities") + CLOUD_KEYS
 
@@ -343,9 +348,10 @@ class PointCloudNVS:
         return torch.cat([rows, target[:, None]], dim=1)[gt > -1]
 
     @torch.no_grad()
-    def predict_frame_with_raydrop(self, lidar_K, lidar_pose, lidar_H, lidar_W, raydrop=None):
-        """lidarnvs_pcgen.py:131-194: pano and intensities multiplied by the mask `output > 0.5` — unless the mask is zero
-        everywhere, which leaves the frame as it is (the reference's rule) — and turned back into the clouds."""
+    def predict_images_with_raydrop(self, lidar_K, lidar_pose, lidar_H, lidar_W, raydrop=None):
+        """The images of predict_frame_with_raydrop without its clouds: pano and intensities multiplied by the mask `output >
+        0.5` — unless the mask is zero everywhere, which leaves the frame as it is (the reference's rule).  Nothing reads the
+        host (the clouds' length is the one host read of predict_frame_with_raydrop)."""
         model = self.raydrop if raydrop is None else raydrop
         if model is None:
             raise RuntimeError("PointCloudNVS.predict_frame_with_raydrop: no ray-drop model")
@@ -359,7 +365,16 @@ class PointCloudNVS:
             raise ValueError(f"PointCloudNVS.predict_frame_with_raydrop: the model must return [{H * W}, 1] outputs")
         keep = (out.detach().to(self.device, torch.float32) > 0.5).reshape(H, W)
         keep = torch.where(keep.any(), keep, torch.ones_like(keep)).to(torch.float32)
-        pano, intensities = frame["pano"] * keep, frame["intensities"] * keep
-        result = {"pano": pano, "intensities": intensities}
-        result.update(self._clouds(pano, intensities, lidar_K, pose))
+        return {"pano": frame["pano"] * keep, "intensities": frame["intensities"] * keep}
+
+    @torch.no_grad()
+    def predict_frame_with_raydrop(self, lidar_K, lidar_pose, lidar_H, lidar_W, raydrop=None):
+        """lidarnvs_pcgen.py:131-194: the masked images of predict_images_with_raydrop, turned back into the clouds."""
+        pose = _pose(lidar_pose, self.device)
+        result = self.predict_images_with_raydrop(lidar_K, pose, lidar_H, lidar_W, raydrop)
+        result.update(self._clouds(result["pano"], result["intensities"], lidar_K, pose))
         return result
+
+    def evaluate(self, frames, raydrop=True, nerf_mvl=False, **predict_kwargs):
+        """nvs_eval.evaluate_nvs on this model: (mean metrics under the reference's eight keys, the evaluator)."""
+        return evaluate_nvs(self, frames, raydrop=raydrop, nerf_mvl=nerf_mvl, **predict_kwargs)
